@@ -2,7 +2,7 @@
 """Headline benchmark: images/s of the whole Multi-HMR forward (ViT-L 896x896, batch 32 per GPU, 8 pinned
 queries per image -> HPH -> SMPL-X LBS), BASELINE.json config #4 (`multiHMR_896_L`, image-sharded over N GPUs).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one full `Model.forward` over one batch of synthetic images already resident in HBM (seeded N(0,1) pixels, seeded
@@ -10,13 +10,16 @@ random weights of the named architecture, synthetic SMPL-X arrays), detections p
 `idx=` / `is_training=True` hook (model.py:141-151), plus -- for N > 1 -- the RCCL all-gather that collates every rank's persons.
 Rank 0 prints ONE JSON line.
 
-`dtype` is f16: the MFMA operand format whose outputs meet the north star's 1e-3 parity (tests/test_gpu_parity_fullsize.py; the
-line's `parity` object is measured in this very process against the CPU oracle on image 0 of the benchmark batch with the
-benchmark weights).  bf16 operands run the same kernels ~4 % faster and are reported beside (`other_precision`), but miss 1e-3.
+`dtype` is f16: the MFMA operand format whose outputs meet the north star's 1e-3 parity (tests/test_gpu_parity_fullsize.py; with
+`--full` the line's `parity` object is measured in this very process against the CPU oracle on image 0 of the benchmark batch with
+the benchmark weights).  bf16 operands run the same kernels ~4 % faster and are reported beside with `--full` (`other_precision`),
+but miss 1e-3.
 
-Nothing but the K forwards (and the collation) is inside the timed region: the per-kernel hipEvent brackets that feed `roofline`
-are collected in separate profiled passes afterwards, as are the other BASELINE configurations (`configs`), the SMPL-X layer alone
-(`lbs`, BASELINE.json's second metric ms/person) and the CPU baseline.
+Nothing but the K forwards (and the collation) is inside the timed region.  A plain run stops there: set-up, W warm-up steps, the K
+timed steps, the outputs of the last step if `--dump-outputs DIR` is given, the line.  Everything else is measured only with `--full`,
+in separate passes after the timed region: the per-kernel hipEvent brackets that feed `roofline`, the inference mode, the SMPL-X layer
+alone (`lbs`, BASELINE.json's second metric ms/person), the other precision, the other BASELINE configurations (`configs`), the
+batch-1 latency, and the CPU baseline with the `parity` check.
 """
 from __future__ import annotations
 
@@ -40,6 +43,7 @@ import synthetic  # noqa: E402
 
 PEAK_MFMA_TFLOPS = 2500.0     # bf16/f16 dense, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
 PEAK_HBM_GBS = 8000.0         # HBM3E spec, same table (6.29 TB/s measured float4 copy)
+DUMP_BUDGET = 64 * 2 ** 20    # --dump-outputs: bytes of array data in all
 PARITY_KEYS = ["scores", "offset", "loc", "dist", "shape", "expression", "rotmat", "transl", "v3d", "j3d", "j2d"]
 #: the other single-GPU BASELINE.json configurations: name, backbone, S, images, persons / image
 OTHER_CONFIGS = [("cfg2 multiHMR_672_S", "dinov2_vits14", 672, 16, 8), ("cfg3 multiHMR_672_L", "dinov2_vitl14", 672, 32, 8),
@@ -108,6 +112,19 @@ def prof_collect():
     _lib.check(_lib.lib().mhmr_prof_collect(C.byref(n), C.byref(ms), C.byref(work)), "prof_collect")
     _lib.lib().mhmr_prof_enable(-1)
     return n.value, ms.value, work.value
+
+
+def dump_outputs(out, d):
+    """--dump-outputs: the arrays the timed path returned in its last step, as DIR/<name>.npy in float32.  Above DUMP_BUDGET in all,
+    every array keeps the same fixed, seeded sample of its leading rows (images for `scores`, persons for the rest), sized to fit."""
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in out.items() if torch.is_tensor(v) and not k.startswith("_")}
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(d, exist_ok=True)
+    for k, a in sorted(arrs.items()):
+        if total > DUMP_BUDGET and a.ndim and a.shape[0] > 1:
+            n = max(1, a.shape[0] * DUMP_BUDGET // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], n, replace=False))]
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
 
 
 def build_model(backbone, S, dtype, smplx_data, mean_params, dev):
@@ -196,13 +213,19 @@ def main():
     ap.add_argument("--img-size", type=int, default=896)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--persons", type=int, default=8, help="pinned detections per image")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle legs (cpu_baseline AND parity)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the roofline side measurements, the other configs and the other precision")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements: roofline passes, inference mode, LBS, other precision, "
+                         "other configs, batch-1 latency, CPU baseline + parity (a plain run times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle legs (cpu_baseline AND parity)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the roofline side measurements, the other configs and the other precision")
     ap.add_argument("--only-latency", action="store_true", help="print the latency_b1 object alone (A/B sessions)")
     ap.add_argument("--only-headline-kernels", action="store_true",
-                    help="profiling runs (rocprofv3 --pmc): the headline forward and its roofline passes only, so that per-kernel "
+                    help="with --full, profiling runs (rocprofv3 --pmc): the headline forward and its roofline passes only, so that per-kernel "
                          "averages are not mixed with the other configurations' shapes")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.only_latency:
         dev = torch.device("cuda", 0)
@@ -298,6 +321,8 @@ def main():
     drain()               # every step's persons are collated on every rank inside the timed region
     barrier()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out_last, args.dump_outputs)
     compute_ms = sum(a.elapsed_time(b) for a, b in compute_ev) if compute_ev else None
     if world > 1:
         t = torch.tensor([dt, compute_ms], device=dev, dtype=torch.float64)
@@ -327,12 +352,13 @@ def main():
                                "collation": "async RCCL all_gather of counts + padded person records, overlapped with the next step",
                                "ranks_verified_by_all_reduce": ranks_seen}
 
-    if rank == 0 and stub:
+    if stub:
+        result["stub"] = True
+    if rank == 0 and stub and args.full:
         # stub mode: rank 0's extra passes are a few more calls of the stand-in (the other ranks wait at the barrier below)
         for _ in range(4):
             model(x, idx=idx, K=K, is_training=True)
-        result["stub"] = True
-    if rank == 0 and not stub:
+    if rank == 0 and not stub and args.full:
         # ---- profiled passes, OUTSIDE the timed region: hipEvent brackets around every GEMM / attention launch ----
         # `launches`, `algorithmic_flops_per_launch`, `share_of_step` are PER FORWARD (the brackets run over `profiled_forwards` forwards)
         reps = 2
@@ -366,7 +392,7 @@ def main():
             "traffic": pmc.get("_attention_bytes_per_call") if pmc else None, "traffic_source": pmc_src,
             "launches": n_a // reps, "profiled_forwards": reps,
             "avg_launch_ms": round(ms_a / max(n_a, 1), 4), "share_of_step": round(ms_a / reps / ms_step, 3)}
-    extras = rank == 0 and not stub and not args.no_extras and not args.only_headline_kernels
+    extras = args.full and rank == 0 and not stub and not args.no_extras and not args.only_headline_kernels
     if extras and world == 1:
         result["inference_mode"] = inference_bench(model, x, K, out_last, B, q, dev, steps=min(args.steps, 20))
     if extras:
@@ -378,7 +404,7 @@ def main():
     if world > 1:
         torch.distributed.barrier()
 
-    if rank == 0 and world == 1 and not stub and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not stub and not args.no_cpu_baseline:
         result["cpu_baseline"], result["parity"] = cpu_baseline_and_parity(args, smplx_data, mean_params, model, x, K, idx, out_last)
     if extras and world == 1:
         # release the headline model's workspace before the other configurations

@@ -2,7 +2,7 @@
 
 What runs is bench.py's own code: the per-step asynchronous collation (`collate.allgather_persons_async`, waited one step later),
 drain + barrier on both sides of the timed region, the all_reduce(MAX) of the clock, rank 0's extra passes while the other ranks
-wait at the barrier behind them, the single JSON line of rank 0, destroy_process_group.  A hang or a rank-divergent collective in
+wait at the barrier behind them (`--full`), the single JSON line of rank 0, destroy_process_group.  A hang or a rank-divergent collective in
 that flow is found here, not on the 8-GPU node (which the builder never sees).  Both launch forms are covered: the driver's
 `python -m torch.distributed.run ... bench.py --gpus N` and the bare `python bench.py --gpus N` that starts its own ranks."""
 import json
@@ -14,7 +14,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--steps", "3", "--warmup", "2", "--batch", "4", "--persons", "3", "--img-size", "224"]
+ARGS = ["--steps", "3", "--warmup", "2", "--batch", "4", "--persons", "3", "--img-size", "224", "--full"]
 
 
 def _free_port():
@@ -49,3 +49,17 @@ def test_bench_starts_its_own_ranks_in_stub_mode():
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + ARGS
     _check(subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300), 2)
+
+
+def test_plain_bench_run_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """Without --full: no extra passes; --dump-outputs writes rank 0's outputs of the LAST timed step (the stand-in fills every person
+    tensor with its call number: warm-up 2 + steps 3 -> 5), one float32 .npy per output array."""
+    import numpy as np
+    env = dict(os.environ, MHMR_BENCH_STUB="1")
+    env.pop("WORLD_SIZE", None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", str(tmp_path)] + ARGS[:-1]
+    _check(subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300), 2)
+    names = sorted(p.name for p in tmp_path.iterdir())
+    assert names == sorted(f"{k}.npy" for k in ("scores", "loc", "transl", "transl_pelvis", "rotvec", "expression", "shape", "j3d", "j2d", "v3d"))
+    j3d = np.load(tmp_path / "j3d.npy")
+    assert j3d.dtype == np.float32 and j3d.shape == (4 * 3, 127, 3) and (j3d == 5).all()

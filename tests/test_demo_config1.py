@@ -1,7 +1,7 @@
 """BASELINE.json config 1: `multiHMR_672_S on example_data/ via demo.py`.  Golden vectors = the reference's own demo.open_image ->
 get_camera_parameters -> forward_model run verbatim on its seven example photographs (tests/golden/make_golden_demo.py).
 
-* CPU (build container only: the photographs live under /root/reference): the drop-in's preprocessing -- host tables + the integer
+* CPU (the photographs are stored under tests/golden/example_data/): the drop-in's preprocessing -- host tables + the integer
   two-pass algorithm the kernel implements -- reproduces the reference's padded uint8 image of ALL SEVEN photographs bit for bit.
 * GPU: for the two photographs whose decoded pixels are part of the fixture, ``Preprocessor`` (mhmr_preprocess_u8) is bit-exact
   and ``forward_model`` returns the same persons (count, order) with every tensor within 1e-3 (f16 operands)."""
@@ -20,10 +20,9 @@ from oracle import preprocess_ref as ref
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "demo_672_s.npz"))
 S = 672
-EXAMPLES = "/root/reference/example_data"
+EXAMPLES = os.path.join(os.path.dirname(__file__), "golden", "example_data")
 
 
-@pytest.mark.skipif(not os.path.isdir(EXAMPLES), reason="the reference's example photographs exist only in the build container")
 def test_preprocessing_of_the_seven_example_photographs_is_bit_exact():
     from PIL import Image
     paths = sorted(glob.glob(os.path.join(EXAMPLES, "*.jpg")))

@@ -7,12 +7,12 @@ TAG=${1:-r04}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT/pmc/lbs $OUT/trace
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --only-headline-kernels"
+BENCH="python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --only-headline-kernels"
 LBS="python $R/tools/lbs_bench.py 160"
-# (a) the headline forward alone: per-kernel averages comparable with the bench line's avg_launch_ms; (b) the whole default command
+# (a) the headline forward alone: per-kernel averages comparable with the bench line's avg_launch_ms; (b) the whole --full command
 if [ "$2" != "pmc" ]; then
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o headline --output-format csv -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --only-headline-kernels > $OUT/trace/headline.json 2> $OUT/trace/err_headline.txt
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/trace/bench.json 2> $OUT/trace/err.txt
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o headline --output-format csv -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --only-headline-kernels > $OUT/trace/headline.json 2> $OUT/trace/err_headline.txt
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench --output-format csv -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/trace/bench.json 2> $OUT/trace/err.txt
 fi
 # counter passes (every kernel of the forward runs on the caller's stream: one kernel at a time)
 SQSET="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"

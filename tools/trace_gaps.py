@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Kernel-trace digest of `bench.py --steps N --no-extras --no-cpu-baseline` under `rocprofv3 --kernel-trace --output-format csv -d OUT`:
+"""Kernel-trace digest of `bench.py --full --steps N --no-extras --no-cpu-baseline` under `rocprofv3 --kernel-trace --output-format csv -d OUT`:
 the last `forwards` forwards of the trace (found by the attention launches: 24 per ViT-L forward) -- span, busy time, idle time between
 consecutive kernels, overlap (a kernel starting before its predecessor ended), and per-kernel averages.
    python tools/trace_gaps.py OUT [forwards=3] [attention launches per forward=24]"""
