@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define MHMR_VERSION 106   /* 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
+#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
 #define MHMR_OK 0
 #define MHMR_ERR_BAD_ARG (-1)
@@ -478,6 +478,51 @@ int mhmr_preprocess_u8(const void* img, int H, int W, const int* kh, const int* 
  * ---------------------------------------------------------------------------------------------------------- */
 int mhmr_eval_mesh_errors(const float* pred, const float* gt, const float* pred_center, const float* gt_center, int M,
                           int V, float* pve, float* pa_pve, float* Rts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Mesh overlay (reference demo.py:128-158 overlay_human_meshes -> utils/render.py:175-315 render_meshes, which
+ * draws with pyrender / OpenGL): P meshes sharing one face array [F][3], person p drawn into image
+ * image_index[p], blended over uint8 RGB images [B][H][W][3].  One sample per pixel.  The render is defined by
+ * multi_hmr_amd/render.py (the contract) and restated in numpy by tests/render_oracle.py:
+ *   camera X = R x + t (OpenCV: X right, Y down, Z forward), u = fx X / Z + cx, v = fy Y / Z + cy, pixel (r, c)
+ *   sampled at (c + 0.5, r + 0.5); faces with a vertex at Z < znear are dropped; back faces
+ *   (dot((b-a) x (c-a), a) >= 0) culled if cull_back; coverage: edge functions > 0, or == 0 on a top-left edge;
+ *   the winner of a pixel is the smallest key (float_bits(Z) << 32) | (p F + f), Z perspective-correct, kept
+ *   only if znear <= Z <= zfar; glTF metallic-roughness shading with one directional light along the view
+ *   axis plus ambient; the reference's 3x3 mask smoothing; the fp32 alpha blend, every operation rounded.
+ * Geometry (transform, projection, edge functions, depth) is fp64; shading and the blend are fp32.
+ * verts: person p's vertex v at verts[p * vstride + 3 v + axis] (vstride >= 3 V: the v3d block is read in place).
+ * adj_off [V + 1] / adj: for every vertex the (3 face + corner) entries of its incident faces, ascending
+ * (smooth normals only; may be NULL when smooth == 0).  Rt [B][3][4] = [R | t] or NULL (identity, zero).
+ * key_out [B][H][W] (~0 where nothing is drawn) and rgb_out [B][H][W][3] (the shaded colour before the blend,
+ * 0 where nothing is drawn) are optional.  img_out may equal img_in.  P F < 2^32 - 1, B <= 65535,
+ * MHMR_ERR_BAD_SHAPE otherwise; the workspace holds the camera-space vertices and normals, the key buffer and a
+ * list of the faces whose bounding box is large.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, H, W;
+    int P, V, F;
+    const float* verts;
+    long long vstride;
+    const int* faces;
+    const int* adj_off;
+    const int* adj;
+    const int* image_index;
+    const float* K;
+    const float* Rt;
+    const float* colors;
+    float alpha, intensity, ambient, metallic, roughness, znear, zfar;
+    int smooth, cull_back;
+    const unsigned char* img_in;
+    unsigned char* img_out;
+    void* workspace;
+    long long workspace_bytes;
+    unsigned long long* key_out;
+    unsigned char* rgb_out;
+} mhmr_render_desc;
+
+long long mhmr_render_workspace_bytes(const mhmr_render_desc* d);
+int mhmr_render_meshes(const mhmr_render_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Measurement: hipEvent brackets around every launch of one kernel family (0 = GEMM, 1 = attention, 2 = LBS

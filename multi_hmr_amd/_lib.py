@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "anny.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "anny.hip", "render.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -31,8 +31,9 @@ class MhmrError(RuntimeError):
 #: No SLP vectoriser in any translation unit (csrc/mhmr_common.h has the reasons and refuses a build without -DMHMR_NO_SLP): its
 #: op_sel-swizzled v_pk_*_f32 code returned wrong values in two kernels on gfx950, and the scalar build is 2 % faster.
 COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP"]
-#: per-translation-unit extra flags
-EXTRA_FLAGS = {}
+#: per-translation-unit extra flags.  render.hip: every step rounded on its own (the render contract's fp64 geometry and fp32 blend
+#: are restated operation by operation in numpy by the tests; an FMA would change the last bit).
+EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -129,6 +130,14 @@ class LbsConsts(C.Structure):
                 [("pose_levels", _i)])
 
 
+class RenderDesc(C.Structure):
+    _fields_ = ([(n, _i) for n in ("B", "H", "W", "P", "V", "F")] + [("verts", _vp), ("vstride", C.c_longlong)] +
+                [(n, _vp) for n in ("faces", "adj_off", "adj", "image_index", "K", "Rt", "colors")] +
+                [(n, _f) for n in ("alpha", "intensity", "ambient", "metallic", "roughness", "znear", "zfar")] +
+                [("smooth", _i), ("cull_back", _i), ("img_in", _vp), ("img_out", _vp), ("workspace", _vp),
+                 ("workspace_bytes", C.c_longlong), ("key_out", _vp), ("rgb_out", _vp)])
+
+
 _SIGS = {
     "mhmr_version": ([], _i),
     "mhmr_source_hash": ([], C.c_char_p),
@@ -170,6 +179,8 @@ _SIGS = {
     "mhmr_anny_scores": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
     "mhmr_anny_camera": ([_vp, _i, _i, _f, _vp, _vp, _vp], _i),
     "mhmr_anny_decode": ([_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i] + [_vp] * 6 + [_vp], _i),
+    "mhmr_render_workspace_bytes": ([C.POINTER(RenderDesc)], C.c_longlong),
+    "mhmr_render_meshes": ([C.POINTER(RenderDesc), _vp], _i),
     "mhmr_prof_enable": ([_i], _i),
     "mhmr_prof_collect": ([C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)], _i),
 }

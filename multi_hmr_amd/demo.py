@@ -1,9 +1,12 @@
-"""Drop-in for the inference helpers of the reference ``demo.py`` (lines 27-126): ``open_image``,
-``get_camera_parameters``, ``load_model``, ``forward_model``.  Rendering / CLI (demo.py:128-386) is out of scope."""
+"""Drop-in for the reference ``demo.py``: the inference helpers (lines 27-126: ``open_image``, ``get_camera_parameters``,
+``load_model``, ``forward_model``), ``overlay_human_meshes`` (lines 128-158, drawn by ``render.render_batch`` on the GPU) and the
+command line (lines 231-386: ``python -m multi_hmr_amd.demo``, writing ``[input | overlay]`` side by side).  Not carried over (no
+cv2 / trimesh here): the rotating video, the extra side view, GLB / mesh export and the distance annotation."""
 from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 
 from .model import Model
@@ -47,3 +50,87 @@ def forward_model(model, input_image, camera_parameters, det_thresh=0.3, nms_ker
             humans = model(input_image, is_training=False, nms_kernel_size=int(nms_kernel_size), det_thresh=det_thresh,
                            K=camera_parameters)
     return humans
+
+
+def _stacked(tensors):
+    """[P, V, 3] over the persons' vertex tensors: a strided view when they are equally spaced rows of one block (the forward's
+    output block), a device-side stack otherwise; never a host copy of vertices that are already on the device."""
+    t0 = tensors[0]
+    if all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        if t0.is_contiguous() and all(t.shape == t0.shape and t.dtype == t0.dtype and t.is_contiguous() and
+                                      t.untyped_storage().data_ptr() == t0.untyped_storage().data_ptr() for t in tensors):
+            step = (tensors[1].storage_offset() - t0.storage_offset()) if len(tensors) > 1 else t0.numel()
+            if step >= t0.numel() and all(t.storage_offset() == t0.storage_offset() + j * step for j, t in enumerate(tensors)):
+                return t0.as_strided((len(tensors),) + tuple(t0.shape), (step,) + tuple(t0.stride()))
+        return torch.stack(tensors)
+    return torch.stack([torch.as_tensor(np.asarray(t.cpu() if torch.is_tensor(t) else t, np.float32)) for t in tensors]).cuda()
+
+
+def overlay_human_meshes(humans, faces, K, model, img_pil, unique_color=False, alpha=0.8, _color=None):
+    """demo.py:128-158: the persons' meshes (``verts_smplx`` if present, else ``v3d``) drawn over ``img_pil`` with the camera
+    K[0] -> ``(np.uint8 [H, W, 3], colours)``.  One ``render.render_batch`` call on the vertices' device.  Unlike the reference,
+    a rendering error is raised, not printed."""
+    from .render import PALETTE, render_batch
+    if _color is None:
+        _color = [PALETTE[0] for _ in range(len(humans))] if unique_color else PALETTE
+    img = np.asarray(img_pil)
+    if len(humans) == 0:
+        return img, _color
+    name = "verts_smplx" if "verts_smplx" in humans[0] else "v3d"
+    verts = _stacked([h[name] for h in humans])
+    Kc = torch.as_tensor(K)[0].detach().float().cpu().reshape(1, 3, 3)
+    images = torch.from_numpy(np.array(img[..., :3], np.uint8))[None].to(verts.device)
+    cols = [_color[j % len(_color)] for j in range(len(humans))]
+    out = render_batch(images, verts, torch.zeros(len(humans), dtype=torch.int32), Kc, faces, colors=cols, alpha=alpha)
+    return out[0].cpu().numpy(), _color
+
+
+def main(argv=None):
+    """demo.py:231-386 without the video / extra view / mesh export options: every image of --img_folder -> forward -> overlay ->
+    ``<out_folder>/<image>_<model>.png`` = [input | overlay]."""
+    from argparse import ArgumentParser
+    from PIL import Image
+    from .preprocess import open_image
+    parser = ArgumentParser()
+    parser.add_argument("--model_name", type=str, default="multiHMR_896_L_synth")
+    parser.add_argument("--img_folder", type=str, default="example_data")
+    parser.add_argument("--out_folder", type=str, default="demo_out")
+    parser.add_argument("--det_thresh", type=float, default=0.3)
+    parser.add_argument("--nms_kernel_size", type=float, default=3)
+    parser.add_argument("--fov", type=float, default=60)
+    parser.add_argument("--alpha", type=float, default=1.0)
+    parser.add_argument("--unique_color", type=int, default=0, choices=[0, 1])
+    args = parser.parse_args(argv)
+    assert torch.cuda.is_available()
+    suffixes = (".jpg", ".jpeg", ".png", ".webp")
+    if os.path.isfile(args.img_folder) and args.img_folder.lower().endswith(suffixes):
+        l_img_path = [os.path.basename(args.img_folder)]
+        args.img_folder = os.path.dirname(args.img_folder)
+    else:
+        root_dir = os.path.abspath(args.img_folder)
+        l_img_path = sorted(os.path.relpath(os.path.join(r, f), root_dir) for r, _, fs in os.walk(root_dir) for f in fs
+                            if f.lower().endswith(suffixes) and not f.startswith("."))
+    model = load_model(args.model_name)
+    faces = model.smpl_layer["neutral_10"].bm_x.faces
+    model_name = os.path.basename(args.model_name)
+    os.makedirs(args.out_folder, exist_ok=True)
+    written = []
+    for img_path in l_img_path:
+        save_fn = os.path.join(args.out_folder, f"{img_path}_{model_name}.png")
+        os.makedirs(os.path.dirname(save_fn), exist_ok=True)
+        x, img_pil_visu = open_image(os.path.join(args.img_folder, img_path), model.img_size)
+        K = get_camera_parameters(model.img_size, fov=args.fov)
+        humans = forward_model(model, x, K, det_thresh=args.det_thresh, nms_kernel_size=args.nms_kernel_size)
+        ratio = max(img_pil_visu.size) / x.shape[-1]                     # demo.py:340-344: K for the full-resolution image
+        K[0, 0, 2] = img_pil_visu.size[0] / 2.0
+        K[0, 1, 2] = img_pil_visu.size[1] / 2.0
+        K[0, [0, 1], [0, 1]] = ratio * K[0, [0, 1], [0, 1]]
+        pred, _ = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha)
+        Image.fromarray(np.concatenate([np.asarray(img_pil_visu), pred], 1).astype(np.uint8)).save(save_fn)
+        print(f"{len(humans)} persons -> {save_fn}")
+        written.append(save_fn)
+    return written
+
+
+if __name__ == "__main__":
+    main()
