@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
+#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
 #define MHMR_OK 0
 #define MHMR_ERR_BAD_ARG (-1)
@@ -375,6 +375,19 @@ int mhmr_linear_f32(const float* X, int ldx, const int* row_idx, const float* W,
                     const float* R, int ldr, float* Y, int ldy, int M, int N, int K, int act, void* stream);
 int mhmr_layernorm_f32(const float* in, const float* w, const float* b, float* out, int rows, int C, float eps,
                        void* stream);
+/* The three person-head kernels behind mhmr_xattn_layers_forward / mhmr_hph_forward, with caller-chosen tables (inner = 32 heads):
+ *   mhmr_hph_self_attn:  qkv [P, 3 inner] (q | k | v) -> out [P, inner], softmax over the queries of each group gstart[g] .. gstart[g+1]
+ *                        (ngroups / nmax may be upper bounds: repeated gstart entries are empty groups).
+ *   mhmr_hph_cross_attn: q [P, inner], kv [B N, 2 inner] (k | v) -> out [P, inner] for the rows of the work items chunks[3 nchunks] =
+ *                        (image, first query, count <= 8; count-0 padding items only at the tail); rows of no work item are not
+ *                        written.
+ *   mhmr_hph_decode:     dec [P, ldd] = [pose6d(318) | betas(nb) | cam(3) | expr(10)] -> rotmat, rotvec, betas, expr, dist_pp, dist
+ *                        as in mhmr_hph_forward (K [B,3,3], det_b [P]).
+ * MHMR_ERR_BAD_SHAPE for heads <= 0, N <= 0, nb outside [0, 64] or ldd < 318 + nb + 3 + 10, before any launch. */
+int mhmr_hph_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads, void* stream);
+int mhmr_hph_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N, void* stream);
+int mhmr_hph_decode(const float* dec, int ldd, int nb, const float* K, const int* det_b, float fn, int nearness,
+                    float* rotmat, float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * SMPL-X layer.  Replaces SMPL_Layer.forward (blocks/smpl_layer.py:47-155) -> smplx.SMPLX.forward / lbs,

@@ -172,6 +172,9 @@ _SIGS = {
     "mhmr_xattn_layers_forward": ([C.POINTER(HphLayer)] + [_i] * 8 + [_vp] * 7 + [_i, _i, _vp, _i, _i, _vp], _i),
     "mhmr_linear_f32": ([_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mhmr_layernorm_f32": ([_vp, _vp, _vp, _vp, _i, _i, _f, _vp], _i),
+    "mhmr_hph_self_attn": ([_vp, _vp, _vp, _i, _i, _i, _vp], _i),
+    "mhmr_hph_cross_attn": ([_vp, _vp, _vp, _i, _vp, _i, _i, _vp], _i),
+    "mhmr_hph_decode": ([_vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "mhmr_lbs_forward": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp], _i),
     "mhmr_lbs_forward_fused": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp, _vp], _i),
     "mhmr_preprocess_u8": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i] + [_i] * 7 + [_vp, _vp, _vp, _vp], _i),

@@ -599,6 +599,19 @@ int mhmr_linear_f32(const float* X, int ldx, const int* row_idx, const float* W,
 int mhmr_layernorm_f32(const float* in, const float* w, const float* b, float* out, int rows, int C, float eps, void* stream) {
     return mhmr_launch_layernorm_f32(in, w, b, out, rows, C, eps, (hipStream_t)stream);
 }
+int mhmr_hph_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads, void* stream) {
+    if (heads <= 0) return MHMR_ERR_BAD_SHAPE;
+    return mhmr_launch_hph_self_attn(qkv, gstart, out, ngroups, nmax, heads, (hipStream_t)stream);
+}
+int mhmr_hph_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N, void* stream) {
+    if (heads <= 0 || N <= 0) return MHMR_ERR_BAD_SHAPE;
+    return mhmr_launch_hph_cross_attn(q, kv, chunks, nchunks, out, heads, N, (hipStream_t)stream);
+}
+int mhmr_hph_decode(const float* dec, int ldd, int nb, const float* K, const int* det_b, float fn, int nearness, float* rotmat,
+                    float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, void* stream) {
+    if (nb < 0 || nb > 64 || ldd < 318 + nb + 3 + 10) return MHMR_ERR_BAD_SHAPE;      // one thread per beta in a 64-thread block
+    return mhmr_launch_hph_decode(dec, ldd, nb, K, det_b, fn, nearness, rotmat, rotvec, betas, expr, dist_pp, dist, P, (hipStream_t)stream);
+}
 
 // `depth` x (pre-norm self-attention among the queries of one image, cross-attention over that image's N context
 // tokens, GELU feed-forward), each with a residual.  Shared by the Multi-HMR HPH (dim 1024, 8 heads, mlp 1024, depth 2,
@@ -646,6 +659,7 @@ int mhmr_hph_forward(const mhmr_hph_desc* d, const float* feat32, const float* z
     hipStream_t s = (hipStream_t)stream;
     const int C = d->C, dim = d->dim, inner = d->heads * 32, mlp = d->mlp;
     if (d->Ktok % 16 || d->Kc % 64 || C % 16 || dim % 64 || mlp % 16 || (2 * inner) % 128) return MHMR_ERR_BAD_SHAPE;
+    if (d->nb < 0 || d->nb > 64) return MHMR_ERR_BAD_SHAPE;          // the decode writes betas with one thread each of 64
     const int Mctx = (B * d->N + 127) / 128 * 128;
 
     // queries, mlp_offset input, context rows of the detected cells  (model.py:255-265, 500-517, 541-552)

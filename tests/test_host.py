@@ -1,5 +1,6 @@
 """-m "not gpu": host-side logic of the product -- the C-ABI library loads and exports every declared symbol, the
 load-time repacking is exact, the nn.Module surface matches the reference's, and nothing computes on the CPU."""
+import ctypes
 import os
 import re
 
@@ -26,6 +27,30 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert lib.mhmr_prof_enable(99) == -1
     # the library says which sources it was built from, and build() trusts that, not file times
     assert lib.mhmr_source_hash().decode() == _lib.source_hash() == _lib.built_source_hash()
+
+
+def test_person_head_entry_points_reject_bad_shapes_before_any_launch():
+    """The person-head building blocks (and mhmr_hph_forward's nb bound) return MHMR_ERR_BAD_SHAPE before touching the device, so
+    these calls run without a GPU.  nb > 64 would leave betas past the 64-thread decode block unwritten; a short ldd reads the next row."""
+    _lib.build()
+    lib = _lib.lib()
+    BAD = -2
+    assert lib.mhmr_hph_self_attn(None, None, None, 1, 1, 0, None) == BAD
+    assert lib.mhmr_hph_self_attn(None, None, None, 1, 1, -8, None) == BAD
+    assert lib.mhmr_hph_cross_attn(None, None, None, 1, None, 0, 64, None) == BAD
+    assert lib.mhmr_hph_cross_attn(None, None, None, 1, None, 8, 0, None) == BAD
+    assert lib.mhmr_hph_cross_attn(None, None, None, 1, None, 8, -1, None) == BAD
+    dec = lambda ldd, nb, P=1: lib.mhmr_hph_decode(None, ldd, nb, None, None, 1.0, 0, None, None, None, None, None, None, P, None)
+    assert dec(400, -1) == BAD
+    assert dec(400, 65) == BAD
+    assert dec(318 + 10 + 13 - 1, 10) == BAD
+    assert dec(318 + 11 + 13 - 1, 11) == BAD
+    assert dec(318 + 64 + 13, 64, P=0) == 0            # the bounds are inclusive; P = 0 launches nothing
+    d = _lib.HphDesc()
+    d.Ktok, d.Kc, d.C, d.dim, d.heads, d.mlp, d.depth = 16, 64, 16, 64, 2, 16, 1
+    for nb in (65, -1):
+        d.nb, d.Ndec = nb, 318 + nb + 13
+        assert lib.mhmr_hph_forward(ctypes.byref(d), *([None] * 6), 1, None, 1, 1, None, 1, None, 1, *([None] * 9)) == BAD
 
 
 def test_pos_embed_bicubic_matches_torch_scale_factor_form():
