@@ -1,10 +1,10 @@
 """MI355X-native Multi-HMR batched inference (drop-in for naver/multi-hmr ``model.Model`` / ``demo.forward_model``)."""
 from .model import Model  # noqa: F401
-from .demo import forward_model, get_camera_parameters, load_model, open_image, overlay_human_meshes  # noqa: F401
-from .render import render_batch, render_meshes  # noqa: F401
+from .demo import create_rotating_video, forward_model, get_camera_parameters, load_model, open_image, overlay_human_meshes  # noqa: F401
+from .render import render_batch, render_meshes, render_views  # noqa: F401
 
 from .preprocess import Preprocessor  # noqa: F401
 from .graphed import GraphedForward  # noqa: F401
 
-__all__ = ["Model", "GraphedForward", "Preprocessor", "forward_model", "get_camera_parameters", "load_model", "open_image",
-           "overlay_human_meshes", "render_batch", "render_meshes"]
+__all__ = ["Model", "GraphedForward", "Preprocessor", "create_rotating_video", "forward_model", "get_camera_parameters", "load_model",
+           "open_image", "overlay_human_meshes", "render_batch", "render_meshes", "render_views"]

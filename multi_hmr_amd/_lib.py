@@ -184,6 +184,8 @@ _SIGS = {
     "mhmr_anny_decode": ([_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i] + [_vp] * 6 + [_vp], _i),
     "mhmr_render_workspace_bytes": ([C.POINTER(RenderDesc)], C.c_longlong),
     "mhmr_render_meshes": ([C.POINTER(RenderDesc), _vp], _i),
+    "mhmr_render_views_workspace_bytes": ([C.POINTER(RenderDesc), _i], C.c_longlong),
+    "mhmr_render_views": ([C.POINTER(RenderDesc), _i, _vp, _vp], _i),
     "mhmr_prof_enable": ([_i], _i),
     "mhmr_prof_collect": ([C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)], _i),
 }

@@ -1,7 +1,10 @@
 """Drop-in for the reference ``demo.py``: the inference helpers (lines 27-126: ``open_image``, ``get_camera_parameters``,
-``load_model``, ``forward_model``), ``overlay_human_meshes`` (lines 128-158, drawn by ``render.render_batch`` on the GPU) and the
-command line (lines 231-386: ``python -m multi_hmr_amd.demo``, writing ``[input | overlay]`` side by side).  Not carried over (no
-cv2 / trimesh here): the rotating video, the extra side view, GLB / mesh export and the distance annotation."""
+``load_model``, ``forward_model``), ``overlay_human_meshes`` (lines 128-158, drawn by ``render.render_batch`` on the GPU),
+``create_rotating_video`` (lines 160-241, every rotated frame drawn by one ``render.render_views`` call) and the command line
+(lines 231-386: ``python -m multi_hmr_amd.demo``, writing ``[input | overlay]`` side by side, ``[input | overlay | view]`` with
+``--extra_views 1``, and the rotating video with ``--save_rotating_video 1``).  The video is written as an animated PNG, not mp4 (no
+video encoder here).  Not carried over (no trimesh here, and the reference reads ``verts_smplx`` / ``j2d_smplx``, which no model
+emits): GLB / mesh export and the distance annotation."""
 from __future__ import annotations
 
 import os
@@ -85,9 +88,67 @@ def overlay_human_meshes(humans, faces, K, model, img_pil, unique_color=False, a
     return out[0].cpu().numpy(), _color
 
 
+def orbit_extrinsics(center, axis, angles):
+    """View extrinsics [n, 3, 4] float64 that turn the scene about ``center`` (3,) by each angle (degrees) about the camera's 'x' or
+    'y' axis: the reference's ``x' = (x - c) R^T + c`` (demo.py:160-186, its R_y / R_x) written as ``[R | c - R c]``."""
+    c = np.asarray(center, np.float64).reshape(3)
+    out = []
+    for angle in angles:
+        th = np.deg2rad(angle)
+        cs, sn = np.cos(th), np.sin(th)
+        if axis == "y":
+            R = np.array([[cs, 0, sn], [0, 1, 0], [-sn, 0, cs]])
+        elif axis == "x":
+            R = np.array([[1, 0, 0], [0, cs, -sn], [0, sn, cs]])
+        else:
+            raise ValueError("Axis must be 'x' or 'y'")
+        out.append(np.concatenate([R, (c - R @ c)[:, None]], 1))
+    return np.stack(out) if out else np.zeros((0, 3, 4))
+
+
+def create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=False, alpha=0.8, fn='rotating.mp4', n_frames=20,
+                          angle_range=60):
+    """demo.py:188-241: the persons turned about person 0's centre, swept to +angle_range about y, to -angle_range about y and to
+    +angle_range about x and back, over a white image, with ``n_frames // 4`` copies of the overlay over the photograph at the start
+    and between the sweeps -> the frame list (np.uint8 [H, W, 3]), None when there are no persons.  The 3 n_frames rotated frames
+    are one ``render.render_views`` call (the vertex normals computed once, not once per frame).  fn: the frames are written as an
+    animated PNG (100 ms per frame, the reference's 10 fps) to ``splitext(fn)[0] + '.png'``; the reference's mp4 needs cv2."""
+    from PIL import Image
+    from . import render
+    if len(humans) == 0:
+        return None
+    central, _color = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=unique_color, alpha=alpha, _color=None)
+    central = central.astype(np.uint8)
+    name = "verts_smplx" if "verts_smplx" in humans[0] else "v3d"
+    center = humans[0][name].mean(0).detach().cpu().numpy()
+    angles = [angle_range * i / (n_frames - 1) for i in range(n_frames)]
+    Rt = np.concatenate([orbit_extrinsics(center, "y", angles), orbit_extrinsics(center, "y", [-a for a in angles]),
+                         orbit_extrinsics(center, "x", angles)])
+    verts = _stacked([h[name] for h in humans])
+    W, H = img_pil_visu.size
+    white = torch.full((1, H, W, 3), 255, dtype=torch.uint8, device=verts.device)
+    Kc = torch.as_tensor(K)[0].detach().float().cpu().reshape(1, 3, 3)
+    cols = [_color[j % len(_color)] for j in range(len(humans))]
+    views = render.render_views(white, verts, torch.zeros(len(humans), dtype=torch.int32), Kc, faces, torch.from_numpy(Rt)[None],
+                                colors=cols, alpha=alpha)[0].cpu().numpy()
+    sweeps = [list(views[k * n_frames:(k + 1) * n_frames]) for k in range(3)]
+    pause = [central for _ in range(n_frames // 4)]
+    frames = list(pause)
+    for sweep in sweeps:
+        frames += sweep + sweep[::-1][1:-1] + pause
+    if fn is not None:
+        path = os.path.splitext(fn)[0] + ".png"
+        imgs = [Image.fromarray(f) for f in frames]
+        imgs[0].save(path, save_all=True, append_images=imgs[1:], duration=100, loop=0)
+        print(f"Saved video to {path}")
+    return frames
+
+
 def main(argv=None):
-    """demo.py:231-386 without the video / extra view / mesh export options: every image of --img_folder -> forward -> overlay ->
-    ``<out_folder>/<image>_<model>.png`` = [input | overlay]."""
+    """demo.py:231-386 without the mesh export and distance options: every image of --img_folder -> forward -> overlay ->
+    ``<out_folder>/<image>_<model>.png`` = [input | overlay], or [input | overlay | view] with --extra_views 1 (the persons turned
+    30 degrees about y, over white; a white panel where nobody was detected); --save_rotating_video 1 adds
+    ``<image>_<model>_rotating.png`` (animated, when somebody was detected).  Returns every path written."""
     from argparse import ArgumentParser
     from PIL import Image
     from .preprocess import open_image
@@ -100,6 +161,8 @@ def main(argv=None):
     parser.add_argument("--fov", type=float, default=60)
     parser.add_argument("--alpha", type=float, default=1.0)
     parser.add_argument("--unique_color", type=int, default=0, choices=[0, 1])
+    parser.add_argument("--extra_views", type=int, default=0, choices=[0, 1])
+    parser.add_argument("--save_rotating_video", type=int, default=0, choices=[0, 1])
     args = parser.parse_args(argv)
     assert torch.cuda.is_available()
     suffixes = (".jpg", ".jpeg", ".png", ".webp")
@@ -126,9 +189,19 @@ def main(argv=None):
         K[0, 1, 2] = img_pil_visu.size[1] / 2.0
         K[0, [0, 1], [0, 1]] = ratio * K[0, [0, 1], [0, 1]]
         pred, _ = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha)
-        Image.fromarray(np.concatenate([np.asarray(img_pil_visu), pred], 1).astype(np.uint8)).save(save_fn)
+        l_img = [np.asarray(img_pil_visu), pred]
+        if args.extra_views:                                             # demo.py:351-354: the side view, 30 degrees about y
+            frames = create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha,
+                                           fn=None, n_frames=2, angle_range=30)
+            l_img.append(frames[1] if frames is not None else np.full_like(pred, 255))
+        Image.fromarray(np.concatenate(l_img, 1).astype(np.uint8)).save(save_fn)
         print(f"{len(humans)} persons -> {save_fn}")
         written.append(save_fn)
+        if args.save_rotating_video:                                     # demo.py:362-364, an animated PNG for the mp4
+            fn = os.path.splitext(save_fn)[0] + "_rotating.mp4"
+            if create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha, fn=fn,
+                                     n_frames=20, angle_range=60) is not None:
+                written.append(os.path.splitext(fn)[0] + ".png")
     return written
 
 

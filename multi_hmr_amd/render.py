@@ -95,15 +95,10 @@ def _colors(colors, P):
     return np.array(c, np.float32, copy=True, order="C")
 
 
-def render_batch(images_u8, verts, image_index, K, faces, colors=None, alpha=0.8, Rt=None, smooth=True, cull_back=True,
-                 return_debug=False, intensity=3.0, metallic=0.0, roughness=0.5):
-    """Draw P meshes sharing one face array into B images, on the images' device.
-
-    images_u8 [B, H, W, 3] uint8 cuda; verts [P, V, 3] float32 cuda (rows of one person contiguous; any person stride, so a slice of
-    the forward's ``v3d`` block is read in place); image_index [P] (image of each mesh); K [B, 3, 3]; faces [F, 3]; colors [P, 3] in
-    [0, 1] (None: ``PALETTE``); Rt [B, 3, 4] = [R | t] or None.  Returns the blended images [B, H, W, 3] uint8 (a new tensor) and, with
-    return_debug=True, also the winning keys [B, H, W] (int64 holding the uint64 bits; -1 = nothing drawn) and the pre-blend rgb
-    [B, H, W, 3] uint8."""
+def _render(images_u8, verts, image_index, K, faces, colors, alpha, Rt, nviews, smooth, cull_back, return_debug, intensity, metallic,
+            roughness):
+    """render_batch (nviews None: mhmr_render_meshes, Rt [B, 3, 4] or None) and render_views (mhmr_render_views, Rt [B, nviews, 3, 4]
+    or None = identity in every view).  Outputs [B, H, W, ...] or [B, nviews, H, W, ...]."""
     if not (torch.is_tensor(images_u8) and images_u8.is_cuda and images_u8.dtype == torch.uint8 and images_u8.dim() == 4
             and images_u8.shape[-1] == 3):
         raise ValueError("images_u8 must be a cuda uint8 tensor [B, H, W, 3]")
@@ -120,7 +115,8 @@ def render_batch(images_u8, verts, image_index, K, faces, colors=None, alpha=0.8
     if idx.numel() != P:
         raise ValueError(f"image_index has {idx.numel()} entries for {P} meshes")
     Kt = torch.as_tensor(K, dtype=torch.float32).to(dev).reshape(B, 3, 3).contiguous()
-    Rtt = None if Rt is None else torch.as_tensor(Rt, dtype=torch.float32).to(dev).reshape(B, 3, 4).contiguous()
+    views = () if nviews is None else (nviews,)
+    Rtt = None if Rt is None else torch.as_tensor(Rt, dtype=torch.float32).to(dev).reshape((B,) + views + (3, 4)).contiguous()
     if P:
         f_dev, off_dev, adj_dev = _faces_on(faces, V, dev)
         F = int(f_dev.shape[0])
@@ -128,28 +124,62 @@ def render_batch(images_u8, verts, image_index, K, faces, colors=None, alpha=0.8
         f_dev = off_dev = adj_dev = None
         F = int(np.asarray(faces).shape[0]) if faces is not None else 0
     col = torch.from_numpy(_colors(colors, P)).to(dev)
-    out = torch.empty_like(images)
-    key = torch.empty(B, H, W, dtype=torch.int64, device=dev) if return_debug else None
-    rgb = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev) if return_debug else None
+    out = torch.empty((B,) + views + (H, W, 3), dtype=torch.uint8, device=dev)
+    key = torch.empty((B,) + views + (H, W), dtype=torch.int64, device=dev) if return_debug else None
+    rgb = torch.empty((B,) + views + (H, W, 3), dtype=torch.uint8, device=dev) if return_debug else None
 
     d = _lib.RenderDesc()
     d.B, d.H, d.W, d.P, d.V, d.F = B, H, W, P, V, F
     d.verts, d.vstride = _lib.ptr(verts) if P else None, int(verts.stride(0)) if P > 1 else 3 * V
     d.faces, d.adj_off, d.adj = _lib.ptr(f_dev), _lib.ptr(off_dev), _lib.ptr(adj_dev)
-    d.image_index, d.K, d.Rt, d.colors = _lib.ptr(idx), _lib.ptr(Kt), _lib.ptr(Rtt), _lib.ptr(col)
+    d.image_index, d.K, d.colors = _lib.ptr(idx), _lib.ptr(Kt), _lib.ptr(col)
+    d.Rt = _lib.ptr(Rtt) if nviews is None else None
     d.alpha, d.intensity, d.ambient, d.metallic, d.roughness = float(alpha), float(intensity), AMBIENT, float(metallic), float(roughness)
     d.znear, d.zfar, d.smooth, d.cull_back = ZNEAR, ZFAR, int(bool(smooth)), int(bool(cull_back))
     d.img_in, d.img_out = _lib.ptr(images), _lib.ptr(out)
     d.key_out, d.rgb_out = _lib.ptr(key), _lib.ptr(rgb)
     L = _lib.lib()
-    nbytes = L.mhmr_render_workspace_bytes(C.byref(d))
+    if nviews is None:
+        nbytes, what = L.mhmr_render_workspace_bytes(C.byref(d)), "mhmr_render_workspace_bytes"
+    else:
+        nbytes, what = L.mhmr_render_views_workspace_bytes(C.byref(d), nviews), "mhmr_render_views_workspace_bytes"
     if nbytes < 0:
-        _lib.check(int(nbytes), "mhmr_render_workspace_bytes")
+        _lib.check(int(nbytes), what)
     with torch.cuda.device(dev):
         ws = _workspace(int(nbytes), dev)
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-        _lib.check(L.mhmr_render_meshes(C.byref(d), torch.cuda.current_stream(dev).cuda_stream), "mhmr_render_meshes")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if nviews is None:
+            _lib.check(L.mhmr_render_meshes(C.byref(d), stream), "mhmr_render_meshes")
+        else:
+            _lib.check(L.mhmr_render_views(C.byref(d), nviews, _lib.ptr(Rtt), stream), "mhmr_render_views")
     return (out, key, rgb) if return_debug else out
+
+
+def render_batch(images_u8, verts, image_index, K, faces, colors=None, alpha=0.8, Rt=None, smooth=True, cull_back=True,
+                 return_debug=False, intensity=3.0, metallic=0.0, roughness=0.5):
+    """Draw P meshes sharing one face array into B images, on the images' device.
+
+    images_u8 [B, H, W, 3] uint8 cuda; verts [P, V, 3] float32 cuda (rows of one person contiguous; any person stride, so a slice of
+    the forward's ``v3d`` block is read in place); image_index [P] (image of each mesh); K [B, 3, 3]; faces [F, 3]; colors [P, 3] in
+    [0, 1] (None: ``PALETTE``); Rt [B, 3, 4] = [R | t] or None.  Returns the blended images [B, H, W, 3] uint8 (a new tensor) and, with
+    return_debug=True, also the winning keys [B, H, W] (int64 holding the uint64 bits; -1 = nothing drawn) and the pre-blend rgb
+    [B, H, W, 3] uint8."""
+    return _render(images_u8, verts, image_index, K, faces, colors, alpha, Rt, None, smooth, cull_back, return_debug, intensity,
+                   metallic, roughness)
+
+
+def render_views(images_u8, verts, image_index, K, faces, Rt, colors=None, alpha=0.8, smooth=True, cull_back=True, return_debug=False,
+                 intensity=3.0, metallic=0.0, roughness=0.5):
+    """Draw every image from NV cameras in one call: view (b, v) sees image b's meshes through K[b] and Rt[b, v] = [R | t], blended
+    over images_u8[b].  Arguments as ``render_batch``, with Rt [B, NV, 3, 4] (NV >= 1).  Returns [B, NV, H, W, 3] uint8 and, with
+    return_debug=True, the keys [B, NV, H, W] and the pre-blend rgb [B, NV, H, W, 3].  View v of the result is byte-identical to
+    ``render_batch(..., Rt=Rt[:, v])``; the vertex normals are computed once per mesh, not once per view (csrc/render.hip)."""
+    Rt = torch.as_tensor(Rt, dtype=torch.float32)
+    if Rt.dim() != 4 or Rt.shape[2:] != (3, 4) or Rt.shape[1] < 1:
+        raise ValueError(f"Rt must be [B, NV, 3, 4] with NV >= 1, got {tuple(Rt.shape)}")
+    return _render(images_u8, verts, image_index, K, faces, colors, alpha, Rt, int(Rt.shape[1]), smooth, cull_back, return_debug,
+                   intensity, metallic, roughness)
 
 
 def render_meshes(img, l_mesh, l_face, cam_param, color=None, alpha=1.0, show_camera=False, intensity=3.0, metallicFactor=0.,
