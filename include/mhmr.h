@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
+#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
 #define MHMR_OK 0
 #define MHMR_ERR_BAD_ARG (-1)
@@ -479,6 +479,27 @@ int mhmr_anny_decode(const float* rot6d, const float* useful, int J, const float
 int mhmr_preprocess_u8(const void* img, int H, int W, const int* kh, const int* bh, int ksh, const int* kv,
                        const int* bv, int ksv, int ow, int oh, int y0, int rows, int S, int pad_x, int pad_y,
                        const float* lut, void* tmp, float* out, void* stream);
+
+/* The same for B images of different sizes in TWO launches (horizontal pass, vertical pass + pad + lut, each over a
+ * (block, image) grid; B <= 65535) -> out [B][3][S][S] fp32, the tensor Model.forward takes.  Per pixel the arithmetic is
+ * mhmr_preprocess_u8's, so image b of the batch is bit-identical to the one-image call (and to PIL).
+ * One descriptor per image: its geometry exactly as the arguments of mhmr_preprocess_u8, and DEVICE pointers of the
+ * decoded image (anywhere on the device: a tensor of its own, a slice of a staging buffer, a decoder's frame), of the
+ * tables of its geometry (two images of one size may share them) and of its own tmp [rows][ow][3] slice (slices of
+ * two images must not overlap).
+ * The descriptors are passed twice: `host` [B] is read by this function to validate every image before any launch
+ * and to size the grids; `dev` [B] is a device copy of the same bytes, which the kernels read.  The caller makes that
+ * copy on `stream` (or otherwise before the call in stream order) and keeps both alive: `host` until the call returns,
+ * `dev` until the work has run.  B <= 0, S <= 0, B > 65535 or a per-image shape condition of mhmr_preprocess_u8 ->
+ * MHMR_ERR_BAD_SHAPE; a null pointer (arguments or descriptor fields) -> MHMR_ERR_BAD_ARG. */
+typedef struct {
+    const void* img;                                   /* uint8 [H][W][3], device */
+    int H, W, ow, oh, y0, rows, pad_x, pad_y, ksh, ksv;
+    const int *kh, *bh, *kv, *bv;                      /* device; formats as for mhmr_preprocess_u8 */
+    void* tmp;                                         /* uint8 [rows][ow][3], device */
+} mhmr_pre_image;
+int mhmr_preprocess_u8_batch(const mhmr_pre_image* host, const mhmr_pre_image* dev, int B, int S, const float* lut,
+                             float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Accuracy metrics of the reference's evaluation loop, train.py:372-395 (PVE, PA-PVE) and

@@ -5,6 +5,7 @@ from .render import render_batch, render_meshes, render_views  # noqa: F401
 
 from .preprocess import Preprocessor  # noqa: F401
 from .graphed import GraphedForward  # noqa: F401
+from .pipeline import ImageResult, PipelineError, predict_images  # noqa: F401
 
-__all__ = ["Model", "GraphedForward", "Preprocessor", "create_rotating_video", "forward_model", "get_camera_parameters", "load_model",
-           "open_image", "overlay_human_meshes", "render_batch", "render_meshes", "render_views"]
+__all__ = ["Model", "GraphedForward", "ImageResult", "PipelineError", "Preprocessor", "create_rotating_video", "forward_model", "get_camera_parameters", "load_model",
+           "open_image", "overlay_human_meshes", "predict_images", "render_batch", "render_meshes", "render_views"]

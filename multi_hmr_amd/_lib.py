@@ -138,6 +138,12 @@ class RenderDesc(C.Structure):
                  ("workspace_bytes", C.c_longlong), ("key_out", _vp), ("rgb_out", _vp)])
 
 
+class PreImage(C.Structure):
+    """include/mhmr.h mhmr_pre_image: one image of mhmr_preprocess_u8_batch (device pointers + the geometry of its plan)."""
+    _fields_ = ([("img", _vp)] + [(n, _i) for n in ("H", "W", "ow", "oh", "y0", "rows", "pad_x", "pad_y", "ksh", "ksv")] +
+                [(n, _vp) for n in ("kh", "bh", "kv", "bv", "tmp")])
+
+
 _SIGS = {
     "mhmr_version": ([], _i),
     "mhmr_source_hash": ([], C.c_char_p),
@@ -178,6 +184,7 @@ _SIGS = {
     "mhmr_lbs_forward": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp], _i),
     "mhmr_lbs_forward_fused": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp, _vp], _i),
     "mhmr_preprocess_u8": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i] + [_i] * 7 + [_vp, _vp, _vp, _vp], _i),
+    "mhmr_preprocess_u8_batch": ([C.POINTER(PreImage), _vp, _i, _i, _vp, _vp, _vp], _i),
     "mhmr_eval_mesh_errors": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),
     "mhmr_anny_scores": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
     "mhmr_anny_camera": ([_vp, _i, _i, _f, _vp, _vp, _vp], _i),

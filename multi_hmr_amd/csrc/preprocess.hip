@@ -6,6 +6,7 @@
 // 1 << 21, arithmetic shift, clip to 0..255), so the result is bit-identical to PIL's; the ImageNet normalisation is a
 // 3 x 256 lookup table the host fills with the reference's own numpy expression (float32 divide, float64 mean/std, cast).
 // Byte/integer streaming work: HBM-bound, one thread per output pixel, no LDS needed (taps overlap in L1/L2).
+// mhmr_preprocess_u8_batch runs the same per-pixel bodies for B images of different sizes in two launches over (block, image).
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
 
@@ -19,11 +20,9 @@ __device__ __forceinline__ int clip8(int v) {
 }
 
 // tmp[y][ox][c] = clip8(sum_t img[y0 + y][xmin(ox) + t][c] * kh[ox][t])      (rows y0 .. y0 + rows - 1 of the source only)
-__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ img, int W, int y0, int rows,
-                                                         const int* __restrict__ kh, const int* __restrict__ bh, int ksh,
-                                                         int ow, uint8_t* __restrict__ tmp) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * ow) return;
+// One body for the one-image and the batch kernel: i = the thread's pixel of tmp, i < rows * ow checked by the caller.
+__device__ __forceinline__ void resample_h_pixel(const uint8_t* __restrict__ img, int W, int y0, const int* __restrict__ kh,
+                                                 const int* __restrict__ bh, int ksh, int ow, uint8_t* __restrict__ tmp, int i) {
     const int y = i / ow, ox = i - y * ow;
     const int xmin = bh[2 * ox], xmax = bh[2 * ox + 1];
     const int* k = kh + (size_t)ox * ksh;
@@ -42,12 +41,10 @@ __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restri
 }
 
 // out[c][Y][X] = lut[c][ inside ? clip8(sum_t tmp[ymin(oy) - y0 + t][ox][c] * kv[oy][t]) : 0 ],  (ox, oy) = (X - pad_x, Y - pad_y)
-__global__ __launch_bounds__(256) void resample_v_norm_kernel(const uint8_t* __restrict__ tmp, int y0,
-                                                              const int* __restrict__ kv, const int* __restrict__ bv, int ksv,
-                                                              int ow, int oh, int S, int pad_x, int pad_y,
-                                                              const float* __restrict__ lut, float* __restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= S * S) return;
+// i = the thread's pixel of one [S][S] plane, i < S * S checked by the caller.
+__device__ __forceinline__ void resample_v_norm_pixel(const uint8_t* __restrict__ tmp, int y0, const int* __restrict__ kv,
+                                                      const int* __restrict__ bv, int ksv, int ow, int oh, int S, int pad_x, int pad_y,
+                                                      const float* __restrict__ lut, float* __restrict__ out, int i) {
     const int Y = i / S, X = i - Y * S;
     const int ox = X - pad_x, oy = Y - pad_y;
     int v0 = 0, v1 = 0, v2 = 0;
@@ -70,13 +67,53 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(const uint8_t* __r
     out[(size_t)2 * S * S + i] = lut[512 + v2];
 }
 
+__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ img, int W, int y0, int rows,
+                                                         const int* __restrict__ kh, const int* __restrict__ bh, int ksh,
+                                                         int ow, uint8_t* __restrict__ tmp) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * ow) return;
+    resample_h_pixel(img, W, y0, kh, bh, ksh, ow, tmp, i);
+}
+
+__global__ __launch_bounds__(256) void resample_v_norm_kernel(const uint8_t* __restrict__ tmp, int y0,
+                                                              const int* __restrict__ kv, const int* __restrict__ bv, int ksv,
+                                                              int ow, int oh, int S, int pad_x, int pad_y,
+                                                              const float* __restrict__ lut, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * S) return;
+    resample_v_norm_pixel(tmp, y0, kv, bv, ksv, ow, oh, S, pad_x, pad_y, lut, out, i);
+}
+
+// The batch forms: blockIdx.y = image, its descriptor read from device memory (uniform over the block); the grid's x extent is
+// the largest image's, so the blocks past an image's own pixel count exit.
+__global__ __launch_bounds__(256) void resample_h_batch_kernel(const mhmr_pre_image* __restrict__ desc) {
+    const mhmr_pre_image& d = desc[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= d.rows * d.ow) return;
+    resample_h_pixel((const uint8_t*)d.img, d.W, d.y0, d.kh, d.bh, d.ksh, d.ow, (uint8_t*)d.tmp, i);
+}
+
+__global__ __launch_bounds__(256) void resample_v_norm_batch_kernel(const mhmr_pre_image* __restrict__ desc, int S,
+                                                                    const float* __restrict__ lut, float* __restrict__ out) {
+    const mhmr_pre_image& d = desc[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * S) return;
+    resample_v_norm_pixel((const uint8_t*)d.tmp, d.y0, d.kv, d.bv, d.ksv, d.ow, d.oh, S, d.pad_x, d.pad_y, lut,
+                          out + (size_t)blockIdx.y * 3 * S * S, i);
+}
+
+// the shape conditions of one image (shared by both entry points)
+bool bad_image_shape(int H, int W, int ow, int oh, int ksh, int ksv, int y0, int rows, int S, int pad_x, int pad_y) {
+    if (H <= 0 || W <= 0 || ow <= 0 || oh <= 0 || ow > S || oh > S || ksh <= 0 || ksv <= 0) return true;
+    return y0 < 0 || rows <= 0 || y0 + rows > H || pad_x < 0 || pad_y < 0 || pad_x + ow > S || pad_y + oh > S;
+}
+
 }  // namespace
 
 extern "C" int mhmr_preprocess_u8(const void* img, int H, int W, const int* kh, const int* bh, int ksh, const int* kv,
                                   const int* bv, int ksv, int ow, int oh, int y0, int rows, int S, int pad_x, int pad_y,
                                   const float* lut, void* tmp, float* out, void* stream) {
-    if (H <= 0 || W <= 0 || ow <= 0 || oh <= 0 || ow > S || oh > S || ksh <= 0 || ksv <= 0) return MHMR_ERR_BAD_SHAPE;
-    if (y0 < 0 || rows <= 0 || y0 + rows > H || pad_x < 0 || pad_y < 0 || pad_x + ow > S || pad_y + oh > S) return MHMR_ERR_BAD_SHAPE;
+    if (bad_image_shape(H, W, ow, oh, ksh, ksv, y0, rows, S, pad_x, pad_y)) return MHMR_ERR_BAD_SHAPE;
     if (!img || !kh || !bh || !kv || !bv || !lut || !tmp || !out) return MHMR_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int n1 = rows * ow, n2 = S * S;
@@ -84,6 +121,25 @@ extern "C" int mhmr_preprocess_u8(const void* img, int H, int W, const int* kh, 
                        (uint8_t*)tmp);
     hipLaunchKernelGGL(resample_v_norm_kernel, dim3((n2 + 255) / 256), dim3(256), 0, s, (const uint8_t*)tmp, y0, kv, bv, ksv, ow, oh, S,
                        pad_x, pad_y, lut, out);
+    MHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mhmr_preprocess_u8_batch(const mhmr_pre_image* host, const mhmr_pre_image* dev, int B, int S, const float* lut,
+                                        float* out, void* stream) {
+    if (B <= 0 || B > 65535 || S <= 0) return MHMR_ERR_BAD_SHAPE;
+    if (!host || !dev || !lut || !out) return MHMR_ERR_BAD_ARG;
+    int n1 = 0;
+    for (int b = 0; b < B; ++b) {
+        const mhmr_pre_image& d = host[b];
+        if (bad_image_shape(d.H, d.W, d.ow, d.oh, d.ksh, d.ksv, d.y0, d.rows, S, d.pad_x, d.pad_y)) return MHMR_ERR_BAD_SHAPE;
+        if (!d.img || !d.kh || !d.bh || !d.kv || !d.bv || !d.tmp) return MHMR_ERR_BAD_ARG;
+        n1 = d.rows * d.ow > n1 ? d.rows * d.ow : n1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int n2 = S * S;
+    hipLaunchKernelGGL(resample_h_batch_kernel, dim3((n1 + 255) / 256, B), dim3(256), 0, s, dev);
+    hipLaunchKernelGGL(resample_v_norm_batch_kernel, dim3((n2 + 255) / 256, B), dim3(256), 0, s, dev, S, lut, out);
     MHMR_CHECK_LAUNCH();
     return 0;
 }

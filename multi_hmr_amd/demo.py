@@ -148,7 +148,8 @@ def main(argv=None):
     """demo.py:231-386 without the mesh export and distance options: every image of --img_folder -> forward -> overlay ->
     ``<out_folder>/<image>_<model>.png`` = [input | overlay], or [input | overlay | view] with --extra_views 1 (the persons turned
     30 degrees about y, over white; a white panel where nobody was detected); --save_rotating_video 1 adds
-    ``<image>_<model>_rotating.png`` (animated, when somebody was detected).  Returns every path written."""
+    ``<image>_<model>_rotating.png`` (animated, when somebody was detected).  ``--batch_size N`` > 1 infers N images per forward
+    (``pipeline.predict_images``) and draws each result as before.  Returns every path written."""
     from argparse import ArgumentParser
     from PIL import Image
     from .preprocess import open_image
@@ -163,6 +164,8 @@ def main(argv=None):
     parser.add_argument("--unique_color", type=int, default=0, choices=[0, 1])
     parser.add_argument("--extra_views", type=int, default=0, choices=[0, 1])
     parser.add_argument("--save_rotating_video", type=int, default=0, choices=[0, 1])
+    parser.add_argument("--batch_size", type=int, default=1, help="> 1: decode, preprocess and infer that many images per forward "
+                        "(pipeline.predict_images); the files written are the same")
     args = parser.parse_args(argv)
     assert torch.cuda.is_available()
     suffixes = (".jpg", ".jpeg", ".png", ".webp")
@@ -178,16 +181,11 @@ def main(argv=None):
     model_name = os.path.basename(args.model_name)
     os.makedirs(args.out_folder, exist_ok=True)
     written = []
-    for img_path in l_img_path:
+
+    def write(img_path, humans, K, img_pil_visu):
+        """Overlay (+ side view, + rotating video) of one image with its full-resolution camera K -> the files of that image."""
         save_fn = os.path.join(args.out_folder, f"{img_path}_{model_name}.png")
         os.makedirs(os.path.dirname(save_fn), exist_ok=True)
-        x, img_pil_visu = open_image(os.path.join(args.img_folder, img_path), model.img_size)
-        K = get_camera_parameters(model.img_size, fov=args.fov)
-        humans = forward_model(model, x, K, det_thresh=args.det_thresh, nms_kernel_size=args.nms_kernel_size)
-        ratio = max(img_pil_visu.size) / x.shape[-1]                     # demo.py:340-344: K for the full-resolution image
-        K[0, 0, 2] = img_pil_visu.size[0] / 2.0
-        K[0, 1, 2] = img_pil_visu.size[1] / 2.0
-        K[0, [0, 1], [0, 1]] = ratio * K[0, [0, 1], [0, 1]]
         pred, _ = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha)
         l_img = [np.asarray(img_pil_visu), pred]
         if args.extra_views:                                             # demo.py:351-354: the side view, 30 degrees about y
@@ -202,6 +200,23 @@ def main(argv=None):
             if create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha, fn=fn,
                                      n_frames=20, angle_range=60) is not None:
                 written.append(os.path.splitext(fn)[0] + ".png")
+
+    if args.batch_size > 1:                                              # one forward per batch_size images, then the same drawing
+        from .pipeline import predict_images
+        opened = (Image.open(os.path.join(args.img_folder, p)) for p in l_img_path)      # decoded on the pipeline's threads
+        for r in predict_images(model, opened, batch_size=args.batch_size, fov=args.fov, det_thresh=args.det_thresh,
+                                nms_kernel_size=args.nms_kernel_size):
+            write(l_img_path[r.index], r.humans, r.K_full, r.source.convert("RGB"))
+        return written
+    for img_path in l_img_path:
+        x, img_pil_visu = open_image(os.path.join(args.img_folder, img_path), model.img_size)
+        K = get_camera_parameters(model.img_size, fov=args.fov)
+        humans = forward_model(model, x, K, det_thresh=args.det_thresh, nms_kernel_size=args.nms_kernel_size)
+        ratio = max(img_pil_visu.size) / x.shape[-1]                     # demo.py:340-344: K for the full-resolution image
+        K[0, 0, 2] = img_pil_visu.size[0] / 2.0
+        K[0, 1, 2] = img_pil_visu.size[1] / 2.0
+        K[0, [0, 1], [0, 1]] = ratio * K[0, [0, 1], [0, 1]]
+        write(img_path, humans, K, img_pil_visu)
     return written
 
 

@@ -13,7 +13,9 @@ Host side = table construction only (a few KB per image size, cached):
 ``tests/test_preprocess.py`` holds these bit-exact against the installed Pillow itself."""
 from __future__ import annotations
 
+import ctypes
 import math
+import threading
 from functools import lru_cache
 
 import numpy as np
@@ -107,7 +109,8 @@ def norm_lut() -> np.ndarray:
 class Preprocessor:
     """``pre = Preprocessor(img_size, device); x = pre(img_u8)`` with ``img_u8`` a uint8 ``[H, W, 3]`` RGB tensor (host or
     device) -> ``[1, 3, S, S]`` float32 on the device, bit-identical to ``demo.open_image``'s tensor.  Asynchronous on the
-    current stream; coefficient tables are cached per source size."""
+    current stream; coefficient tables are cached per source size.  ``pre.batch([img_u8, ...])`` does the same for a list of images
+    of any sizes in two launches and one host-to-device copy -> ``[B, 3, S, S]``, the tensor ``Model.forward`` takes."""
 
     def __init__(self, img_size: int, device=torch.device("cuda")):
         self.S = int(img_size)
@@ -116,6 +119,12 @@ class Preprocessor:
             raise _lib.MhmrError("Preprocessor needs a HIP device: there is no CPU fallback")
         self.lut = torch.from_numpy(norm_lut()).to(self.device)
         self._tables = {}
+        # batch(): two pinned staging buffers used in turn (descriptors + the host images of one call; the event says when the copy
+        # out of it has run), their device copy, and the workspace the images' tmp slices are carved from; all grow on demand
+        self._pinned = [[None, None], [None, None]]
+        self._turn = 0
+        self._staging = self._tmp = None
+        self._batch_lock = threading.Lock()
 
     def _plan(self, H: int, W: int):
         key = (H, W)
@@ -149,6 +158,73 @@ class Preprocessor:
                                                  t["bv"].data_ptr(), t["ksv"], t["ow"], t["oh"], t["y0"], t["rows"], S, t["px"], t["py"],
                                                  self.lut.data_ptr(), t["tmp"].data_ptr(), out.data_ptr(), st), "mhmr_preprocess_u8")
         return out
+
+    def batch(self, images, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``images``: a list of uint8 ``[H, W, 3]`` RGB tensors of any sizes, on the host, on the device or mixed -> ``[B, 3, S, S]``
+        float32 on the device (written into ``out`` if given), image b bit-identical to ``self(images[b])``.  One
+        ``mhmr_preprocess_u8_batch`` call: two launches however many images there are.  The host images and the descriptors travel in
+        ONE pinned buffer and one non-blocking copy; device images are read where they are.  Asynchronous on the current stream;
+        calls on one Preprocessor must all use the same stream (the staging buffers are reused in stream order).  The plan of every
+        source size met stays cached (tables of a few KB and the one-image ``tmp`` of ``__call__``, rows x ow x 3 bytes): an endless
+        stream of ever new sizes grows that cache; use a new Preprocessor per source, or clear ``_tables``, there."""
+        B, S = len(images), self.S
+        if B == 0 or B > 65535:
+            raise ValueError("expected 1 ... 65535 images")
+        for img in images:
+            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+                raise ValueError("expected a uint8 [H, W, 3] RGB image")
+        dev = self.lut.device                              # with its index: self.device may be a bare "cuda"
+        with self._batch_lock:
+            plans = [self._plan(int(img.shape[0]), int(img.shape[1])) for img in images]
+            if out is None:
+                out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+            if not (out.is_contiguous() and out.numel() == B * 3 * S * S and out.dtype == torch.float32 and out.device == dev):
+                raise ValueError(f"out must be a contiguous float32 tensor of {B} x 3 x {S} x {S} elements on {dev}")
+            up = lambda n: -(-n // 256) * 256
+            # layout of the staging buffer: [B descriptors][host image 0][host image 1] ...; of the workspace: [tmp 0][tmp 1] ...
+            off, img_off, tmp_off, tmp_bytes = up(B * ctypes.sizeof(_lib.PreImage)), [], [], 0
+            for img, t in zip(images, plans):
+                img_off.append(None if img.is_cuda else off)
+                if not img.is_cuda:
+                    off += up(img.numel())
+                tmp_off.append(tmp_bytes)
+                tmp_bytes += up(t["rows"] * t["ow"] * 3)
+            slot = self._pinned[self._turn]
+            self._turn ^= 1
+            if slot[1] is not None:
+                slot[1].synchronize()                      # the copy out of this buffer two calls ago
+            if slot[0] is None or slot[0].numel() < off:
+                slot[0] = torch.empty(off + off // 4, dtype=torch.uint8, pin_memory=True)
+            if self._staging is None or self._staging.numel() < off:
+                self._staging = torch.empty(off + off // 4, dtype=torch.uint8, device=dev)
+            if self._tmp is None or self._tmp.numel() < tmp_bytes:
+                self._tmp = torch.empty(tmp_bytes + tmp_bytes // 4, dtype=torch.uint8, device=dev)
+            pin, staging = slot[0], self._staging
+            desc, keep = (_lib.PreImage * B)(), []
+            for b, (img, t) in enumerate(zip(images, plans)):
+                d, H, W = desc[b], int(img.shape[0]), int(img.shape[1])
+                if img.is_cuda:
+                    img = img.to(dev).contiguous()
+                    keep.append(img)
+                    d.img = img.data_ptr()
+                else:
+                    pin[img_off[b]:img_off[b] + img.numel()].view(H, W, 3).copy_(img)
+                    d.img = staging.data_ptr() + img_off[b]
+                d.H, d.W, d.ow, d.oh, d.y0, d.rows, d.pad_x, d.pad_y, d.ksh, d.ksv = (H, W, t["ow"], t["oh"], t["y0"], t["rows"], t["px"],
+                                                                                     t["py"], t["ksh"], t["ksv"])
+                d.kh, d.bh, d.kv, d.bv = t["kh"].data_ptr(), t["bh"].data_ptr(), t["kv"].data_ptr(), t["bv"].data_ptr()
+                d.tmp = self._tmp.data_ptr() + tmp_off[b]
+            pin[:ctypes.sizeof(desc)].copy_(torch.frombuffer(desc, dtype=torch.uint8))
+            with torch.cuda.device(dev):
+                staging[:off].copy_(pin[:off], non_blocking=True)
+                if slot[1] is None:
+                    slot[1] = torch.cuda.Event()
+                slot[1].record()
+                st = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(_lib.lib().mhmr_preprocess_u8_batch(desc, staging.data_ptr(), B, S, self.lut.data_ptr(), out.data_ptr(), st),
+                           "mhmr_preprocess_u8_batch")
+            del keep                                       # device inputs made contiguous here: freed in stream order, after the kernels
+        return out.view(B, 3, S, S)
 
 
 _PRE = {}
