@@ -572,6 +572,42 @@ long long mhmr_render_views_workspace_bytes(const mhmr_render_desc* d, int nview
 int mhmr_render_views(const mhmr_render_desc* d, int nviews, const float* view_Rt, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Scene packing for the 3D export (reference utils/render.py:62-173 create_scene, demo.py:371-384): P meshes
+ * sharing one face array, laid out as a glTF binary chunk holds them, in ONE launch (multi_hmr_amd/scene.py writes
+ * the file; tests/scene_oracle.py restates this contract in numpy):
+ *   out [P][2][V][3] fp32: per person the transformed positions, then the transformed unit normals, so the persons
+ *     p0 .. p1 of one image are one contiguous byte range; bounds [P][2][3] fp32: per person the component-wise
+ *     minimum, then maximum, of the positions just written (glTF requires them on a POSITION accessor).
+ *   Position: X = R x + t in fp64, summed as ((R0 x0 + R1 x1) + R2 x2) + t, rounded once to fp32.
+ *   Normal: the angle-weighted vertex normal of render contract item 6 (incident non-degenerate faces in ascending
+ *     face order, corner angle x unit face normal, normalised, fp64; the sum order is the CSR's, no atomics),
+ *     rotated by R, rounded once to fp32.  A vertex with no non-degenerate incident face gets (0, 0, 1), not
+ *     rotated.
+ *   Bounds: the exact min / max of the fp32 positions (order-independent, hence deterministic).
+ * transform [3][4] fp32 = [R | t], R taken to be a rotation (not checked); NULL = diag(-1, -1, 1), t = 0: what
+ * create_scene applies to the whole scene (OpenCV camera axes -> glTF's y up, z towards the viewer).  It is a
+ * rotation, so the faces keep their winding and one index buffer serves every person.
+ * verts, vstride, faces, adj_off, adj as in mhmr_render_desc (faces with an index outside [0, V) contribute
+ * nothing); F == 0: no face is read and every normal is (0, 0, 1).
+ * V <= 0, F < 0, P < 0, vstride < 3 V with P > 1, out == NULL with P > 0 -> MHMR_ERR_BAD_SHAPE; another null
+ * pointer that would be read or written -> MHMR_ERR_BAD_ARG; both before any launch.  P == 0 launches nothing and
+ * returns 0.  No allocation, no workspace, no synchronisation; the launch goes to `stream`; re-entrant.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int P, V, F;
+    const float* verts;
+    long long vstride;
+    const int* faces;
+    const int* adj_off;
+    const int* adj;
+    const float* transform;
+    float* out;
+    float* bounds;
+} mhmr_scene_desc;
+
+int mhmr_scene_pack(const mhmr_scene_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement: hipEvent brackets around every launch of one kernel family (0 = GEMM, 1 = attention, 2 = LBS
  * vertex kernel), recorded on the launch stream.  enable(kind >= 0) starts a fresh window, enable(-1) stops;
  * collect() synchronises the recorded events and returns launches, summed milliseconds and summed work

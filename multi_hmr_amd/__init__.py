@@ -2,10 +2,12 @@
 from .model import Model  # noqa: F401
 from .demo import create_rotating_video, forward_model, get_camera_parameters, load_model, open_image, overlay_human_meshes  # noqa: F401
 from .render import render_batch, render_meshes, render_views  # noqa: F401
+from .scene import create_scene, export_batch, get_bbox, pack_meshes, print_distance_on_image, read_glb  # noqa: F401
 
 from .preprocess import Preprocessor  # noqa: F401
 from .graphed import GraphedForward  # noqa: F401
 from .pipeline import ImageResult, PipelineError, predict_images  # noqa: F401
 
-__all__ = ["Model", "GraphedForward", "ImageResult", "PipelineError", "Preprocessor", "create_rotating_video", "forward_model", "get_camera_parameters", "load_model",
-           "open_image", "overlay_human_meshes", "predict_images", "render_batch", "render_meshes", "render_views"]
+__all__ = ["Model", "GraphedForward", "ImageResult", "PipelineError", "Preprocessor", "create_rotating_video", "create_scene", "export_batch", "forward_model", "get_bbox",
+           "get_camera_parameters", "load_model", "open_image", "overlay_human_meshes", "pack_meshes", "predict_images", "print_distance_on_image",
+           "read_glb", "render_batch", "render_meshes", "render_views"]

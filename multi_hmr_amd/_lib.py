@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "anny.hip", "render.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "anny.hip", "render.hip", "scene.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -32,8 +32,8 @@ class MhmrError(RuntimeError):
 #: op_sel-swizzled v_pk_*_f32 code returned wrong values in two kernels on gfx950, and the scalar build is 2 % faster.
 COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP"]
 #: per-translation-unit extra flags.  render.hip: every step rounded on its own (the render contract's fp64 geometry and fp32 blend
-#: are restated operation by operation in numpy by the tests; an FMA would change the last bit).
-EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"]}
+#: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  scene.hip: the same fp64 geometry.
+EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -138,6 +138,12 @@ class RenderDesc(C.Structure):
                  ("workspace_bytes", C.c_longlong), ("key_out", _vp), ("rgb_out", _vp)])
 
 
+class SceneDesc(C.Structure):
+    """include/mhmr.h mhmr_scene_desc."""
+    _fields_ = ([(n, _i) for n in ("P", "V", "F")] + [("verts", _vp), ("vstride", C.c_longlong)] +
+                [(n, _vp) for n in ("faces", "adj_off", "adj", "transform", "out", "bounds")])
+
+
 class PreImage(C.Structure):
     """include/mhmr.h mhmr_pre_image: one image of mhmr_preprocess_u8_batch (device pointers + the geometry of its plan)."""
     _fields_ = ([("img", _vp)] + [(n, _i) for n in ("H", "W", "ow", "oh", "y0", "rows", "pad_x", "pad_y", "ksh", "ksv")] +
@@ -193,6 +199,7 @@ _SIGS = {
     "mhmr_render_meshes": ([C.POINTER(RenderDesc), _vp], _i),
     "mhmr_render_views_workspace_bytes": ([C.POINTER(RenderDesc), _i], C.c_longlong),
     "mhmr_render_views": ([C.POINTER(RenderDesc), _i, _vp, _vp], _i),
+    "mhmr_scene_pack": ([C.POINTER(SceneDesc), _vp], _i),
     "mhmr_prof_enable": ([_i], _i),
     "mhmr_prof_collect": ([C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)], _i),
 }

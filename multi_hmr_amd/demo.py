@@ -2,9 +2,9 @@
 ``load_model``, ``forward_model``), ``overlay_human_meshes`` (lines 128-158, drawn by ``render.render_batch`` on the GPU),
 ``create_rotating_video`` (lines 160-241, every rotated frame drawn by one ``render.render_views`` call) and the command line
 (lines 231-386: ``python -m multi_hmr_amd.demo``, writing ``[input | overlay]`` side by side, ``[input | overlay | view]`` with
-``--extra_views 1``, and the rotating video with ``--save_rotating_video 1``).  The video is written as an animated PNG, not mp4 (no
-video encoder here).  Not carried over (no trimesh here, and the reference reads ``verts_smplx`` / ``j2d_smplx``, which no model
-emits): GLB / mesh export and the distance annotation."""
+``--extra_views 1``, and the rotating video with ``--save_rotating_video 1``; ``--save_mesh 1`` adds the vertices as ``.npy`` and the
+scene as ``.glb``, ``--distance 1`` writes every person's distance on the overlay: ``scene.py``).  The video is written as an animated
+PNG, not mp4 (no video encoder here)."""
 from __future__ import annotations
 
 import os
@@ -15,6 +15,7 @@ import torch
 from .model import Model
 
 from .preprocess import IMG_NORM_MEAN, IMG_NORM_STD, get_camera_parameters, open_image  # noqa: F401  (demo.py:27-68 on the GPU)
+from .scene import create_scene, get_bbox, print_distance_on_image  # noqa: F401  (utils/render.py:62-173, 365-405)
 
 CACHE_DIR_MULTIHMR = "models/multiHMR"          # reference utils/constants.py:9
 
@@ -145,11 +146,13 @@ def create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=Fa
 
 
 def main(argv=None):
-    """demo.py:231-386 without the mesh export and distance options: every image of --img_folder -> forward -> overlay ->
-    ``<out_folder>/<image>_<model>.png`` = [input | overlay], or [input | overlay | view] with --extra_views 1 (the persons turned
-    30 degrees about y, over white; a white panel where nobody was detected); --save_rotating_video 1 adds
-    ``<image>_<model>_rotating.png`` (animated, when somebody was detected).  ``--batch_size N`` > 1 infers N images per forward
-    (``pipeline.predict_images``) and draws each result as before.  Returns every path written."""
+    """demo.py:231-386: every image of --img_folder -> forward -> overlay -> ``<out_folder>/<image>_<model>.png`` = [input | overlay],
+    or [input | overlay | view] with --extra_views 1 (the persons turned 30 degrees about y, over white; a white panel where nobody
+    was detected); --save_rotating_video 1 adds ``<image>_<model>_rotating.png`` (animated, when somebody was detected); --distance 1
+    writes every person's distance from the camera on the overlay panel; --save_mesh 1 adds ``<image>_<model>.png.npy`` (float32
+    [P, V, 3], the persons' vertices) and ``<image>_<model>.png.glb`` (``scene.create_scene``: the persons in the overlay's colours,
+    the photograph and the camera).  ``--batch_size N`` > 1 infers N images per forward (``pipeline.predict_images``) and draws each
+    result as before.  Returns every path written."""
     from argparse import ArgumentParser
     from PIL import Image
     from .preprocess import open_image
@@ -164,6 +167,8 @@ def main(argv=None):
     parser.add_argument("--unique_color", type=int, default=0, choices=[0, 1])
     parser.add_argument("--extra_views", type=int, default=0, choices=[0, 1])
     parser.add_argument("--save_rotating_video", type=int, default=0, choices=[0, 1])
+    parser.add_argument("--distance", type=int, default=0, choices=[0, 1])
+    parser.add_argument("--save_mesh", type=int, default=0, choices=[0, 1])
     parser.add_argument("--batch_size", type=int, default=1, help="> 1: decode, preprocess and infer that many images per forward "
                         "(pipeline.predict_images); the files written are the same")
     args = parser.parse_args(argv)
@@ -186,7 +191,9 @@ def main(argv=None):
         """Overlay (+ side view, + rotating video) of one image with its full-resolution camera K -> the files of that image."""
         save_fn = os.path.join(args.out_folder, f"{img_path}_{model_name}.png")
         os.makedirs(os.path.dirname(save_fn), exist_ok=True)
-        pred, _ = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha)
+        pred, _color = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha)
+        if args.distance:                                                # demo.py:348-350, with the camera of the photograph
+            pred = print_distance_on_image(pred, humans, _color, K=K)
         l_img = [np.asarray(img_pil_visu), pred]
         if args.extra_views:                                             # demo.py:351-354: the side view, 30 degrees about y
             frames = create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha,
@@ -200,6 +207,16 @@ def main(argv=None):
             if create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha, fn=fn,
                                      n_frames=20, angle_range=60) is not None:
                 written.append(os.path.splitext(fn)[0] + ".png")
+        if args.save_mesh:                                               # demo.py:370-384
+            name = "verts_smplx" if humans and "verts_smplx" in humans[0] else "v3d"
+            l_mesh = [h[name] for h in humans]
+            V = int(model.smpl_layer["neutral_10"].bm_x.num_vertices)
+            verts = _stacked(l_mesh).detach().float().cpu().numpy() if humans else np.zeros((0, V, 3), np.float32)
+            np.save(save_fn + ".npy", verts)
+            cols = [_color[j % len(_color)] for j in range(len(humans))]  # the overlay's colours, where the reference draws new ones
+            scene = create_scene(img_pil_visu, l_mesh, [faces for _ in humans], color=cols, metallicFactor=0., roughnessFactor=0.5, K=K)
+            scene.export(save_fn + ".glb")
+            written.extend([save_fn + ".npy", save_fn + ".glb"])
 
     if args.batch_size > 1:                                              # one forward per batch_size images, then the same drawing
         from .pipeline import predict_images
