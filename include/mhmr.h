@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
+#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
 #define MHMR_OK 0
 #define MHMR_ERR_BAD_ARG (-1)
@@ -512,6 +512,64 @@ int mhmr_preprocess_u8_batch(const mhmr_pre_image* host, const mhmr_pre_image* d
  * ---------------------------------------------------------------------------------------------------------- */
 int mhmr_eval_mesh_errors(const float* pred, const float* gt, const float* pred_center, const float* gt_center, int M,
                           int V, float* pve, float* pa_pve, float* Rts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Ground truth for the evaluation loop: what the reference's Trainer.prepare_gt (train.py:58-182)
+ * and the 3DPW branch of its evaluate (train.py:383-429) compute with the smplx package and dense matrices.
+ *
+ * mhmr_body_forward: smplx.lbs.lbs (pose2rot=True) for a body model described by data -- SMPL (6890 vertices, 24
+ * joints), SMPL-X (10475, 55) or any other member of the family -- in fp32 throughout, with fp32 constants:
+ *   pose [G][J][3] rotation vectors, joint 0 = the global orientation (applied about the rest pelvis, as upstream);
+ *   batch_rodrigues' convention angle = |v + 1e-8|;  coef [G][nc] = [betas | expression];  transl [G][3] (NULL = 0)
+ *   added to vertices and joints;  K [G][3][3] (NULL = no projection; utils/camera.py:14-27 otherwise).
+ *   vertices [G][V][3];  joints [G][J + E + L][3] = the posed joints, E vertices picked by id, L barycentric
+ *   landmarks (sum_f bary[l][f] * vertex lmk_idx[l][f]);  v2d [G][V][2], j2d [G][J + E + L][2] when K is given.
+ * Workspaces: ws_F [ceil(G / 8)][K][8] floats, ws_A [G][J][12] floats.  Three launches on `stream`, no allocation,
+ * no synchronisation.  J > 64, K != nc + 9 (J - 1), K > 1536 or Vp not a multiple of 64 -> MHMR_ERR_BAD_SHAPE;
+ * G == 0 launches nothing.  parents[i] < i for i > 0 is the caller's duty (multi_hmr_amd/bodymodel.py checks it).
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int V, Vp;                /* vertices; V rounded up to a multiple of 64 (columns of the operands, zero-padded)   */
+    int J, nc, K;             /* joints; shape + expression directions; K = nc + 9 (J - 1) rows of the basis          */
+    int E, L;                 /* picked-vertex joints, landmarks (either may be 0)                                    */
+    const float* vtemp;       /* [3][Vp]       v_template                                                             */
+    const float* basis;       /* [K][3][Vp]    [shapedirs(nb) | exprdirs(ne) | posedirs(9 (J - 1))]                  */
+    const float* J0;          /* [J*3]         J_regressor . v_template                                               */
+    const float* JS;          /* [J*3][nc]     J_regressor . dirs                                                     */
+    const int* parents;       /* [J]           parents[0] is ignored                                                  */
+    const float* weights;     /* [J][Vp]       dense skinning weights, joint-major                                    */
+    const int* extra_idx;     /* [E]                                                                                  */
+    const int* lmk_idx;       /* [L][3]        faces[lmk_faces_idx]                                                   */
+    const float* lmk_bary;    /* [L][3]                                                                               */
+} mhmr_body_consts;
+
+int mhmr_body_forward(const mhmr_body_consts* c, const float* pose, const float* coef, const float* transl, const float* K, int G,
+                      float* ws_F, float* ws_A, float* vertices, float* joints, float* v2d, float* j2d, void* stream);
+
+/* Sparse vertex regressor: out [M][R][3] = A . (in [M][Vin][3] - center [M][3]) for A in CSR form (rowptr [R + 1],
+ * col, val); center NULL = none.  Each row is summed in the order of its entries (the loaders sort them by column) in
+ * fp64 and rounded once: deterministic.  A row without entries gives zeros; an entry whose column is outside
+ * [0, Vin) is skipped. */
+int mhmr_sparse_regress(const int* rowptr, const int* col, const float* val, int R, int Vin, const float* in, const float* center,
+                        int M, float* out, void* stream);
+
+/* Detection targets of train.py:136-158 for n humans listed in (image, human) order: joints [n][NJ][3], K [n][3][3],
+ * img [n] (image of each human, 0 <= img < B), the grid is Gp x Gp cells of `patch` pixels:
+ *   loc [n][2] = projection of joint `center_joint`;  pk_idx [n][2] = clamp(floor(loc / patch), 0, Gp - 1) as (x, y);
+ *   offset = (loc - (pk_idx + 0.5) patch) / patch;
+ *   dist_pp [n] = (nearness ? log(z_pelvis + 1e-10) : z_pelvis) * fn / K[0][0]  (utils/camera.py:62-84);
+ *   scores [B][Gp][Gp] indexed [image][y][x]: 1 in every claimed cell;  visible [n]: of several humans in one cell the
+ *   first of the list stays visible (atomicMin of the list index per cell, then a compare: the result does not depend on
+ *   execution order).  ws_owner: B Gp Gp ints.  scores and ws_owner are (re)initialised by the call. */
+int mhmr_gt_targets(const float* joints, int NJ, int center_joint, const float* K, const int* img, int n, int B, int Gp, int patch,
+                    float fn, int nearness, float* loc, int* pk_idx, float* offset, float* dist_pp, float* scores, int* visible,
+                    int* ws_owner, void* stream);
+
+/* utils/camera.py:14-27 perspective_projection: pts [n][N][3], K [n][3][3] -> out [n][N][2] = (K (x / x_z))[:2]. */
+int mhmr_project_points(const float* pts, const float* K, int n, int N, float* out, void* stream);
+
+/* roma.rotvec_to_rotmat (train.py:165): rotvec [n][3] -> rotmat [n][3][3], axis = v / max(|v|, 1e-6). */
+int mhmr_rotvec_to_rotmat(const float* rotvec, int n, float* rotmat, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Mesh overlay (reference demo.py:128-158 overlay_human_meshes -> utils/render.py:175-315 render_meshes, which

@@ -1,0 +1,199 @@
+"""Ground-truth body models: what the reference builds with ``smplx.create(SMPLX_DIR, 'smplx', num_betas=11)`` and
+``smplx.create(SMPLX_DIR, 'smpl', gender=...)`` (train.py:41-43) and calls in ``prepare_gt`` (train.py:76-109), on ``mhmr_body_forward``
+(csrc/bodymodel.hip): the general fp32 layer -- full pose with the global orientation, eye poses, ``transl``, any vertex / joint count.
+``Model``'s own SMPL-X layer (csrc/lbs.hip) is the PREDICTION's layer and cannot serve here (f16 correctives, 53 rotations, no transl).
+
+There is no CPU path: calling a ``BodyModel`` with CPU tensors raises."""
+from __future__ import annotations
+
+import os
+import pickle
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import _lib
+from .constants import SMPL_EXTRA_JOINT_VERTS, SMPL_NUM_JOINTS, SMPLX_EXTRA_JOINT_VERTS, SMPLX_NUM_JOINTS
+
+VERTEX_TILE = 64          # csrc/bodymodel.hip VT
+PERSON_GROUP = 8          # csrc/bodymodel.hip PG
+
+
+def _dense(a):
+    """numpy array of a model-file entry: scipy-sparse matrices (J_regressor of the SMPL pickles) and array wrappers with ``.r``."""
+    if hasattr(a, "toarray"):
+        a = a.toarray()
+    elif hasattr(a, "r") and not isinstance(a, np.ndarray):
+        a = a.r
+    return np.asarray(a)
+
+
+def load_body_data(data) -> dict:
+    """A dict is taken as it is; ``.npz`` is read with numpy; anything else is tried as a pickle with the latin-1 encoding the
+    python-2 SMPL files need.  The original SMPL pickles hold ``chumpy`` arrays: without that package they cannot be read, and the
+    error says what to do instead of a bare ModuleNotFoundError."""
+    if isinstance(data, dict):
+        return data
+    path = os.fspath(data)
+    if path.endswith(".npz"):
+        return dict(np.load(path, allow_pickle=True))
+    try:
+        with open(path, "rb") as f:
+            out = pickle.load(f, encoding="latin1")
+    except ModuleNotFoundError as e:
+        if "chumpy" in str(e):
+            raise _lib.MhmrError(f"{path} stores chumpy arrays and the chumpy package is not installed: convert the file once to plain "
+                                 "numpy (the 'clean_ch' step of the smplx tools, or np.savez of the arrays) and pass that") from e
+        raise
+    if not isinstance(out, dict):
+        raise _lib.MhmrError(f"{path}: expected a pickled dict of model arrays, got {type(out).__name__}")
+    return out
+
+
+class BodyModel:
+    """``BodyModel(data, model_type='smplx' | 'smpl', num_betas=..., num_expression_coeffs=10)``; called with smplx's keyword names it
+    returns an object with ``.vertices [G, V, 3]`` and ``.joints [G, J + E + L, 3]`` (SMPL-X: 55 + 21 + 51 = 127, SMPL: 24 + 21 = 45).
+    Ours, not smplx's: ``K=[G, 3, 3]`` also returns ``.v2d`` / ``.j2d`` (utils/camera.py:14-27) from the same launches.
+    ``data`` may carry ``extra_joint_verts`` to override the picked vertex ids of constants.py."""
+
+    def __init__(self, data, model_type: str = "smplx", num_betas: int | None = None, num_expression_coeffs: int = 10):
+        if model_type not in ("smplx", "smpl"):
+            raise ValueError(f"model_type {model_type!r}: 'smplx' or 'smpl'")
+        data = load_body_data(data)
+        self.model_type = model_type
+        self.num_betas = int(num_betas if num_betas is not None else 10)
+        self.num_expression_coeffs = int(num_expression_coeffs) if model_type == "smplx" else 0
+        f32 = lambda a: np.ascontiguousarray(_dense(a), dtype=np.float32)
+        self.v_template = f32(data["v_template"])
+        self.num_vertices = V = int(self.v_template.shape[0])
+        self.faces = np.asarray(_dense(data["f"]), dtype=np.int64)
+        self.J_regressor = f32(data["J_regressor"])
+        self.num_joints = J = int(self.J_regressor.shape[0])
+        want = SMPLX_NUM_JOINTS if model_type == "smplx" else SMPL_NUM_JOINTS
+        if J != want:
+            raise ValueError(f"{model_type}: {want} joints expected, the data has {J}")
+        sd = _dense(data["shapedirs"])
+        if sd.shape[-1] < self.num_betas:
+            raise ValueError(f"num_betas={self.num_betas} but shapedirs has {sd.shape[-1]} directions")
+        dirs = [sd[:, :, :self.num_betas]]
+        if self.num_expression_coeffs:
+            if sd.shape[-1] < 300 + self.num_expression_coeffs:
+                raise ValueError("shapedirs holds no expression directions at 300:")
+            dirs.append(sd[:, :, 300:300 + self.num_expression_coeffs])
+        self.shapedirs = np.ascontiguousarray(np.concatenate(dirs, axis=-1), dtype=np.float32)          # [V, 3, nc]
+        pd = _dense(data["posedirs"])
+        self.posedirs = np.ascontiguousarray(pd.reshape(V, 3, -1), dtype=np.float32)                    # [V, 3, 9 (J - 1)]
+        if self.posedirs.shape[-1] != 9 * (J - 1):
+            raise ValueError(f"posedirs: {9 * (J - 1)} correctives expected, got {self.posedirs.shape[-1]}")
+        self.lbs_weights = f32(data["weights"])
+        parents = np.asarray(_dense(data["kintree_table"]))[0].astype(np.int64).copy()
+        parents[0] = -1
+        if not all(0 <= int(parents[i]) < i for i in range(1, J)):
+            raise ValueError("kintree_table: every joint's parent must come before it")
+        self.parents = parents
+        default = SMPLX_EXTRA_JOINT_VERTS if model_type == "smplx" else SMPL_EXTRA_JOINT_VERTS
+        self.extra_joint_verts = np.asarray(data.get("extra_joint_verts", default), dtype=np.int64).reshape(-1)
+        if self.extra_joint_verts.size and not (0 <= self.extra_joint_verts.min() and self.extra_joint_verts.max() < V):
+            raise ValueError("extra_joint_verts outside the mesh")
+        if model_type == "smplx":
+            self.lmk_vidx = self.faces[np.asarray(data["lmk_faces_idx"], dtype=np.int64)]               # [L, 3]
+            self.lmk_bary = f32(data["lmk_bary_coords"])
+            if not (0 <= self.lmk_vidx.min() and self.lmk_vidx.max() < V):
+                raise ValueError("landmark faces outside the mesh")
+        else:
+            self.lmk_vidx, self.lmk_bary = np.zeros((0, 3), dtype=np.int64), np.zeros((0, 3), dtype=np.float32)
+        self.num_out_joints = J + len(self.extra_joint_verts) + len(self.lmk_vidx)
+        self._packed: dict = {}
+
+    # ---- constants, once per device
+    def _consts(self, device):
+        key = (device.type, device.index)
+        if key in self._packed:
+            return self._packed[key]
+        V, J = self.num_vertices, self.num_joints
+        Vp = -(-V // VERTEX_TILE) * VERTEX_TILE
+        nc = self.shapedirs.shape[-1]
+        K = nc + 9 * (J - 1)
+        basis = np.zeros((K, 3, Vp), dtype=np.float32)
+        basis[:nc, :, :V] = self.shapedirs.transpose(2, 1, 0)
+        basis[nc:, :, :V] = self.posedirs.transpose(2, 1, 0)
+        vtemp = np.zeros((3, Vp), dtype=np.float32)
+        vtemp[:, :V] = self.v_template.T
+        Jr = self.J_regressor.astype(np.float64)
+        J0 = Jr @ self.v_template.astype(np.float64)
+        JS = np.einsum("jv,vkl->jkl", Jr, self.shapedirs.astype(np.float64)).reshape(J * 3, nc)
+        W = np.zeros((J, Vp), dtype=np.float32)
+        W[:, :V] = self.lbs_weights.T
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)
+        p = dict(vtemp=t(vtemp, torch.float32), basis=t(basis, torch.float32), J0=t(J0.reshape(-1), torch.float32), JS=t(JS, torch.float32),
+                 parents=t(self.parents, torch.int32), weights=t(W, torch.float32), extra_idx=t(self.extra_joint_verts, torch.int32),
+                 lmk_idx=t(self.lmk_vidx, torch.int32), lmk_bary=t(self.lmk_bary, torch.float32))
+        c = _lib.BodyConsts()
+        c.V, c.Vp, c.J, c.nc, c.K, c.E, c.L = V, Vp, J, nc, K, len(self.extra_joint_verts), len(self.lmk_vidx)
+        for k, v in p.items():
+            setattr(c, k, v.data_ptr() if v.numel() else None)
+        p["struct"], p["K"], p["nc"] = c, K, nc
+        self._packed[key] = p
+        return p
+
+    @property
+    def basis_bytes(self) -> int:
+        """Bytes of the blend basis one pass of the vertex kernel streams (the roofline's numerator, per 8 persons)."""
+        Vp = -(-self.num_vertices // VERTEX_TILE) * VERTEX_TILE
+        return (self.shapedirs.shape[-1] + 9 * (self.num_joints - 1)) * 3 * Vp * 4
+
+    @property
+    def expression(self):
+        """Zeros ``[1, num_expression_coeffs]`` (train.py:108 reads ``smplx_neutral_11.expression``)."""
+        return torch.zeros(1, self.num_expression_coeffs)
+
+    def full_pose(self, G, dev, global_orient=None, body_pose=None, jaw_pose=None, leye_pose=None, reye_pose=None, left_hand_pose=None,
+                  right_hand_pose=None):
+        part = lambda t, n: (torch.zeros(G, n, 3, device=dev) if t is None else t.to(device=dev, dtype=torch.float32).reshape(G, n, 3))
+        if self.model_type == "smpl":
+            if any(t is not None for t in (jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)):
+                raise TypeError("SMPL takes global_orient, body_pose, betas and transl only")
+            parts = [part(global_orient, 1), part(body_pose, 23)]
+        else:
+            parts = [part(global_orient, 1), part(body_pose, 21), part(jaw_pose, 1), part(leye_pose, 1), part(reye_pose, 1),
+                     part(left_hand_pose, 15), part(right_hand_pose, 15)]
+        return torch.cat(parts, dim=1).contiguous()
+
+    @torch.no_grad()
+    def __call__(self, global_orient=None, body_pose=None, jaw_pose=None, leye_pose=None, reye_pose=None, left_hand_pose=None,
+                 right_hand_pose=None, betas=None, expression=None, transl=None, K=None, **unused):
+        given = [t for t in (global_orient, body_pose, betas, transl, jaw_pose, left_hand_pose) if t is not None]
+        if not given:
+            raise ValueError("BodyModel needs at least one of global_orient, body_pose, betas, transl to know the batch")
+        dev = given[0].device
+        if dev.type != "cuda":
+            raise _lib.MhmrError("BodyModel runs on the HIP device only (no CPU fallback)")
+        G = int(given[0].shape[0])
+        if self.model_type == "smpl" and expression is not None:
+            raise TypeError("SMPL has no expression")
+        V, NJ, ne = self.num_vertices, self.num_out_joints, self.num_expression_coeffs
+        out = SimpleNamespace(vertices=torch.empty(G, V, 3, device=dev), joints=torch.empty(G, NJ, 3, device=dev), v2d=None, j2d=None)
+        if K is not None:
+            out.v2d, out.j2d = torch.empty(G, V, 2, device=dev), torch.empty(G, NJ, 2, device=dev)
+        if G == 0:
+            return out
+        p = self._consts(dev)
+        pose = self.full_pose(G, dev, global_orient, body_pose, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)
+        f = lambda t, n: (torch.zeros(G, n, device=dev) if t is None else t.to(device=dev, dtype=torch.float32).reshape(G, n))
+        coef = f(betas, self.num_betas)
+        if ne:
+            coef = torch.cat([coef, f(expression, ne)], dim=1)
+        coef = coef.contiguous()
+        tr = None if transl is None else transl.to(device=dev, dtype=torch.float32).reshape(G, 3).contiguous()
+        Kc = None if K is None else K.to(device=dev, dtype=torch.float32).reshape(G, 3, 3).contiguous()
+        groups = -(-G // PERSON_GROUP)
+        ws_F = torch.empty(groups, p["K"], PERSON_GROUP, device=dev)
+        ws_A = torch.empty(G, self.num_joints, 12, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mhmr_body_forward(p["struct"], pose.data_ptr(), coef.data_ptr(), _lib.ptr(tr), _lib.ptr(Kc), G, ws_F.data_ptr(),
+                                                    ws_A.data_ptr(), out.vertices.data_ptr(), out.joints.data_ptr(), _lib.ptr(out.v2d),
+                                                    _lib.ptr(out.j2d), torch.cuda.current_stream(dev).cuda_stream), "mhmr_body_forward")
+        return out
+
+    forward = __call__

@@ -47,6 +47,27 @@ _LMK = [f"face_landmark_{i}" for i in range(51)]
 SMPLX_JOINT_NAMES = _BODY + _HANDS + _EXTRA + _LMK
 assert len(SMPLX_JOINT_NAMES) == 127 and SMPLX_JOINT_NAMES[15] == "head" and SMPLX_JOINT_NAMES[55] == "nose"
 
+# ----------------------------------------------------------------------------------------------
+# SMPL topology (ground truth of 3DPW, train.py:42-43, 76-94) and the H36M joint subset of its metrics
+# ----------------------------------------------------------------------------------------------
+SMPL_NUM_VERTS = 6890
+SMPL_NUM_JOINTS = 24
+SMPL_PARENTS = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21]
+
+#: [3P-mem] smplx/vertex_ids.py ``vertex_ids['smplh']`` (what smplx.SMPL's VertexJointSelector picks), written from memory of the
+#: published file -- no copy of the smplx package was available to check against; in VertexJointSelector's order (face, feet, left
+#: finger tips, right finger tips).  ``BodyModel(data)`` takes ``data['extra_joint_verts']`` instead when it is there.
+SMPL_EXTRA_JOINT_VERTS = [
+    332, 6260, 2800, 4071, 583,          # nose, reye, leye, rear, lear
+    3216, 3226, 3387, 6617, 6624, 6787,  # LBigToe, LSmallToe, LHeel, RBigToe, RSmallToe, RHeel
+    2746, 2319, 2445, 2556, 2673,        # lthumb, lindex, lmiddle, lring, lpinky
+    6191, 5782, 5905, 6016, 6133,        # rthumb, rindex, rmiddle, rring, rpinky
+]
+
+#: train.py:402-403 (SPIN constants.py): rows of J_regressor_h36m in the order of the 17 / 14 evaluation joints
+H36M_TO_J17 = [6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10, 0, 7, 9]
+H36M_TO_J14 = H36M_TO_J17[:14]
+
 
 VIT_CFG = {
     "dinov2_vits14": dict(embed_dim=384, depth=12, num_heads=6),

@@ -4,7 +4,12 @@ Procrustes-aligned per-vertex error (and the same on regressed joints).  Matchin
 stays on the host exactly as in the reference (``utils/training.py:9-195``); the mesh metrics run in
 ``mhmr_eval_mesh_errors`` on the device where the vertices already are.  Datasets are not part of this repository: the
 caller provides ground truth dicts with the keys the reference's ``prepare_gt`` produces (``j2d [G,J,2]``, ``v3d [G,V,3]``,
-``transl_pelvis [G,1,3]``, ``K``)."""
+``transl_pelvis [G,1,3]``, ``K``) -- or builds them from the datasets' annotations with ``groundtruth.GroundTruth``.
+
+The 3DPW branch (train.py:383-384, 396-429): SMPL ground truth (6890 vertices) is compared with the prediction mapped onto the SMPL
+topology by the ``smplx2smpl`` matrix, and MPJPE / PA-MPJPE are taken on 14 H36M joints regressed from both meshes.  Both matrices
+are sparse (a handful of non-zeros per row of the 6890 x 10475 one, which the reference multiplies as a dense 288 MB matrix): they
+are held in CSR form and applied by ``mhmr_sparse_regress``."""
 from __future__ import annotations
 
 from itertools import product
@@ -111,6 +116,73 @@ def mesh_errors(pred_pts, gt_pts, pred_center=None, gt_center=None, return_trans
     return (pve, pa, rts) if return_transform else (pve, pa)
 
 
+def csr_from_matrix(matrix):
+    """Dense (numpy / torch) or scipy-sparse matrix -> (rowptr int32 [R + 1], col int32, val float32, (R, C)); the entries of a row
+    are in ascending column order (the kernel sums them in that order), explicit zeros are dropped."""
+    if hasattr(matrix, "tocsr"):
+        m = matrix.tocsr().copy()
+        m.sum_duplicates()
+        m.sort_indices()
+        m.eliminate_zeros()
+        return (np.asarray(m.indptr, dtype=np.int32), np.asarray(m.indices, dtype=np.int32), np.asarray(m.data, dtype=np.float32),
+                (int(m.shape[0]), int(m.shape[1])))
+    if isinstance(matrix, torch.Tensor):
+        matrix = matrix.detach().cpu().numpy()
+    a = np.asarray(matrix)
+    if a.ndim != 2:
+        raise ValueError(f"a regressor is a matrix, got shape {a.shape}")
+    rows, cols = np.nonzero(a)                                  # row-major: ascending columns inside a row
+    rowptr = np.zeros(a.shape[0] + 1, dtype=np.int32)
+    np.cumsum(np.bincount(rows, minlength=a.shape[0]), out=rowptr[1:])
+    return rowptr, cols.astype(np.int32), a[rows, cols].astype(np.float32), (int(a.shape[0]), int(a.shape[1]))
+
+
+class SparseRegressor:
+    """``out [M, R, 3] = A (x [M, C, 3] - center [M, 3])`` on the device for a fixed sparse ``A`` (CSR made once here, uploaded once per
+    device).  Deterministic: a row is summed in column order."""
+
+    def __init__(self, matrix):
+        self.rowptr, self.col, self.val, self.shape = csr_from_matrix(matrix)
+        if self.col.size and not (0 <= int(self.col.min()) and int(self.col.max()) < self.shape[1]):
+            raise ValueError("column index outside the matrix")
+        self._dev = {}
+
+    @property
+    def nnz(self):
+        return int(self.val.size)
+
+    def __call__(self, x, center=None):
+        if x.device.type != "cuda":
+            raise _lib.MhmrError("SparseRegressor runs on the HIP device only (no CPU fallback)")
+        R, Cn = self.shape
+        assert x.dim() == 3 and x.shape[1] == Cn and x.shape[2] == 3, (tuple(x.shape), self.shape)
+        dev, M = x.device, int(x.shape[0])
+        key = (dev.type, dev.index)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(a).to(dev) for a in (self.rowptr, self.col, self.val))
+        rp, co, va = self._dev[key]
+        x = x.to(torch.float32).contiguous()
+        c = None if center is None else center.to(device=dev, dtype=torch.float32).reshape(M, 3).contiguous()
+        out = torch.empty(M, R, 3, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mhmr_sparse_regress(rp.data_ptr(), _lib.ptr(co) if co.numel() else None, _lib.ptr(va) if va.numel() else None,
+                                                      R, Cn, x.data_ptr(), _lib.ptr(c), M, out.data_ptr(),
+                                                      torch.cuda.current_stream(dev).cuda_stream), "mhmr_sparse_regress")
+        return out
+
+
+def load_smplx2smpl(path) -> SparseRegressor:
+    """train.py:44-45: the pickle with key ``'matrix'`` (6890 x 10475, dense or scipy-sparse)."""
+    import pickle
+    with open(path, "rb") as f:
+        return SparseRegressor(pickle.load(f, encoding="latin1")["matrix"])
+
+
+def load_h36m_regressor(path) -> SparseRegressor:
+    """train.py:400: ``J_regressor_h36m.npy`` (17 x 6890)."""
+    return SparseRegressor(np.load(path))
+
+
 class Evaluator:
     """Accumulates the reference's metrics over batches::
 
@@ -121,7 +193,13 @@ class Evaluator:
         print(ev.summary())                      # pve, pa_pve (mm), precision, recall, f1_score (%)
     """
 
-    def __init__(self):
+    def __init__(self, smplx2smpl=None, h36m_regressor=None):
+        """``smplx2smpl``: when the ground truth has 6890 vertices the prediction is regressed to SMPL before PVE / PA-PVE
+        (train.py:383-384).  ``h36m_regressor``: mpjpe / pa_mpjpe are taken on the 14 joints ``H36M_TO_J14`` regressed from the (SMPL)
+        meshes and centred on H36M joint 0 (train.py:396-429) instead of the body model's own joints.  Both: a ``SparseRegressor`` or a
+        matrix."""
+        as_reg = lambda m: m if m is None or isinstance(m, SparseRegressor) else SparseRegressor(m)
+        self.smplx2smpl, self.h36m_regressor = as_reg(smplx2smpl), as_reg(h36m_regressor)
         self.count = self.miss = self.fp = 0
         self._sums = {k: torch.zeros((), dtype=torch.float64) for k in ("pve", "pa_pve", "mpjpe", "pa_mpjpe")}
         self._n = self._nj = 0
@@ -146,11 +224,25 @@ class Evaluator:
         c_hat = torch.stack([pred[i]["transl_pelvis"].reshape(3) for i in pid])
         v_gt = gt["v3d"][gid].to(dev)
         c_gt = gt["transl_pelvis"][gid].reshape(-1, 3).to(dev)
+        if v_gt.shape[1] == 6890 and v_hat.shape[1] != 6890:
+            if self.smplx2smpl is None:
+                raise _lib.MhmrError("the ground truth is an SMPL mesh: Evaluator(smplx2smpl=...) is needed to compare (train.py:383-384)")
+            v_hat, c_hat = self.smplx2smpl(v_hat, c_hat), None          # centred, then regressed, as the reference
         pve, pa = mesh_errors(v_hat, v_gt, c_hat, c_gt)
         self._sums["pve"] += pve.double().sum().cpu()
         self._sums["pa_pve"] += pa.double().sum().cpu()
-        if "j3d" in gt:        # joint errors on the body model's own joints, pelvis-centred (the reference regresses H36M joints
-            j_gt = gt["j3d"][gid].to(dev)          # from SMPL vertices for 3DPW only, train.py:398-423: that needs assets we do not have)
+        if self.h36m_regressor is not None:
+            from .constants import H36M_TO_J14
+            if v_hat.shape[1] != self.h36m_regressor.shape[1] or v_gt.shape[1] != self.h36m_regressor.shape[1]:
+                raise _lib.MhmrError("the H36M regressor does not fit the meshes")
+            j14 = torch.as_tensor(H36M_TO_J14, device=dev)
+            h_gt, h_hat = self.h36m_regressor(v_gt, c_gt), self.h36m_regressor(v_hat, c_hat)     # [M, 17, 3] of the centred meshes
+            mp, pamp = mesh_errors(h_hat[:, j14], h_gt[:, j14], h_hat[:, 0], h_gt[:, 0])
+            self._sums["mpjpe"] += mp.double().sum().cpu()
+            self._sums["pa_mpjpe"] += pamp.double().sum().cpu()
+            self._nj += len(best)
+        elif "j3d" in gt:        # joint errors on the body model's own joints, pelvis-centred (without an H36M regressor)
+            j_gt = gt["j3d"][gid].to(dev)
             J = j_gt.shape[1]
             j_hat = torch.stack([pred[i]["j3d"][:J] for i in pid])
             mp, pamp = mesh_errors(j_hat, j_gt, j_hat[:, 0], j_gt[:, 0])
@@ -166,3 +258,32 @@ class Evaluator:
             out.update({k: float(self._sums[k] / self._nj) for k in ("mpjpe", "pa_mpjpe")})
         out.update(precision=precision, recall=recall, f1_score=f1, matched=self._n, count=self.count)
         return out
+
+
+@torch.no_grad()
+def evaluate_dataset(model, batches, gt_builder, det_thresh=0.3, nms_kernel_size=3, use_gt_idx=False, evaluator=None):
+    """The reference's evaluation loop (train.py:346-429) over ``batches`` of ``(x, y)``: ``gt = gt_builder.prepare(y)``, the
+    inference forward with ``K=gt['K']``, matching and metrics; returns ``Evaluator.summary()``.  ``evaluator``: an ``Evaluator`` carrying
+    the regressors (a fresh plain one otherwise).  A batch without humans is skipped (``prepare`` returns None; the reference would fail
+    on ``gt['K']``).
+
+    ``use_gt_idx=True`` is OURS -- the reference has no such switch: the ground truth's own ``gt['idx']`` goes through the
+    ``is_training=True`` forward, so every ground-truth person gets exactly one prediction at its own cell and the mesh metrics are
+    measured without the detector in the way."""
+    ev = evaluator if evaluator is not None else Evaluator()
+    dev = next(iter(model.parameters())).device if hasattr(model, "parameters") else torch.device("cuda")
+    for x, y in batches:
+        y = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in y.items()}
+        gt = gt_builder.prepare(y)
+        if gt is None:
+            continue
+        x = x.to(dev)
+        if use_gt_idx:
+            out = model(x, idx=gt["idx"], K=gt["K"], is_training=True)
+            n = int(gt["idx"][0].shape[0])
+            pelvis = out["transl_pelvis"] if "transl_pelvis" in out else out["j3d"][:, :1]
+            pred = [dict(v3d=out["v3d"][i], j3d=out["j3d"][i], j2d=out["j2d"][i], transl_pelvis=pelvis[i]) for i in range(n)]
+        else:
+            pred = model(x, is_training=False, K=gt["K"], det_thresh=det_thresh, nms_kernel_size=nms_kernel_size)
+        ev.update(pred, gt)
+    return ev.summary()

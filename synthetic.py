@@ -320,3 +320,72 @@ def make_hostile(sd: dict, kind: str, seed: int = 0, strength: float = 1.0) -> d
     else:
         raise ValueError(kind)
     return sd
+
+
+# ----------------------------------------------------------------------------------------------
+# Stand-ins for the assets of the evaluation loop (reference train.py:42-45, 400): gendered SMPL models, the smplx2smpl matrix and
+# J_regressor_h36m.  They draw from generators of their own, so the functions above keep producing the same bytes.
+# ----------------------------------------------------------------------------------------------
+def make_smpl_data(seed: int = 0, gender: str = "male", max_influences: int = 4) -> dict:
+    """A synthetic stand-in for ``SMPL_{MALE,FEMALE}.pkl``: 6890 vertices, 24 joints with the SMPL parent table, 10 shape directions,
+    207 pose correctives; the same 'blob per bone' construction as ``make_smplx_data``.  The two genders differ in every array."""
+    from multi_hmr_amd.constants import SMPL_NUM_JOINTS, SMPL_NUM_VERTS, SMPL_PARENTS
+    rng = np.random.RandomState(seed + {"male": 7001, "female": 7002, "neutral": 7003}[gender])
+    V, J = SMPL_NUM_VERTS, SMPL_NUM_JOINTS
+    parents = np.asarray(SMPL_PARENTS, dtype=np.int64)
+    jt = np.zeros((J, 3), dtype=np.float64)
+    for j in range(1, J):
+        d = rng.randn(3)
+        d /= np.linalg.norm(d)
+        jt[j] = jt[parents[j]] + 0.18 * (0.6 + 0.4 * rng.rand()) * d
+    primary = rng.randint(0, J, size=V)
+    primary[:J] = np.arange(J)
+    v_template = jt[primary] + 0.035 * rng.randn(V, 3)
+    weights = np.zeros((V, J), dtype=np.float64)
+    others = rng.randint(0, J, size=(V, max_influences))
+    alpha = rng.dirichlet(np.ones(max_influences + 2) * 0.7, size=V)
+    for v in range(V):
+        js = [int(primary[v])] + ([int(parents[primary[v]])] if parents[primary[v]] >= 0 else []) + [int(o) for o in others[v]]
+        js = list(dict.fromkeys(js))[:max_influences]
+        w = alpha[v, :len(js)]
+        weights[v, js] = w / w.sum()
+    weights = weights.astype(np.float32)
+    weights[np.arange(V), primary] += (1.0 - weights.astype(np.float64).sum(axis=1)).astype(np.float32)   # rows sum to 1 in fp32 too
+    J_regressor = np.zeros((J, V), dtype=np.float64)
+    for j in range(J):
+        owned = np.nonzero(primary == j)[0]
+        pick = owned[:24] if len(owned) >= 24 else np.concatenate([owned, rng.randint(0, V, 24 - len(owned))])
+        np.add.at(J_regressor[j], pick, rng.dirichlet(np.ones(len(pick))))
+    kintree = np.stack([np.where(parents < 0, 2 ** 32 - 1, parents), np.arange(J)]).astype(np.int64)
+    return {
+        "v_template": v_template.astype(np.float32),
+        "f": rng.randint(0, V, size=(13776, 3)).astype(np.int64),
+        "shapedirs": (0.012 * rng.randn(V, 3, 10)).astype(np.float32),
+        "posedirs": (0.0025 * rng.randn(V, 3, 9 * (J - 1))).astype(np.float32),
+        "J_regressor": J_regressor.astype(np.float32),
+        "weights": weights,
+        "kintree_table": kintree,
+    }
+
+
+def make_smplx2smpl(seed: int = 0, rows: int = 6890, cols: int = SMPLX_NUM_VERTS):
+    """Stand-in for the 'matrix' of ``smplx2smpl.pkl``: every SMPL vertex is a barycentric combination of up to three SMPL-X vertices
+    (rows sum to 1; row 0 has a single weight of exactly 1).  Returned as a scipy CSR matrix: dense it would be 288 MB."""
+    import scipy.sparse as sp
+    rng = np.random.RandomState(seed + 7100)
+    col = rng.randint(0, cols, size=(rows, 3))
+    w = rng.dirichlet(np.ones(3), size=rows).astype(np.float32)
+    w[0], col[0] = (1.0, 0.0, 0.0), (col[0, 0], col[0, 0], col[0, 0])
+    m = sp.coo_matrix((w.reshape(-1), (np.repeat(np.arange(rows), 3), col.reshape(-1))), shape=(rows, cols), dtype=np.float32).tocsr()
+    m.sum_duplicates()
+    m.eliminate_zeros()
+    return m
+
+
+def make_h36m_regressor(seed: int = 0, cols: int = 6890) -> np.ndarray:
+    """Stand-in for ``J_regressor_h36m.npy``: dense float32 [17, cols], each row a convex combination of 32 vertices."""
+    rng = np.random.RandomState(seed + 7200)
+    m = np.zeros((17, cols), dtype=np.float64)
+    for j in range(17):
+        np.add.at(m[j], rng.choice(cols, 32, replace=False), rng.dirichlet(np.ones(32)))
+    return m.astype(np.float32)
