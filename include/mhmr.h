@@ -16,6 +16,10 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the library is built with hidden visibility: the declarations of this header are its whole export surface */
+#if defined(__GNUC__)
+#pragma GCC visibility push(default)
+#endif
 
 #define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
@@ -674,6 +678,9 @@ int mhmr_scene_pack(const mhmr_scene_desc* d, void* stream);
 int mhmr_prof_enable(int kind);
 int mhmr_prof_collect(int* launches, double* total_ms, double* total_work);
 
+#if defined(__GNUC__)
+#pragma GCC visibility pop
+#endif
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,9 @@ class MhmrError(RuntimeError):
 
 #: No SLP vectoriser in any translation unit (csrc/mhmr_common.h has the reasons and refuses a build without -DMHMR_NO_SLP): its
 #: op_sel-swizzled v_pk_*_f32 code returned wrong values in two kernels on gfx950, and the scalar build is 2 % faster.
-COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP"]
+#: Hidden visibility: the dynamic symbols of the library are the declarations of include/mhmr.h (which carry default visibility), not its
+#: internal launchers and template helpers.
+COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: per-translation-unit extra flags.  render.hip: every step rounded on its own (the render contract's fp64 geometry and fp32 blend
 #: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  scene.hip: the same fp64 geometry.
 EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"]}

@@ -1319,7 +1319,7 @@ int mhmr_launch_attention_pitch(const void* qk, const void* vt, void* out, int B
 }
 
 int mhmr_launch_attention(const void* qk, const void* vt, void* out, int B, int T, int Tp, int C, int H, int dtype, int* flags,
-                          hipStream_t s, int ldo = 0, int o8 = 0) {
+                          hipStream_t s, int ldo, int o8) {
     static const char* v = getenv("MHMR_ATTN_VARIANT");      // A/B measurements only
     const int variant = v ? atoi(v) : (flags ? MHMR_ATTN_DEFAULT_VARIANT : 2);
     return mhmr_launch_attention_pitch(qk, vt, out, B, T, Tp, C, H, dtype, 15.f, variant, flags, s, ldo > 0 ? ldo : C, o8);

@@ -6,45 +6,6 @@
 #include <stdlib.h>
 #include "mhmr_internal.h"
 
-// launchers defined in the other translation units
-int mhmr_launch_attention(const void* qk, const void* vt, void* out, int B, int T, int Tp, int C, int H, int dtype, int* flags, hipStream_t s, int ldo = 0, int o8 = 0);
-int mhmr_launch_layernorm_pitch(const float* in, const float* w, const float* b, void* out16, int ld16, int o8, int rows, int C, float eps, int dtype, hipStream_t s);
-bool mhmr_gemm256_eligible(const GemmArgs& g);
-int mhmr_launch_attention_ex(const void* qk, const void* vt, void* out, int B, int T, int Tp, int C, int H, int dtype, float limit_log2, int variant, int* flags, hipStream_t s);
-int mhmr_attention_flag_count_impl(int B, int Tp, int H);
-int mhmr_launch_im2col(const float* x, void* a, int B, int S, int G, int Kp, int dtype, hipStream_t s);
-int mhmr_launch_init_rows(float* resid, const float* cls_pos0, int B, int T, int Tp, int C, hipStream_t s);
-int mhmr_launch_layernorm(const float* in, const float* w, const float* b, void* out16, int rows, int C, float eps, int dtype, hipStream_t s);
-int mhmr_launch_final_norm(const float* resid, const float* w, const float* b, void* ctx16, int ldctx, float* feat32, int B, int Np, int Tp, int C, float eps, int dtype, hipStream_t s);
-int mhmr_launch_linear_f32(const float* X, int ldx, const int* row_idx, const float* W, int ldw, const float* bias, const float* R, int ldr, float* Y, int ldy, int M, int N, int K, int act, hipStream_t s);
-int mhmr_launch_layernorm_f32(const float* in, const float* w, const float* b, float* out, int rows, int C, float eps, hipStream_t s);
-int mhmr_launch_scores(const void* hid, int ld, const float* w2, const float* b2, float* scores, int rows, int C, int dtype, hipStream_t s);
-int mhmr_launch_detect_count(const float* scores, int B, int G, int nms_kernel, float thr, int* counts, hipStream_t s);
-int mhmr_launch_detect_write(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b, int* det_y, int* det_x, float* det_score, int cap, hipStream_t s);
-int mhmr_launch_person_groups(const int* counts, const int* det_b, int P, int B, int cap, int* base, int* gstart, int ngcap, int* chunks, int nccap, int* info, hipStream_t s);
-int mhmr_launch_camera_embed(const float* Kmat, const float* freq, int B, int G, int patch, float* zK, void* ctx16, int Kc, int C, int dtype, int nbands, hipStream_t s);
-int mhmr_launch_hph_inputs(const float* feat32, const float* zK, const int* det_b, const int* det_y, const int* det_x, const float* cq_x, const float* cq_y, const float* cv_x, const float* cv_y, const float* init_tail, int ntail, float* zc, float* token, int Ktok, void* ctx16, int Kc, int* det_row, int P, int G, int C, int dtype, const int* nvalid, int cam_dim, hipStream_t s);
-int mhmr_launch_hph_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads, hipStream_t s);
-int mhmr_launch_hph_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N, hipStream_t s);
-int mhmr_launch_hph_decode(const float* dec, int ldd, int nb, const float* Kmat, const int* det_b, float fn, int nearness, float* rotmat, float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, hipStream_t s);
-int mhmr_launch_cls_linear(const void* A, long long a_stride, const void* W, int ldw, int B, int N, int K, int a_k, const float* bias,
-                           const float* gamma, void* out, long long o_stride, int n_base, int C, void* vt, int H, int Tp, int vcol, int epi,
-                           int dtype, hipStream_t s);
-int mhmr_launch_cls_linear_fold(const void* A, long long a_stride, const void* W, int ldw, int B, int N, int K, int a_k, const float* bias,
-                                const float* gamma, void* out, long long o_stride, int n_base, int C, void* vt, int H, int Tp, int vcol, int epi,
-                                int dtype, const float* rowstats, long long rs_stride, const float* colsum, const float* fbias, void* x16,
-                                long long x_stride, hipStream_t s, const ClsStats* st = nullptr);
-int mhmr_launch_ln_stats(const float* pstats, const float* resid, float* rowstats, int B, int N, int Tp, int C, float eps, hipStream_t s);
-int mhmr_launch_attention_f32(const float* qkv, void* out, int B, int T, int Tp, int C, int H, int dtype, hipStream_t s);
-int mhmr_launch_im2col_pair(const float* x, void* a, int B, int S, int G, int Kp, int dtype, hipStream_t s);
-int mhmr_launch_layernorm_pair(const float* in, const float* w, const float* b, void* out16, int rows, int C, float eps, int dtype, hipStream_t s);
-int mhmr_launch_gelu_pair(const float* in, void* out, long long M, int N, int dtype, hipStream_t s);
-int mhmr_launch_splitk_resid(const float* part, int nslices, int rows, int C, const float* bias, const float* gamma, float* resid, void* x16,
-                             int ldx, float* rowstats, float eps, int dtype, hipStream_t s);
-bool mhmr_splitk_plan(int M, int N, int K, int* ksplit, int* nslices);
-int mhmr_launch_vt_transpose(const void* v, int ldv, void* vt, int B, int Tp, int H, int dtype, hipStream_t s);
-int mhmr_launch_loc(const float* offset, const int* det_y, const int* det_x, int patch, float* loc, int P, hipStream_t s);
-
 thread_local int g_mhmr_anyorder = 0;        // mhmr_internal.h: the next launches of this host thread go out without the AQL barrier bit
 #ifndef MHMR_ANYORDER_DEFAULT
 #define MHMR_ANYORDER_DEFAULT 1      // +0.1 ... +0.8 % on the headline step in six of six interleaved A/B pairs (profiles/r06_session_a.txt, _c.txt)
@@ -254,8 +215,8 @@ int mhmr_ln_stats(const float* pstats, const float* resid, float* rowstats, int 
 int mhmr_cls_linear16(const void* A, long long a_stride, const void* W, int ldw, int B, int N, int K, int a_k, const float* bias,
                       const float* gamma, void* out, long long o_stride, int n_base, int C, void* vt, int H, int Tp, int vcol, int epi,
                       int dtype, void* stream) {
-    return mhmr_launch_cls_linear(A, a_stride, W, ldw, B, N, K, a_k, bias, gamma, out, o_stride, n_base, C, vt, H, Tp, vcol, epi, dtype,
-                                  (hipStream_t)stream);
+    const ClsArgs a{A, a_stride, W, ldw, B, N, K, a_k, bias, gamma, out, o_stride, n_base, C, vt, H, Tp, vcol};
+    return mhmr_launch_cls_linear(a, epi, dtype, (hipStream_t)stream);
 }
 
 int mhmr_attention16(const void* qk, const void* vt, void* out, int B, int T, int Tp, int C, int H, int dtype, void* stream) {
@@ -335,29 +296,218 @@ static int vit_forward_x3(const mhmr_vit_desc* d, const float* x, float* feat32,
     return mhmr_launch_final_norm(d->resid, d->norm_w, d->norm_b, ctx16, ldctx, feat32, B, d->N, Tp, C, 1e-6f, dt, s);
 }
 
-int mhmr_vit_forward(const mhmr_vit_desc* d, const float* x, float* feat32, void* ctx16, int ldctx, void* stream) {
-    if (!d || !x || !feat32 || !ctx16) return MHMR_ERR_BAD_ARG;
-    if (d->S % 14 || d->G * 14 != d->S || d->N != d->G * d->G || d->T != d->N + 1 || d->Tp % 64 || d->Tp < d->T ||
-        d->C != d->H * 64 || d->Kp % 64 || d->Kp < 588 || (d->C != 384 && d->C != 768 && d->C != 1024))
-        return MHMR_ERR_BAD_SHAPE;
-    hipStream_t s = (hipStream_t)stream;
-    if (d->x3) return vit_forward_x3(d, x, feat32, ctx16, ldctx, s);
-    const int dt = d->dtype, B = d->B, C = d->C, N = d->N, Tp = d->Tp, M = B * Tp;
-    const int Mp = (B * N + 127) / 128 * 128;
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ mhmr_vit_forward: decide, then launch
+// vit_switches (the environment) -> vit_form (everything decided before the block loop) -> per block: vit_block_ops (which weights,
+// which low halves, which launches merge) -> vit_launch (the launches, in stream order).
+namespace {
+
+// The environment switches of the forward: A/B measurements and bisecting; everything is on by default.
+struct VitSwitches {
+    bool rowmap;        // MHMR_ROWMAP=0: no token-row map and no 256x256 all-rows form: one GEMM over all B * Tp rows
+    bool gemm128;       // MHMR_GEMM128 set (gemm.hip forces the 128x128 kernel everywhere): the same
+    bool lnfold;        // MHMR_LNFOLD=0: LayerNorm as launches of its own
+    bool lo8;           // MHMR_LO8=0: the fp8 low-half ranges of a lo8 pack are not used
+    bool anyorder;      // MHMR_ANYORDER=0 / 1 (default MHMR_ANYORDER_DEFAULT)
+    bool qkv_merge;     // MHMR_QKV_MERGE=0: Q | K and V as two launches in a short batch too
+    bool fc1_rowmap;    // MHMR_FC1_ROWMAP=0: fc1 of a short batch over all rows
+    bool cls_stats;     // MHMR_CLS_STATS=0: row statistics as ln_stats launches
+};
+
+inline bool env_not_zero(const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); }
+
+VitSwitches vit_switches() {
+    static const VitSwitches once = [] {
+        VitSwitches w{};
+        w.rowmap = env_not_zero("MHMR_ROWMAP");
+        w.gemm128 = getenv("MHMR_GEMM128") != nullptr;
+        w.lnfold = env_not_zero("MHMR_LNFOLD");
+        w.lo8 = env_not_zero("MHMR_LO8");
+        w.anyorder = getenv("MHMR_ANYORDER") ? atoi(getenv("MHMR_ANYORDER")) != 0 : MHMR_ANYORDER_DEFAULT != 0;
+        w.qkv_merge = env_not_zero("MHMR_QKV_MERGE");
+        w.fc1_rowmap = env_not_zero("MHMR_FC1_ROWMAP");
+        return w;
+    }();
+    VitSwitches w = once;
+    w.cls_stats = env_not_zero("MHMR_CLS_STATS");      // (read per call: tests switch it in-process)
+    return w;
+}
+
+// Any-order launches (mhmr_internal.h) need a stream whose packets the runtime queues as they come: not while the stream is being
+// captured, not inside a profiling window (the hipEvent brackets are ordinary packets)
+bool stream_takes_anyorder(hipStream_t s) {
+    if (g_prof.kind >= 0) return false;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
+}
+
+// The form of one forward: everything that is decided before the block loop.
+struct VitForm {
+    int rc = 0;              // MHMR_ERR_*: this description cannot run
     // Token rows of an image: patches 0..N-1, the class token at row N, zero padding up to Tp (vit_misc.hip).  When the patch rows of
     // an image are whole 256-row tiles and every linear runs on the 256x256 kernel, the five big GEMMs of a block cover the B * N
     // patch rows only (GemmArgs::img_rows: exact tile rounds) and the B class rows go through the skinny kernel (vit_cls.hip);
-    // otherwise one GEMM covers all B * Tp rows.  MHMR_ROWMAP=0 forces the latter (A/B measurements).  Everything is launched on the
-    // caller's stream: the call is re-entrant across streams and capturable.
-    static const bool rowmap_env = !(getenv("MHMR_ROWMAP") && atoi(getenv("MHMR_ROWMAP")) == 0) && !getenv("MHMR_GEMM128");
-    // (Tp a multiple of 256 where N is one too -- the row map's own padding is N + 64 -- is the caller saying "all rows": multi_hmr_amd/vit.py
-    // pads tiny batches that way, whose launches are latency-bound and not worth six class-row launches per block)
-    const bool rowmap = rowmap_env && C % 256 == 0 && N % 256 == 0 && Tp % 256 != 0 && (uint64_t)M * (uint64_t)C * 4u < (1ull << 32);
-    const int Mg = rowmap ? B * N : M, ir = rowmap ? N : 0, is = rowmap ? Tp : 0;
-    const size_t esz = 2;
-    const long long cls_row = (long long)N;                          // the class row inside an image
-    const int vcol = (N & ~12) | ((N & 4) << 1) | ((N & 8) >> 1);    // its (key-permuted) V^T column
+    // otherwise one GEMM covers all B * Tp rows.
+    bool rowmap = false;
+    int Mg = 0, img_rows = 0, img_stride = 0;      // rows of a block GEMM; its token-row map (0, 0: rows are physical)
+    long long cls_row = 0;   // the class row inside an image
+    int vcol = 0;            // its (key-permuted) V^T column
+    // ... or, without the row map (N not a multiple of 256: 1288^2, 518^2), every block linear on the 256x256 kernel over ALL B * Tp rows
+    // (Tp a multiple of 256: vit.padded_tokens): the class and padding rows are rows like any other, with block sums of their own
+    bool allrows256 = false;
+    // (C = 384, ViT-S: the three linears whose output is C wide -- V, proj, fc2 -- run as N = Cp = 512 with the last 128 columns masked,
+    // GemmArgs::n_valid; the caller says with mhmr_vit_desc.cpad that their weights and per-column vectors are zero-padded for it)
+    bool nmask = false;
+    int Cp = 0;
+    // LayerNorm fold (GemmArgs in mhmr_internal.h): needs every block linear on the 256x256 kernel and the two workspaces
+    bool fold = false;
+    // fp8 low-half ranges (mhmr_vit_desc.lo8): the rows of `xn` and `att` are 3C/2 elements wide (the bf8 copy of a row behind its C values)
+    bool lo8 = false;
+    bool lo8_ranges = false; // ... and a block's v_w8 / proj_w8 run as such a range (needs the 256x256 kernel for that launch)
+    int pit = 0;             // row pitch of xn / att in elements
+    int o8 = 0;              // byte offset of the bf8 copy inside such a row
+    // Row statistics inside the class-row launches (vit_cls.hip, round 6): with mhmr_vit_desc.cls_pstats the residual class-row launch of
+    // proj / fc2 also carries the patch rows' statistics (extra workgroups) and leaves block sums of the class rows, from which the class-row
+    // consumers take (mean, rstd) themselves: no ln_stats launch at all under the token-row map.
+    bool cst = false;
+    // Any-order launches (mhmr_internal.h): the V projection and the class-row linears are independent of the big GEMM launched right in
+    // front of them and nothing reads their outputs before the next ordinary launch
+    bool ao = false;
+    // Split-k residual linears (a batch of one: all rows through the 256x256 kernel, 68 / 40 tiles on 256 CUs): the k range is cut so that
+    // tiles x slices fill the chip, and the reduction that follows (vit_misc.hip splitk_resid_kernel) runs the residual epilogue AND leaves
+    // the row statistics, so the ln_stats launch behind such a linear disappears.  Needs the workspace mhmr_vit_desc.splitk.
+    bool splitk = false;
+    // A short batch (all rows, the whole qkv linear at most one round of tiles): ONE launch for Q | K | V + a transpose of the V rows
+    // (gemm256.hip QKV), instead of two launches of half a round each.  Needs mhmr_vit_desc.v16 (and, per block, a V without a low half).
+    bool qkv_merge = false;
+    // One 896^2 image over all rows is 17 row tiles x 16 column tiles = 272 tiles: one round of the chip + 16 tiles that cost a second.
+    // When the PATCH rows alone fit one round (16 x 16 = 256), fc1 -- and only fc1, and only with its LayerNorm folded -- takes the
+    // token-row map and its class rows the skinny kernel; the padding rows of `hid` are then never written (they stay as allocated:
+    // zero) and nobody reads what the padding rows of the residual stream become.
+    bool fc1map = false;
+};
 
+VitForm vit_form(const mhmr_vit_desc* d, const VitSwitches& w, int ncu, bool anyorder_stream) {
+    VitForm f;
+    const int B = d->B, C = d->C, N = d->N, Tp = d->Tp, M = B * Tp;
+    const bool k256 = w.rowmap && !w.gemm128;
+    const bool fits = (uint64_t)M * (uint64_t)C * 4u < (1ull << 32);
+    // (Tp a multiple of 256 where N is one too -- the row map's own padding is N + 64 -- is the caller saying "all rows": multi_hmr_amd/vit.py
+    // (row_map, padded_tokens) pads tiny batches that way, whose launches are latency-bound and not worth six class-row launches per block)
+    f.rowmap = k256 && C % 256 == 0 && N % 256 == 0 && Tp % 256 != 0 && fits;
+    f.Mg = f.rowmap ? B * N : M;
+    f.img_rows = f.rowmap ? N : 0;
+    f.img_stride = f.rowmap ? Tp : 0;
+    f.cls_row = (long long)N;
+    f.vcol = (N & ~12) | ((N & 4) << 1) | ((N & 8) >> 1);
+    f.Cp = (C + 255) / 256 * 256;
+    f.allrows256 = !f.rowmap && k256 && (C % 256 == 0 || (C % 128 == 0 && d->cpad == f.Cp)) && M % 256 == 0 && fits;
+    f.nmask = f.allrows256 && C % 256 != 0;
+    f.fold = (f.rowmap || f.allrows256) && w.lnfold && d->pstats && d->rowstats;
+    f.lo8 = d->lo8 != 0 && C % 256 == 0;
+    if (d->lo8 && !f.lo8) { f.rc = MHMR_ERR_BAD_SHAPE; return f; }
+    f.lo8_ranges = f.lo8 && w.lo8 && (f.rowmap || f.allrows256);
+    f.pit = f.lo8 ? C + C / 2 : C;
+    f.o8 = 2 * C;
+    f.cst = w.cls_stats && f.rowmap && f.fold && !f.lo8 && d->cls_pstats && C % 128 == 0 && C <= 1024;
+    f.ao = w.anyorder && anyorder_stream;
+    f.splitk = f.allrows256 && f.fold && d->splitk;
+    f.qkv_merge = w.qkv_merge && f.allrows256 && !f.nmask && d->v16 && (M / 256) * (3 * C / 256) <= ncu;
+    f.fc1map = w.fc1_rowmap && f.allrows256 && !f.nmask && N % 256 == 0 && (M / 256) * (4 * C / 256) > ncu && (B * N / 256) * (4 * C / 256) <= ncu;
+    return f;
+}
+
+// A weight whose rows may carry the low halves behind the high ones ([W_hi | W_lo] along k, one accumulator chain): k = the whole k
+// extent (and the row pitch), a_k = where the activation's k index wraps (0: no low half)
+struct WeightK { const void* w; int k, a_k; };
+
+// The operands of one block.
+struct VitBlockOps {
+    int rc = 0;
+    bool f1 = false, f2 = false;         // norm1 folded into qkv, norm2 into fc1
+    bool vlo8 = false, plo8 = false;     // the V / output projection runs its low half as an fp8 range (v_w8 / proj_w8)
+    bool next_f1 = false;                // the next block folds its norm1: this block's fc2 leaves the statistics for it
+    bool next_vlo8 = false;              // the next block's V has an fp8 range: this block's fc2 leaves the bf8 copy of its rows
+    bool qkv_merged = false, fc1map = false;
+    WeightK v{}, proj{};                 // big GEMM: fp8 range, or a second 16-bit range (v_w2 / proj_w2), or the plain weight
+    WeightK v_cls{}, proj_cls{};         // the class-row kernel keeps the 16-bit low halves
+};
+
+VitBlockOps vit_block_ops(const mhmr_vit_desc* d, const VitForm& f, int l) {
+    VitBlockOps o;
+    const mhmr_vit_block& k = d->blocks[l];
+    const int C = d->C;
+    o.rc = MHMR_ERR_BAD_ARG;
+    if (!f.fold && k.flags) return o;               // folded weights cannot run through the plain LayerNorm path
+    // block 0's norm1 follows the patch embedding, whose epilogue leaves no row statistics: it cannot be folded (include/mhmr.h);
+    // a folded linear needs its column sums
+    if (l == 0 && (k.flags & 1)) return o;
+    if (((k.flags & 1) && !k.qkv_colsum) || ((k.flags & 2) && !k.fc1_colsum)) return o;
+    o.rc = 0;
+    const bool last = l + 1 == d->L;
+    o.f1 = f.fold && (k.flags & 1);
+    o.f2 = f.fold && (k.flags & 2);
+    o.next_f1 = !last && f.fold && (d->blocks[l + 1].flags & 1);
+    o.vlo8 = f.lo8_ranges && k.v_w8;
+    o.plo8 = f.lo8_ranges && k.proj_w8;
+    o.next_vlo8 = !last && f.lo8_ranges && d->blocks[l + 1].v_w8;
+    const void* v_hi = (const char*)k.qkv_w + (size_t)2 * C * C * 2;      // the V rows of the 16-bit qkv weight
+    o.v_cls = k.v_w2 ? WeightK{k.v_w2, 2 * C, C} : WeightK{v_hi, C, 0};
+    o.proj_cls = k.proj_w2 ? WeightK{k.proj_w2, 2 * C, C} : WeightK{k.proj_w, C, 0};
+    o.v = o.vlo8 ? WeightK{k.v_w8, f.pit, C} : o.v_cls;
+    o.proj = o.plo8 ? WeightK{k.proj_w8, f.pit, C} : o.proj_cls;
+    o.qkv_merged = f.qkv_merge && !k.v_w2 && !o.vlo8;
+    o.fc1map = f.fc1map && o.f2;
+    return o;
+}
+
+// A [B * Tp, ld] activation buffer of esz-byte elements, as the class-row kernel sees it: the class row of image b
+struct TokenBuf { void* base; int ld, esz; };
+// where the (mean, rstd) / block sums of a class-row launch come from and go to
+enum ClsRowStats {
+    CLS_ROWS_PLAIN,          // none: bias epilogue
+    CLS_ROWS_CONSUME,        // folded LayerNorm: (mean, rstd) of the class rows from rowstats, or (cst) from the class rows' own block sums
+    CLS_ROWS_PRODUCE,        // residual epilogue: leaves (cst) the class rows' block sums
+    CLS_ROWS_PRODUCE_PATCH,  // ... and extra workgroups turn the block sums of the big GEMM IN FRONT of it into the patch rows' (mean, rstd)
+};
+
+// "The class row of every image through one linear": out = epi(in . w^T) over the B class rows of two token buffers.
+// bias: the linear's bias (with CLS_ROWS_CONSUME its folded form, beside colsum); gamma: CLS_RESID
+ClsArgs cls_rows_linear(const mhmr_vit_desc* d, const VitForm& f, int epi, TokenBuf in, WeightK w, int n, const float* bias,
+                        const float* colsum, const float* gamma, TokenBuf out, ClsRowStats st) {
+    const int C = d->C, Tp = d->Tp;
+    auto cls_row = [&](TokenBuf t) { return (char*)t.base + (size_t)f.cls_row * t.ld * t.esz; };
+    ClsArgs a;
+    a.A = cls_row(in); a.a_stride = (long long)Tp * in.ld;
+    a.W = w.w; a.ldw = w.k; a.B = d->B; a.N = n; a.K = w.k; a.a_k = w.a_k;
+    a.bias = bias; a.gamma = gamma;
+    a.out = cls_row(out); a.o_stride = (long long)Tp * out.ld;
+    a.C = C; a.H = d->H; a.Tp = Tp;
+    if (epi == CLS_QKV) { a.vt = d->vt; a.vcol = f.vcol; }
+    if (epi == CLS_RESID && f.fold) { a.x16 = cls_row({d->xn, f.pit, 2}); a.x_stride = (long long)Tp * f.pit; }
+    if (st == CLS_ROWS_CONSUME) {
+        a.bias = nullptr; a.fbias = bias; a.colsum = colsum;
+        if (!f.cst) { a.rowstats = d->rowstats + (size_t)f.cls_row * 2; a.rs_stride = 2LL * Tp; }     // (mean, rstd) of image b's class row: + b * 2 Tp
+    }
+    if (f.cst && st != CLS_ROWS_PLAIN) { a.cls_pstats = d->cls_pstats; a.cls_nblk = C / 16; a.cls_C = C; }
+    if (st == CLS_ROWS_PRODUCE_PATCH) {
+        a.st_pstats = d->pstats; a.st_rowstats = d->rowstats;
+        a.st_B = d->B; a.st_N = d->N; a.st_Tp = Tp; a.st_C = C;
+    }
+    return a;
+}
+
+// ANY_ORDER_IF(on, launch): `launch` goes out without the AQL barrier bit when `on` (mhmr_internal.h).  The ONLY way a launch of the
+// forward gets that flag, so this name at a call is the complete list of the launches that may run beside their predecessor: each must
+// be independent of the launch in front of it, and nothing may read its output before the next ordinary launch.
+#define ANY_ORDER_IF(on, launch) ([&]() -> int { AnyOrder scope(on); return (launch); }())
+
+int vit_launch(const mhmr_vit_desc* d, const VitForm& f, const float* x, float* feat32, void* ctx16, int ldctx, hipStream_t s) {
+    const int dt = d->dtype, B = d->B, C = d->C, N = d->N, Tp = d->Tp, M = B * Tp, Mg = f.Mg, pit = f.pit;
+    const int Mp = (B * N + 127) / 128 * 128;
+    const TokenBuf xn{d->xn, pit, 2}, qk{d->qk, 2 * C, 2}, att{d->att, pit, 2}, hid{d->hid, 4 * C, 2}, resid{d->resid, C, 4};
+    // Everything is launched on the caller's stream: the call is re-entrant across streams and capturable.
     // tokens: patch embedding (im2col + GEMM with bias / pos-embed epilogue), class + padding rows
     TRY(mhmr_launch_im2col(x, d->a_patch, B, d->S, d->G, d->Kp, dt, s));
     TRY(mhmr_launch_init_rows(d->resid, d->cls_pos0, B, d->T, Tp, C, s));
@@ -366,63 +516,15 @@ int mhmr_vit_forward(const mhmr_vit_desc* d, const float* x, float* feat32, void
                    B * d->N, EPI_PATCH};
         TRY(mhmr_launch_gemm(g, dt, s));
     }
-    auto rows = [&](GemmArgs& g) { g.img_rows = ir; g.img_stride = is; };
-    // LayerNorm fold (GemmArgs in mhmr_internal.h): needs the token-row map (every block linear on the 256x256 kernel) and the two workspaces
-    static const bool fold_env = !(getenv("MHMR_LNFOLD") && atoi(getenv("MHMR_LNFOLD")) == 0);
-    // ... or, without the row map (N not a multiple of 256: 1288^2, 518^2), every block linear on the 256x256 kernel over ALL B * Tp rows
-    // (Tp a multiple of 256: vit.padded_tokens): the class and padding rows are rows like any other, with block sums of their own
-    // (C = 384, ViT-S: the three linears whose output is C wide -- V, proj, fc2 -- run as N = Cp = 512 with the last 128 columns masked,
-    // GemmArgs::n_valid; the caller says with mhmr_vit_desc.cpad that their weights and per-column vectors are zero-padded for it)
-    const int Cp = (C + 255) / 256 * 256;
-    const bool allrows256 = !rowmap && rowmap_env && (C % 256 == 0 || (C % 128 == 0 && d->cpad == Cp)) && M % 256 == 0 &&
-                            (uint64_t)M * (uint64_t)C * 4u < (1ull << 32);
-    const bool nmask = allrows256 && C % 256 != 0;
-    auto masked = [&](GemmArgs& g) { if (nmask) { g.N = Cp; g.n_valid = C; } };
-    const bool fold = (rowmap || allrows256) && fold_env && d->pstats && d->rowstats;
-    auto ln_stats = [&]() { return rowmap ? mhmr_launch_ln_stats(d->pstats, d->resid, d->rowstats, B, N, Tp, C, 1e-6f, s)
-                                          : mhmr_launch_ln_stats(d->pstats, d->resid, d->rowstats, 1, M, M, C, 1e-6f, s); };
-    const long long rowC = (long long)Tp * C;
-    const float* cls_stats = fold ? d->rowstats + (size_t)cls_row * 2 : nullptr;      // (mean, rstd) of image b's class row: + b * 2 Tp
-    // fp8 low-half ranges (mhmr_vit_desc.lo8): the rows of `xn` and `att` are 3C/2 elements wide (the bf8 copy of a row behind its C values)
-    static const bool lo8_env = !(getenv("MHMR_LO8") && atoi(getenv("MHMR_LO8")) == 0);
-    const bool lo8 = d->lo8 != 0 && C % 256 == 0;
-    if (d->lo8 && !lo8) return MHMR_ERR_BAD_SHAPE;
-    const int pit = lo8 ? C + C / 2 : C;                        // row pitch of xn / att in elements
-    const long long rowP = (long long)Tp * pit;
-    const int o8 = 2 * C;                                       // byte offset of the bf8 copy inside such a row
-    // does this block's V / output projection run its low half as an fp8 range?  (needs the 256x256 kernel for that launch; MHMR_LO8=0: A/B)
-    auto v8 = [&](const mhmr_vit_block& k) { return lo8 && lo8_env && k.v_w8 && (rowmap || allrows256); };
-    auto p8 = [&](const mhmr_vit_block& k) { return lo8 && lo8_env && k.proj_w8 && (rowmap || allrows256); };
-    // Split-k residual linears (a batch of one: all rows through the 256x256 kernel, 68 / 40 tiles on 256 CUs): the k range is cut so that
-    // tiles x slices fill the chip, and the reduction that follows (vit_misc.hip splitk_resid_kernel) runs the residual epilogue AND leaves
-    // the row statistics, so the ln_stats launch behind such a linear disappears.  Needs the workspace mhmr_vit_desc.splitk.
-    // Any-order launches (mhmr_internal.h): the V projection and the class-row linears are independent of the big GEMM launched right in
-    // front of them and nothing reads their outputs before the next ordinary launch; not while the stream is being captured, not inside
-    // a profiling window (the hipEvent brackets are ordinary packets)
-    static const bool ao_env = getenv("MHMR_ANYORDER") ? atoi(getenv("MHMR_ANYORDER")) != 0 : MHMR_ANYORDER_DEFAULT != 0;
-    bool ao = ao_env && g_prof.kind < 0;
-    if (ao) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) ao = false;
-    }
-    // Row statistics inside the class-row launches (vit_cls.hip, round 6): with mhmr_vit_desc.cls_pstats the residual class-row launch of
-    // proj / fc2 also carries the patch rows' statistics (extra workgroups) and leaves block sums of the class rows, from which the class-row
-    // consumers take (mean, rstd) themselves: no ln_stats launch at all under the token-row map.  MHMR_CLS_STATS=0: the separate launches.
-    const bool cls_stats_env = !(getenv("MHMR_CLS_STATS") && atoi(getenv("MHMR_CLS_STATS")) == 0);     // (read per call: tests switch it in-process)
-    const bool cst = cls_stats_env && rowmap && fold && !lo8 && d->cls_pstats && C % 128 == 0 && C <= 1024;
-    ClsStats cs_consume, cs_produce, cs_produce_stats;
-    if (cst) {
-        cs_consume.cls_pstats = d->cls_pstats; cs_consume.cls_nblk = C / 16; cs_consume.cls_C = C;
-        cs_produce = cs_consume;
-        cs_produce_stats = cs_consume;
-        cs_produce_stats.st_pstats = d->pstats; cs_produce_stats.st_rowstats = d->rowstats;
-        cs_produce_stats.st_B = B; cs_produce_stats.st_N = N; cs_produce_stats.st_Tp = Tp; cs_produce_stats.st_C = C;
-    }
+    auto rows = [&](GemmArgs& g) { g.img_rows = f.img_rows; g.img_stride = f.img_stride; };
+    auto masked = [&](GemmArgs& g) { if (f.nmask) { g.N = f.Cp; g.n_valid = C; } };
+    auto ln_stats = [&]() { return f.rowmap ? mhmr_launch_ln_stats(d->pstats, d->resid, d->rowstats, B, N, Tp, C, 1e-6f, s)
+                                            : mhmr_launch_ln_stats(d->pstats, d->resid, d->rowstats, 1, M, M, C, 1e-6f, s); };
     bool stats_fresh = false;            // rowstats already hold the statistics of the current residual rows
     auto resid_linear = [&](GemmArgs& g) -> int {
         int ks = 0, S = 0;
         stats_fresh = false;
-        if (allrows256 && fold && d->splitk && !g.lo8 && g.n_valid == 0 && g.x16 && g.ldx16 == 0 && mhmr_splitk_plan(g.M, g.N, g.K, &ks, &S) &&
+        if (f.splitk && !g.lo8 && g.n_valid == 0 && g.x16 && g.ldx16 == 0 && mhmr_splitk_plan(g.M, g.N, g.K, &ks, &S) &&
             (long long)S * g.M * g.N * 4 <= d->splitk_bytes) {
             GemmArgs gs{g.A, g.lda, g.W, g.ldw, g.M, g.N, g.K, nullptr, nullptr, d->splitk, g.N, nullptr, 0, Tp, d->H, g.M, EPI_F32};
             gs.a_k = g.a_k;
@@ -435,135 +537,121 @@ int mhmr_vit_forward(const mhmr_vit_desc* d, const float* x, float* feat32, void
         }
         return mhmr_launch_gemm(g, dt, s);
     };
+    // the residual linears under the fold also leave the 16-bit copy of their rows (the next linear's operand) and its block sums
+    auto produces = [&](GemmArgs& g) { if (f.fold) { g.x16 = d->xn; g.pstats = d->pstats; g.ldx16 = f.lo8 ? pit : 0; } };
     for (int l = 0; l < d->L; ++l) {
         const mhmr_vit_block& k = d->blocks[l];
-        if (!fold && k.flags) return MHMR_ERR_BAD_ARG;               // folded weights cannot run through the plain LayerNorm path
-        // block 0's norm1 follows the patch embedding, whose epilogue leaves no row statistics: it cannot be folded (include/mhmr.h);
-        // a folded linear needs its column sums
-        if (l == 0 && (k.flags & 1)) return MHMR_ERR_BAD_ARG;
-        if (((k.flags & 1) && !k.qkv_colsum) || ((k.flags & 2) && !k.fc1_colsum)) return MHMR_ERR_BAD_ARG;
-        const bool f1 = fold && (k.flags & 1), f2 = fold && (k.flags & 2);
-        // the V and output projections may carry the low halves of their weights ([W_hi | W_lo] along k, one accumulator chain): as an
-        // fp8 range of 128-deep k tiles (v_w8 / proj_w8) or as a second 16-bit range (v_w2 / proj_w2)
-        const bool vlo8 = v8(k), plo8 = p8(k);
-        const void* v_w = vlo8 ? k.v_w8 : k.v_w2 ? k.v_w2 : (const void*)((const char*)k.qkv_w + (size_t)2 * C * C * esz);
-        const int v_k = vlo8 ? pit : k.v_w2 ? 2 * C : C, v_ak = (vlo8 || k.v_w2) ? C : 0;
-        const void* p_w = plo8 ? k.proj_w8 : k.proj_w2 ? k.proj_w2 : k.proj_w;
-        const int p_k = plo8 ? pit : k.proj_w2 ? 2 * C : C, p_ak = (plo8 || k.proj_w2) ? C : 0;
-        // the class-row kernel keeps the 16-bit low halves
-        const void* v_wc = k.v_w2 ? k.v_w2 : (const void*)((const char*)k.qkv_w + (size_t)2 * C * C * esz);
-        const int v_kc = k.v_w2 ? 2 * C : C, v_akc = k.v_w2 ? C : 0;
-        const void* p_wc = k.proj_w2 ? k.proj_w2 : k.proj_w;
-        const int p_kc = k.proj_w2 ? 2 * C : C, p_akc = k.proj_w2 ? C : 0;
-        // x = x + ls1 * proj(MHSA(norm1(x)))
-        if (f1) { if (!stats_fresh) TRY(ln_stats()); }
-        else TRY(mhmr_launch_layernorm_pitch(d->resid, k.ln1_w, k.ln1_b, d->xn, pit, vlo8 ? o8 : 0, M, C, 1e-6f, dt, s));
+        const VitBlockOps b = vit_block_ops(d, f, l);
+        if (b.rc) return b.rc;
+
+        // ---- x = x + ls1 * proj(MHSA(norm1(x)))
+        if (b.f1) { if (!stats_fresh) TRY(ln_stats()); }
+        else TRY(mhmr_launch_layernorm_pitch(d->resid, k.ln1_w, k.ln1_b, d->xn, pit, b.vlo8 ? f.o8 : 0, M, C, 1e-6f, dt, s));
         {
             GemmArgs g{d->xn, pit, k.qkv_w, C, Mg, 2 * C, C, k.qkv_b, nullptr, d->qk, 2 * C, nullptr, 0, Tp, d->H, Mg, EPI_OP16_QK};
-            GemmArgs gv{d->xn, pit, v_w, v_k, Mg, C, v_k, k.qkv_b + 2 * C, nullptr, d->vt, 0, nullptr, 0, Tp, d->H, Mg, EPI_VT};
-            gv.a_k = v_ak;
-            if (vlo8) { gv.lo8 = 1; gv.w8_scale = k.v_w8_scale; }
+            GemmArgs gv{d->xn, pit, b.v.w, b.v.k, Mg, C, b.v.k, k.qkv_b + 2 * C, nullptr, d->vt, 0, nullptr, 0, Tp, d->H, Mg, EPI_VT};
+            gv.a_k = b.v.a_k;
+            if (b.vlo8) { gv.lo8 = 1; gv.w8_scale = k.v_w8_scale; }
             rows(g); rows(gv);
             masked(gv);
-            if (f1) {
+            if (b.f1) {
                 g.bias = nullptr; g.rowstats = d->rowstats; g.colsum = k.qkv_colsum; g.fbias = k.qkv_b;
                 gv.bias = nullptr; gv.rowstats = d->rowstats; gv.colsum = k.qkv_colsum + 2 * C; gv.fbias = k.qkv_b + 2 * C;
             }
-            // A short batch (all rows, the whole qkv linear at most one round of tiles): ONE launch for Q | K | V + a transpose of the V rows
-            // (gemm256.hip QKV), instead of two launches of half a round each.  Needs mhmr_vit_desc.v16 and a V without a low half.
-            static const bool qkv_env = !(getenv("MHMR_QKV_MERGE") && atoi(getenv("MHMR_QKV_MERGE")) == 0);
-            if (qkv_env && allrows256 && !nmask && d->v16 && !k.v_w2 && !vlo8 && (M / 256) * (3 * C / 256) <= mhmr_cu_count()) {
+            if (b.qkv_merged) {
                 g.N = 3 * C;
                 g.out2 = d->v16; g.ldo2 = C; g.split_col = 2 * C; g.qcols = C;
                 TRY(mhmr_launch_gemm(g, dt, s));
                 TRY(mhmr_launch_vt_transpose(d->v16, C, d->vt, B, Tp, d->H, dt, s));
             } else {
-            TRY(mhmr_launch_gemm(g, dt, s));
-            AnyOrder ao_scope(ao);           // V and the class rows of Q | K | V: beside the Q | K projection
-            TRY(mhmr_launch_gemm(gv, dt, s));
-            if (rowmap) {
-                const char* xr = (const char*)d->xn + (size_t)cls_row * pit * esz;
-                char* qr = (char*)d->qk + (size_t)cls_row * 2 * C * esz;
-                const float* st = (f1 && !cst) ? cls_stats : nullptr;
-                const ClsStats* cs = (f1 && cst) ? &cs_consume : nullptr;
-                // (Q | K and V separately when V carries a low half: different k extents)
-                const int nqk = k.v_w2 ? 2 * C : 3 * C;
-                TRY(mhmr_launch_cls_linear_fold(xr, rowP, k.qkv_w, C, B, nqk, C, 0, f1 ? nullptr : k.qkv_b, nullptr, qr, 2 * rowC, 0, C, d->vt, d->H,
-                                                Tp, vcol, 0, dt, st, 2LL * Tp, k.qkv_colsum, k.qkv_b, nullptr, 0, s, cs));
-                if (k.v_w2)
-                    TRY(mhmr_launch_cls_linear_fold(xr, rowP, v_wc, v_kc, B, C, v_kc, v_akc, f1 ? nullptr : k.qkv_b + 2 * C, nullptr, qr, 2 * rowC, 2 * C, C,
-                                                    d->vt, d->H, Tp, vcol, 0, dt, st, 2LL * Tp, f1 ? k.qkv_colsum + 2 * C : nullptr,
-                                                    k.qkv_b + 2 * C, nullptr, 0, s, cs));
-            }
+                // V and the class rows of Q | K | V: beside the Q | K projection
+                TRY(mhmr_launch_gemm(g, dt, s));
+                TRY(ANY_ORDER_IF(f.ao, mhmr_launch_gemm(gv, dt, s)));
+                if (f.rowmap) {
+                    const ClsRowStats st = b.f1 ? CLS_ROWS_CONSUME : CLS_ROWS_PLAIN;
+                    // (Q | K and V separately when V carries a low half: different k extents)
+                    const int nqk = k.v_w2 ? 2 * C : 3 * C;
+                    const ClsArgs c = cls_rows_linear(d, f, CLS_QKV, xn, {k.qkv_w, C, 0}, nqk, k.qkv_b, k.qkv_colsum, nullptr, qk, st);
+                    TRY(ANY_ORDER_IF(f.ao, mhmr_launch_cls_linear(c, CLS_QKV, dt, s)));
+                    if (k.v_w2) {
+                        ClsArgs cv = cls_rows_linear(d, f, CLS_QKV, xn, b.v_cls, C, k.qkv_b + 2 * C, b.f1 ? k.qkv_colsum + 2 * C : nullptr, nullptr,
+                                                     qk, st);
+                        cv.n_base = 2 * C;
+                        TRY(ANY_ORDER_IF(f.ao, mhmr_launch_cls_linear(cv, CLS_QKV, dt, s)));
+                    }
+                }
             }
         }
-        TRY(mhmr_launch_attention(d->qk, d->vt, d->att, B, d->T, Tp, C, d->H, dt, d->attn_flags, s, pit, plo8 ? o8 : 0));
+        TRY(mhmr_launch_attention(d->qk, d->vt, d->att, B, d->T, Tp, C, d->H, dt, d->attn_flags, s, pit, b.plo8 ? f.o8 : 0));
         {
-            GemmArgs g{d->att, pit, p_w, p_k, Mg, C, p_k, k.proj_b, k.ls1, d->resid, C, nullptr, 0, Tp, d->H, Mg, EPI_RESID};
-            g.a_k = p_ak;
-            if (plo8) { g.lo8 = 1; g.w8_scale = k.proj_w8_scale; }
+            GemmArgs g{d->att, pit, b.proj.w, b.proj.k, Mg, C, b.proj.k, k.proj_b, k.ls1, d->resid, C, nullptr, 0, Tp, d->H, Mg, EPI_RESID};
+            g.a_k = b.proj.a_k;
+            if (b.plo8) { g.lo8 = 1; g.w8_scale = k.proj_w8_scale; }
             rows(g);
-            if (fold) { g.x16 = d->xn; g.pstats = d->pstats; g.ldx16 = lo8 ? pit : 0; }
+            produces(g);
             masked(g);
             TRY(resid_linear(g));
-            if (rowmap) {
+            if (f.rowmap) {
                 // (with cst: + the patch rows' statistics for norm2, when the next linear consumes them.  THAT launch reads the block sums
                 // the GEMM in front of it has just written: an ordinary launch, not an any-order one -- session D of round 6 shipped it
                 // any-order for one GPU session and the full-size goldens caught the race: scores 2.5e-3, results differing run to run)
-                const ClsStats* cs = !cst ? nullptr : f2 ? &cs_produce_stats : &cs_produce;
-                AnyOrder ao_scope(ao && !(cst && f2));
-                TRY(mhmr_launch_cls_linear_fold((const char*)d->att + (size_t)cls_row * pit * esz, rowP, p_wc, p_kc, B, C, p_kc, p_akc, k.proj_b, k.ls1,
-                                                d->resid + (size_t)cls_row * C, rowC, 0, C, nullptr, d->H, Tp, 0, 1, dt, nullptr, 0, nullptr, nullptr,
-                                                fold ? (char*)d->xn + (size_t)cls_row * pit * esz : nullptr, rowP, s, cs));
-                if (cst && f2) stats_fresh = true;
+                const bool patch_stats = f.cst && b.f2;
+                const ClsArgs c = cls_rows_linear(d, f, CLS_RESID, att, b.proj_cls, C, k.proj_b, nullptr, k.ls1, resid,
+                                                  patch_stats ? CLS_ROWS_PRODUCE_PATCH : CLS_ROWS_PRODUCE);
+                TRY(ANY_ORDER_IF(f.ao && !patch_stats, mhmr_launch_cls_linear(c, CLS_RESID, dt, s)));
+                if (patch_stats) stats_fresh = true;
             }
         }
-        // x = x + ls2 * fc2(gelu(fc1(norm2(x))))
-        if (f2) { if (!stats_fresh) TRY(ln_stats()); }
+
+        // ---- x = x + ls2 * fc2(gelu(fc1(norm2(x))))
+        if (b.f2) { if (!stats_fresh) TRY(ln_stats()); }
         else TRY(mhmr_launch_layernorm_pitch(d->resid, k.ln2_w, k.ln2_b, d->xn, pit, 0, M, C, 1e-6f, dt, s));
         {
             GemmArgs g{d->xn, pit, k.fc1_w, C, Mg, 4 * C, C, k.fc1_b, nullptr, d->hid, 4 * C, nullptr, 0, Tp, d->H, Mg, EPI_OP16_GELU};
             rows(g);
-            // One 896^2 image over all rows is 17 row tiles x 16 column tiles = 272 tiles: one round of the chip + 16 tiles that cost a second.
-            // When the PATCH rows alone fit one round (16 x 16 = 256), fc1 -- and only fc1 -- takes the token-row map and its class rows the
-            // skinny kernel; the padding rows of `hid` are then never written (they stay as allocated: zero) and nobody reads what the
-            // padding rows of the residual stream become.
-            static const bool fc1map_env = !(getenv("MHMR_FC1_ROWMAP") && atoi(getenv("MHMR_FC1_ROWMAP")) == 0);
-            const int ncu = mhmr_cu_count();
-            const bool fc1map = fc1map_env && allrows256 && !nmask && f2 && N % 256 == 0 && (M / 256) * (4 * C / 256) > ncu &&
-                                (B * N / 256) * (4 * C / 256) <= ncu;
-            if (fc1map) { g.M = B * N; g.Mvalid = B * N; g.img_rows = N; g.img_stride = Tp; }
-            if (f2) { g.bias = nullptr; g.rowstats = d->rowstats; g.colsum = k.fc1_colsum; g.fbias = k.fc1_b; }
+            if (b.fc1map) { g.M = B * N; g.Mvalid = B * N; g.img_rows = N; g.img_stride = Tp; }
+            if (b.f2) { g.bias = nullptr; g.rowstats = d->rowstats; g.colsum = k.fc1_colsum; g.fbias = k.fc1_b; }
             TRY(mhmr_launch_gemm(g, dt, s));
-            if (rowmap || fc1map) {
-                AnyOrder ao_scope(ao);
-                TRY(mhmr_launch_cls_linear_fold((const char*)d->xn + (size_t)cls_row * pit * esz, rowP, k.fc1_w, C, B, 4 * C, C, 0, f2 ? nullptr : k.fc1_b,
-                                                nullptr, (char*)d->hid + (size_t)cls_row * 4 * C * esz, 4 * rowC, 0, C, nullptr, d->H, Tp, 0, 2, dt,
-                                                (f2 && !cst) ? cls_stats : nullptr, 2LL * Tp, k.fc1_colsum, k.fc1_b, nullptr, 0, s,
-                                                (f2 && cst) ? &cs_consume : nullptr));
+            if (f.rowmap || b.fc1map) {
+                const ClsArgs c = cls_rows_linear(d, f, CLS_GELU, xn, {k.fc1_w, C, 0}, 4 * C, k.fc1_b, k.fc1_colsum, nullptr, hid,
+                                                  b.f2 ? CLS_ROWS_CONSUME : CLS_ROWS_PLAIN);
+                TRY(ANY_ORDER_IF(f.ao, mhmr_launch_cls_linear(c, CLS_GELU, dt, s)));
             }
             GemmArgs g2{d->hid, 4 * C, k.fc2_w, 4 * C, Mg, C, 4 * C, k.fc2_b, k.ls2, d->resid, C, nullptr, 0, Tp, d->H, Mg, EPI_RESID};
             rows(g2);
-            if (fold) {
-                // the rows this epilogue leaves are the NEXT block's qkv operand: with their bf8 copy if that block's V has an fp8 range
-                g2.x16 = d->xn; g2.pstats = d->pstats; g2.ldx16 = lo8 ? pit : 0;
-                g2.x8_off = (l + 1 < d->L && v8(d->blocks[l + 1])) ? o8 : 0;
-            }
+            produces(g2);
+            // the rows this epilogue leaves are the NEXT block's qkv operand: with their bf8 copy if that block's V has an fp8 range
+            if (f.fold) g2.x8_off = b.next_vlo8 ? f.o8 : 0;
             masked(g2);
             TRY(resid_linear(g2));
-            if (rowmap) {
+            if (f.rowmap) {
                 // (with cst: + the patch rows' statistics for the NEXT block's norm1, when that block folds it: an ordinary launch then)
-                const bool next_f1 = l + 1 < d->L && fold && (d->blocks[l + 1].flags & 1);
-                const ClsStats* cs = !cst ? nullptr : next_f1 ? &cs_produce_stats : &cs_produce;
-                AnyOrder ao_scope2(ao && !(cst && next_f1));
-                TRY(mhmr_launch_cls_linear_fold((const char*)d->hid + (size_t)cls_row * 4 * C * esz, 4 * rowC, k.fc2_w, 4 * C, B, C, 4 * C, 0, k.fc2_b,
-                                                k.ls2, d->resid + (size_t)cls_row * C, rowC, 0, C, nullptr, d->H, Tp, 0, 1, dt, nullptr, 0, nullptr,
-                                                nullptr, fold ? (char*)d->xn + (size_t)cls_row * pit * esz : nullptr, rowP, s, cs));
-                if (cst && next_f1) stats_fresh = true;
+                const bool patch_stats = f.cst && b.next_f1;
+                const ClsArgs c = cls_rows_linear(d, f, CLS_RESID, hid, {k.fc2_w, 4 * C, 0}, C, k.fc2_b, nullptr, k.ls2, resid,
+                                                  patch_stats ? CLS_ROWS_PRODUCE_PATCH : CLS_ROWS_PRODUCE);
+                TRY(ANY_ORDER_IF(f.ao && !patch_stats, mhmr_launch_cls_linear(c, CLS_RESID, dt, s)));
+                if (patch_stats) stats_fresh = true;
             }
         }
     }
     return mhmr_launch_final_norm(d->resid, d->norm_w, d->norm_b, ctx16, ldctx, feat32, B, d->N, Tp, C, 1e-6f, dt, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mhmr_vit_forward(const mhmr_vit_desc* d, const float* x, float* feat32, void* ctx16, int ldctx, void* stream) {
+    if (!d || !x || !feat32 || !ctx16) return MHMR_ERR_BAD_ARG;
+    if (d->S % 14 || d->G * 14 != d->S || d->N != d->G * d->G || d->T != d->N + 1 || d->Tp % 64 || d->Tp < d->T ||
+        d->C != d->H * 64 || d->Kp % 64 || d->Kp < 588 || (d->C != 384 && d->C != 768 && d->C != 1024))
+        return MHMR_ERR_BAD_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    if (d->x3) return vit_forward_x3(d, x, feat32, ctx16, ldctx, s);
+    const VitSwitches w = vit_switches();
+    const VitForm f = vit_form(d, w, mhmr_cu_count(), w.anyorder && stream_takes_anyorder(s));
+    if (f.rc) return f.rc;
+    return vit_launch(d, f, x, feat32, ctx16, ldctx, s);
 }
 
 int mhmr_detect_scores(const void* hid16, int ld, const float* w2, const float* b2, float* scores, int rows, int C, int dtype,
@@ -657,10 +745,9 @@ int mhmr_hph_forward(const mhmr_hph_desc* d, const float* feat32, const float* z
     if (!d || P < 0) return MHMR_ERR_BAD_ARG;
     if (P == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const int C = d->C, dim = d->dim, inner = d->heads * 32, mlp = d->mlp;
-    if (d->Ktok % 16 || d->Kc % 64 || C % 16 || dim % 64 || mlp % 16 || (2 * inner) % 128) return MHMR_ERR_BAD_SHAPE;
+    const int C = d->C, dim = d->dim;
+    if (d->Ktok % 16 || d->Kc % 64 || C % 16 || dim % 64 || d->mlp % 16 || (2 * d->heads * 32) % 128) return MHMR_ERR_BAD_SHAPE;
     if (d->nb < 0 || d->nb > 64) return MHMR_ERR_BAD_SHAPE;          // the decode writes betas with one thread each of 64
-    const int Mctx = (B * d->N + 127) / 128 * 128;
 
     // queries, mlp_offset input, context rows of the detected cells  (model.py:255-265, 500-517, 541-552)
     TRY(mhmr_launch_hph_inputs(feat32, zK, det_b, det_y, det_x, d->cq_x, d->cq_y, d->cv_x, d->cv_y, d->init_tail,
@@ -673,7 +760,6 @@ int mhmr_hph_forward(const mhmr_hph_desc* d, const float* feat32, const float* z
     // token embedding (+ pos_embedding folded into the bias)  (cross_attn_transformer.py:352-357)
     TRY(mhmr_launch_linear_f32(d->token, d->Ktok, nullptr, d->tok_w, d->Ktok, d->tok_b, nullptr, 0, d->x, dim, P, dim, d->Ktok,
                                MHMR_ACT_NONE, s));
-    (void)Mctx; (void)inner; (void)mlp;
     TRY(mhmr_xattn_layers_forward(d->layers, d->depth, dim, d->heads, d->mlp, d->Kc, d->N, B, d->dtype, d->x, d->xn, d->t1, d->t2, d->kv,
                                   ctx16, gstart, ngroups, nmax, chunks, nchunks, P, stream));
     // read-outs + init (model.py:571-575), 6D -> rotmat -> rotvec, distance post-processing

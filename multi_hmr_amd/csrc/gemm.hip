@@ -260,9 +260,6 @@ int launch_dt(const GemmArgs& g, hipStream_t s) {
 
 }  // namespace
 
-bool mhmr_gemm256_eligible(const GemmArgs& g);
-int mhmr_launch_gemm256(const GemmArgs& g, int dtype, hipStream_t s);
-
 int mhmr_cu_count() {
     static std::atomic<int> cus[64];
     int dev = 0;

@@ -666,8 +666,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs g) {
 
 #ifdef MHMR_GEMM_STAMPS
 }  // namespace
-extern "C" int mhmr_debug_gemm_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_stamps), &p, sizeof(p)); }
-extern "C" int mhmr_debug_gemm_sametile(int v) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_sametile), &v, sizeof(v)); }
+extern "C" __attribute__((visibility("default"))) int mhmr_debug_gemm_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_stamps), &p, sizeof(p)); }
+extern "C" __attribute__((visibility("default"))) int mhmr_debug_gemm_sametile(int v) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_sametile), &v, sizeof(v)); }
 namespace {
 #endif
 

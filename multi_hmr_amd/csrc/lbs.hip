@@ -1104,8 +1104,8 @@ __global__ __launch_bounds__(64 * (LBS_NC + LBS_NL), 3) void lbs_vertex_kernel(c
 }  // namespace
 
 #ifdef MHMR_LBS_STAMPS
-extern "C" int mhmr_debug_lbs_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_lbs_stamps), &p, sizeof(p)); }
-extern "C" int mhmr_debug_pose_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_pose_stamps), &p, sizeof(p)); }
+extern "C" __attribute__((visibility("default"))) int mhmr_debug_lbs_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_lbs_stamps), &p, sizeof(p)); }
+extern "C" __attribute__((visibility("default"))) int mhmr_debug_pose_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_pose_stamps), &p, sizeof(p)); }
 #endif
 
 static int lbs_forward_impl(const mhmr_lbs_consts* c, const float* rotvec, const float* betas, const float* expr,

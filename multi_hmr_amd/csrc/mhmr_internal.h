@@ -1,4 +1,5 @@
-// Internal (non-ABI) declarations shared by the kernel translation units of libmhmr.so.
+// Internal (non-ABI) declarations shared by the translation units of libmhmr.so: the launch-argument structs and, at the end, the ONLY
+// declaration of every function that one .hip file defines and another calls.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,8 +77,6 @@ __host__ __device__ inline long long mhmr_phys_row(int m, int img_rows, int img_
     return img_rows > 0 ? (long long)(m / img_rows) * img_stride + (m % img_rows) : (long long)m;
 }
 
-int mhmr_launch_gemm(const GemmArgs& g, int dtype, hipStream_t s);
-
 // Per-DEVICE one-time kernel attributes (hipFuncAttributeMaxDynamicSharedMemorySize is a property of the function ON A DEVICE: a process
 // that drives a second GPU must set it there too).  One bit per device id in a launcher-local mask; setting an attribute twice from two
 // host threads is harmless, so a relaxed fetch_or is enough.  Device ids >= 64 set the attribute on every call.
@@ -94,9 +93,6 @@ struct DeviceOnce {
     }
     void mark(int dev) { if (dev >= 0 && dev < 64) done.fetch_or(1ull << dev, std::memory_order_relaxed); }
 };
-// multiProcessorCount of the CURRENT device (cached per device id)
-int mhmr_cu_count();
-
 // "Any-order" launches (hipExtAnyOrderLaunch: the AQL packet goes out WITHOUT the barrier bit, so the command processor does not wait for
 // the previous kernel of the stream to finish before dispatching this one).  capi.hip sets the thread-local flag around launches whose
 // inputs were complete before the PREVIOUS launch started and whose outputs nothing touches until the next ordinary launch (which waits
@@ -115,19 +111,99 @@ inline void mhmr_launch_kernel(F kernel, dim3 grid, dim3 block, size_t lds, hipS
     else hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
 }
 
-// Row statistics carried by the class-row kernel's launches (vit_cls.hip, round 6).  cls_pstats [rows][cls_nblk][2]: block sums of the class
-// rows (written by epi = 1, read by epi = 0 / 2 in place of `rowstats`); st_*: the patch rows' statistics as extra workgroups of an epi = 1
-// launch (st_pstats = the big GEMM's block sums, st_rowstats = its consumers' (mean, rstd); st_B images x st_N patch rows of st_Tp-row images).
-struct ClsStats {
-    float* cls_pstats = nullptr;
-    int cls_nblk = 0, cls_C = 0;
-    float eps = 1e-6f;
-    const float* st_pstats = nullptr;
-    float* st_rowstats = nullptr;
-    int st_B = 0, st_N = 0, st_Tp = 0, st_C = 0;
+// The class-row linear (vit_cls.hip): the kernels' argument.
+struct ClsArgs {
+    const void* A = nullptr; long long a_stride = 0;      // activation row b at A + b * a_stride (elements); k contiguous
+    const void* W = nullptr; int ldw = 0;                 // [N][ldw] weight rows (k contiguous)
+    int B = 0, N = 0, K = 0, a_k = 0;                     // K = total k (2 * a_k with a low-half weight pass: A's k index wraps at a_k), K % 128 == 0
+    const float* bias = nullptr; const float* gamma = nullptr;
+    void* out = nullptr; long long o_stride = 0;          // output row b at out + b * o_stride (elements of the output type)
+    int n_base = 0, C = 0;                                // CLS_QKV: global column of local column 0; embed dim (column regions Q | K | V)
+    void* vt = nullptr; int H = 0, Tp = 0, vcol = 0;      // CLS_QKV: V^T [B][H][64][Tp], the (already key-permuted) column of the class token
+    // LayerNorm fold (GemmArgs above): consumer side -- rowstats (mean, rstd) of row b at rowstats + b * rs_stride floats,
+    // out = rstd * (acc - mean * colsum_n) + fbias_n (bias null); producer side (CLS_RESID) -- x16: 16-bit copy of the updated rows
+    const float* rowstats = nullptr; long long rs_stride = 0; const float* colsum = nullptr; const float* fbias = nullptr;
+    void* x16 = nullptr; long long x_stride = 0;
+    // Row statistics carried by the class-row launches (round 6).  Class-row block sums: CLS_RESID writes cls_pstats[row][N / 16][2]; a
+    // consumer (CLS_QKV / CLS_GELU) with cls_pstats != null takes (mean, rstd) of its rows from them (cls_nblk = the producing linear's
+    // N / 16 = embed_dim / 16, cls_C = embed_dim) instead of from `rowstats`
+    float* cls_pstats = nullptr; int cls_nblk = 0, cls_C = 0; float cls_eps = 1e-6f;
+    // statistics role (CLS_RESID only): the patch rows' statistics as st_blocks extra workgroups at blockIdx.x >= N / 16, which run
+    // ln_stats_patch_rows over st_B images x st_N patch rows of st_Tp-row images (st_pstats = the big GEMM's block sums, st_rowstats = its
+    // consumers' (mean, rstd)).  st_blocks is derived by mhmr_launch_cls_linear.
+    const float* st_pstats = nullptr; float* st_rowstats = nullptr; int st_blocks = 0, st_B = 0, st_N = 0, st_Tp = 0, st_C = 0;
 };
+// epilogues of the class-row linear: CLS_QKV = Q | K | V projection of the class rows (Q pre-scaled, V scattered into column `vcol` of V^T),
+// CLS_RESID = out32 += gamma * (acc + bias), CLS_GELU = out16 = gelu(acc + bias)
+enum { CLS_QKV = 0, CLS_RESID = 1, CLS_GELU = 2 };
 
 // ---- per-kernel-family hipEvent profiling (bench.py roofline leg) ----
 enum ProfKind { PROF_GEMM = 0, PROF_ATTN = 1, PROF_LBS = 2, PROF_KINDS = 3 };
+
+// ================================================================================================================================
+// Every function one translation unit defines and another calls, by defining file.  Default arguments live here, once.
+// ================================================================================================================================
+// ---- capi.hip
 void prof_begin(int kind, hipStream_t s);
 void prof_end(int kind, hipStream_t s, double work);
+
+// ---- gemm.hip
+int mhmr_launch_gemm(const GemmArgs& g, int dtype, hipStream_t s);
+int mhmr_cu_count();      // multiProcessorCount of the CURRENT device (cached per device id)
+bool mhmr_splitk_plan(int M, int N, int K, int* ksplit, int* nslices);
+
+// ---- gemm256.hip
+bool mhmr_gemm256_eligible(const GemmArgs& g);
+int mhmr_launch_gemm256(const GemmArgs& g, int dtype, hipStream_t s);
+
+// ---- attention.hip
+int mhmr_launch_attention(const void* qk, const void* vt, void* out, int B, int T, int Tp, int C, int H, int dtype, int* flags, hipStream_t s,
+                          int ldo = 0, int o8 = 0);
+int mhmr_launch_attention_ex(const void* qk, const void* vt, void* out, int B, int T, int Tp, int C, int H, int dtype, float limit_log2,
+                             int variant, int* flags, hipStream_t s);
+int mhmr_attention_flag_count_impl(int B, int Tp, int H);
+
+// ---- attention_f32.hip
+int mhmr_launch_attention_f32(const float* qkv, void* out, int B, int T, int Tp, int C, int H, int dtype, hipStream_t s);
+
+// ---- vit_misc.hip
+int mhmr_launch_im2col(const float* x, void* a, int B, int S, int G, int Kp, int dtype, hipStream_t s);
+int mhmr_launch_im2col_pair(const float* x, void* a, int B, int S, int G, int Kp, int dtype, hipStream_t s);
+int mhmr_launch_init_rows(float* resid, const float* cls_pos0, int B, int T, int Tp, int C, hipStream_t s);
+int mhmr_launch_layernorm(const float* in, const float* w, const float* b, void* out16, int rows, int C, float eps, int dtype, hipStream_t s);
+int mhmr_launch_layernorm_pitch(const float* in, const float* w, const float* b, void* out16, int ld16, int o8, int rows, int C, float eps,
+                                int dtype, hipStream_t s);
+int mhmr_launch_layernorm_pair(const float* in, const float* w, const float* b, void* out16, int rows, int C, float eps, int dtype,
+                               hipStream_t s);
+int mhmr_launch_gelu_pair(const float* in, void* out, long long M, int N, int dtype, hipStream_t s);
+int mhmr_launch_vt_transpose(const void* v, int ldv, void* vt, int B, int Tp, int H, int dtype, hipStream_t s);
+int mhmr_launch_splitk_resid(const float* part, int nslices, int rows, int C, const float* bias, const float* gamma, float* resid, void* x16,
+                             int ldx, float* rowstats, float eps, int dtype, hipStream_t s);
+int mhmr_launch_ln_stats(const float* pstats, const float* resid, float* rowstats, int B, int N, int Tp, int C, float eps, hipStream_t s);
+int mhmr_launch_final_norm(const float* resid, const float* w, const float* b, void* ctx16, int ldctx, float* feat32, int B, int Np, int Tp,
+                           int C, float eps, int dtype, hipStream_t s);
+
+// ---- vit_cls.hip
+int mhmr_launch_cls_linear(const ClsArgs& a, int epi, int dtype, hipStream_t s);
+
+// ---- hph.hip
+int mhmr_launch_linear_f32(const float* X, int ldx, const int* row_idx, const float* W, int ldw, const float* bias, const float* R, int ldr,
+                           float* Y, int ldy, int M, int N, int K, int act, hipStream_t s);
+int mhmr_launch_layernorm_f32(const float* in, const float* w, const float* b, float* out, int rows, int C, float eps, hipStream_t s);
+int mhmr_launch_scores(const void* hid, int ld, const float* w2, const float* b2, float* scores, int rows, int C, int dtype, hipStream_t s);
+int mhmr_launch_detect_count(const float* scores, int B, int G, int nms_kernel, float thr, int* counts, hipStream_t s);
+int mhmr_launch_detect_write(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b, int* det_y, int* det_x,
+                             float* det_score, int cap, hipStream_t s);
+int mhmr_launch_person_groups(const int* counts, const int* det_b, int P, int B, int cap, int* base, int* gstart, int ngcap, int* chunks,
+                              int nccap, int* info, hipStream_t s);
+int mhmr_launch_camera_embed(const float* Kmat, const float* freq, int B, int G, int patch, float* zK, void* ctx16, int Kc, int C, int dtype,
+                             int nbands, hipStream_t s);
+int mhmr_launch_hph_inputs(const float* feat32, const float* zK, const int* det_b, const int* det_y, const int* det_x, const float* cq_x,
+                           const float* cq_y, const float* cv_x, const float* cv_y, const float* init_tail, int ntail, float* zc, float* token,
+                           int Ktok, void* ctx16, int Kc, int* det_row, int P, int G, int C, int dtype, const int* nvalid, int cam_dim,
+                           hipStream_t s);
+int mhmr_launch_hph_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads, hipStream_t s);
+int mhmr_launch_hph_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N, hipStream_t s);
+int mhmr_launch_hph_decode(const float* dec, int ldd, int nb, const float* Kmat, const int* det_b, float fn, int nearness, float* rotmat,
+                           float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, hipStream_t s);
+int mhmr_launch_loc(const float* offset, const int* det_y, const int* det_x, int patch, float* loc, int P, hipStream_t s);

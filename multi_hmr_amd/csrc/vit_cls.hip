@@ -26,27 +26,6 @@
 
 namespace {
 
-struct ClsArgs {
-    const void* A; long long a_stride;      // activation row b at A + b * a_stride (elements); k contiguous
-    const void* W; int ldw;                 // [N][ldw] weight rows (k contiguous)
-    int B, N, K, a_k;                       // K = total k (2 * a_k with a low-half weight pass: A's k index wraps at a_k), K % 128 == 0
-    const float* bias; const float* gamma;
-    void* out; long long o_stride;          // output row b at out + b * o_stride (elements of the output type)
-    int n_base, C;                          // CLS_QKV: global column of local column 0; embed dim (column regions Q | K | V)
-    void* vt; int H, Tp, vcol;              // CLS_QKV: V^T [B][H][64][Tp], the (already key-permuted) column of the class token
-    // LayerNorm fold (GemmArgs in mhmr_internal.h): consumer side -- rowstats (mean, rstd) of row b at rowstats + b * rs_stride floats,
-    // out = rstd * (acc - mean * colsum_n) + fbias_n (bias null); producer side (CLS_RESID) -- x16: 16-bit copy of the updated rows
-    const float* rowstats; long long rs_stride; const float* colsum; const float* fbias;
-    void* x16; long long x_stride;
-    // class-row block sums: CLS_RESID writes cls_pstats[row][N / 16][2]; a consumer with cls_pstats != null takes (mean, rstd) of its rows
-    // from them (cls_nblk = the producing linear's N / 16 = embed_dim / 16, cls_C = embed_dim) instead of from `rowstats`
-    float* cls_pstats; int cls_nblk, cls_C; float cls_eps;
-    // statistics role (CLS_RESID only): st_blocks > 0 extra workgroups at blockIdx.x >= N / 16 run ln_stats_patch_rows over st_B x st_N rows
-    const float* st_pstats; float* st_rowstats; int st_blocks, st_B, st_N, st_Tp, st_C;
-};
-
-enum { CLS_QKV = 0, CLS_RESID = 1, CLS_GELU = 2 };
-
 // U = k steps (of 32) per batch of loads: a wave requests 3 U fragments (weight + two row blocks) before the first MFMA of the batch, so
 // a batch costs ONE L2 round trip (hipcc does not unroll the run-time k loop by itself: one round trip per k step, 32 in a row for fc2)
 template <int DT, int EPI, int U, int NW>
@@ -228,39 +207,23 @@ int launch_cls(const ClsArgs& a, int epi, hipStream_t s) {
 
 }  // namespace
 
-// epi: 0 = Q | K | V projection of the class rows (Q pre-scaled, V scattered into column `vcol` of V^T), 1 = out32 += gamma * (acc + bias),
-// 2 = out16 = gelu(acc + bias)
-int mhmr_launch_cls_linear_fold(const void* A, long long a_stride, const void* W, int ldw, int B, int N, int K, int a_k, const float* bias,
-                                const float* gamma, void* out, long long o_stride, int n_base, int C, void* vt, int H, int Tp, int vcol, int epi,
-                                int dtype, const float* rowstats, long long rs_stride, const float* colsum, const float* fbias, void* x16,
-                                long long x_stride, hipStream_t s, const ClsStats* st) {
-    if (B <= 0 || N <= 0 || N % 16 || K <= 0 || K % 128 || ldw < K || (a_k > 0 && K != 2 * a_k) || a_stride % 8 || ldw % 8) return MHMR_ERR_BAD_SHAPE;
-    if (epi == CLS_RESID && !gamma) return MHMR_ERR_BAD_ARG;
-    if (epi == CLS_QKV && (C % 64 || n_base % 16 || !vt || Tp <= vcol)) return MHMR_ERR_BAD_SHAPE;
-    if (rowstats && (!colsum || !fbias || bias || epi == CLS_RESID)) return MHMR_ERR_BAD_ARG;
-    ClsArgs a{A, a_stride, W, ldw, B, N, K, a_k, bias, gamma, out, o_stride, n_base, C, vt, H, Tp, vcol, rowstats, rs_stride, colsum, fbias,
-              x16, x_stride, nullptr, 0, 0, 1e-6f, nullptr, nullptr, 0, 0, 0, 0, 0};
-    if (st) {
-        if (st->cls_pstats) {
-            // producer: one pair per 16-column workgroup; consumers: N / 16 pairs of a row, four lanes x at most eight 16-byte loads
-            if (epi == CLS_RESID ? st->cls_nblk != N / 16 : (st->cls_nblk % 8 || st->cls_nblk > 64 || st->cls_C != 16 * st->cls_nblk || !colsum || !fbias || bias))
-                return MHMR_ERR_BAD_ARG;
-            a.cls_pstats = st->cls_pstats; a.cls_nblk = st->cls_nblk; a.cls_C = st->cls_C; a.cls_eps = st->eps;
-        }
-        if (st->st_pstats && epi == CLS_RESID) {
-            if (!st->st_rowstats || st->st_C % 128 || st->st_C > 1024 || st->st_B <= 0 || st->st_N <= 0) return MHMR_ERR_BAD_ARG;
-            const int threads = 64 * (K % 256 == 0 ? 8 : 4);
-            a.st_pstats = st->st_pstats; a.st_rowstats = st->st_rowstats; a.st_B = st->st_B; a.st_N = st->st_N; a.st_Tp = st->st_Tp; a.st_C = st->st_C;
-            a.cls_eps = st->eps;
-            a.st_blocks = (int)(((long long)st->st_B * st->st_N * 8 + threads - 1) / threads);
-        }
+// The one entry (ClsArgs and the CLS_* epilogues: mhmr_internal.h).  st_blocks is derived here; everything else is the caller's.
+int mhmr_launch_cls_linear(const ClsArgs& in, int epi, int dtype, hipStream_t s) {
+    ClsArgs a = in;
+    if (a.B <= 0 || a.N <= 0 || a.N % 16 || a.K <= 0 || a.K % 128 || a.ldw < a.K || (a.a_k > 0 && a.K != 2 * a.a_k) || a.a_stride % 8 || a.ldw % 8)
+        return MHMR_ERR_BAD_SHAPE;
+    if (epi == CLS_RESID && !a.gamma) return MHMR_ERR_BAD_ARG;
+    if (epi == CLS_QKV && (a.C % 64 || a.n_base % 16 || !a.vt || a.Tp <= a.vcol)) return MHMR_ERR_BAD_SHAPE;
+    if (a.rowstats && (!a.colsum || !a.fbias || a.bias || epi == CLS_RESID)) return MHMR_ERR_BAD_ARG;
+    // producer: one pair per 16-column workgroup; consumers: N / 16 pairs of a row, four lanes x at most eight 16-byte loads
+    if (a.cls_pstats && (epi == CLS_RESID ? a.cls_nblk != a.N / 16
+                                          : (a.cls_nblk % 8 || a.cls_nblk > 64 || a.cls_C != 16 * a.cls_nblk || !a.colsum || !a.fbias || a.bias)))
+        return MHMR_ERR_BAD_ARG;
+    a.st_blocks = 0;
+    if (a.st_pstats) {
+        if (epi != CLS_RESID || !a.st_rowstats || a.st_C % 128 || a.st_C > 1024 || a.st_B <= 0 || a.st_N <= 0) return MHMR_ERR_BAD_ARG;
+        const int threads = 64 * (a.K % 256 == 0 ? 8 : 4);
+        a.st_blocks = (int)(((long long)a.st_B * a.st_N * 8 + threads - 1) / threads);
     }
     return dtype == MHMR_DT_F16 ? launch_cls<MHMR_DT_F16>(a, epi, s) : launch_cls<MHMR_DT_BF16>(a, epi, s);
-}
-
-int mhmr_launch_cls_linear(const void* A, long long a_stride, const void* W, int ldw, int B, int N, int K, int a_k, const float* bias,
-                           const float* gamma, void* out, long long o_stride, int n_base, int C, void* vt, int H, int Tp, int vcol, int epi,
-                           int dtype, hipStream_t s) {
-    return mhmr_launch_cls_linear_fold(A, a_stride, W, ldw, B, N, K, a_k, bias, gamma, out, o_stride, n_base, C, vt, H, Tp, vcol, epi, dtype,
-                                       nullptr, 0, nullptr, nullptr, nullptr, 0, s, nullptr);
 }

@@ -23,6 +23,16 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     for sym in declared:
         assert getattr(lib, sym) is not None
+    # ... and nothing else: the library is built with hidden visibility, the header's declarations are its whole dynamic surface
+    # (llvm-readelf of the ROCm LLVM beside hipcc; "__hip_*": one toolchain symbol per translation unit)
+    import subprocess
+    hipcc = os.path.realpath(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
+    readelf = os.path.join(os.path.dirname(os.path.dirname(hipcc)), "lib", "llvm", "bin", "llvm-readelf")
+    rows = [l.split() for l in subprocess.run([readelf, "--dyn-syms", "--wide", _lib.LIB_PATH], check=True, capture_output=True,
+                                              text=True).stdout.splitlines()]
+    defined = {r[7].split("@")[0] for r in rows if len(r) == 8 and r[0].rstrip(":").isdigit() and r[6] != "UND"}
+    exported = {n for n in defined if not n.startswith("__hip_")}
+    assert exported == declared, sorted(exported ^ declared)[:20]
     # argument validation happens before any launch, so it is testable without a GPU
     assert lib.mhmr_prof_enable(99) == -1
     # the library says which sources it was built from, and build() trusts that, not file times
