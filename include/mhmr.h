@@ -670,6 +670,60 @@ typedef struct {
 int mhmr_scene_pack(const mhmr_scene_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Training loss (reference loss.py:8-40 _neg_loss, 47-115 Loss.forward) and its gradient with respect to the
+ * predictions, DESIGN.md section 17.  Eleven values in the reference's dict_loss order:
+ *   0 total, 1 bce, 2 offset, 3 rotmat, 4 shape, 5 dist, 6 transl, 7 j3d, 8 v3d, 9 j2d, 10 v2d.
+ * Tensors (fp32, contiguous; `*_hat` = prediction): scores [B][G][G] (the target counts as positive where >= 1),
+ * offset [P][2], rotmat [P][nrot] (53 * 9), shape_hat [P][nb_hat] / shape [P][nb_gt] (the first min(nb_hat, nb_gt)
+ * columns are compared), dist [P] (dist_postprocessed), transl [P][3], pelvis [P][3] (transl_pelvis), j3d [P][J][3],
+ * v3d [P][V][3], j2d [P][J][2], v2d [P][V][2].  P == 0 is legal (the person pointers are not read: the person
+ * terms are 0, bce is computed).
+ * Arithmetic: every element |a - b| is formed in fp32 with the reference's operations in its order, no FMA --
+ * (y - pelvis) - (y_hat - pelvis_hat) for j3d / v3d, y_hat - y elsewhere; a 2D point counts when both target
+ * coordinates are > 0 and < img_size; every sum is fp64, combined in a fixed order (lane, wave, workgroup, then a
+ * launch that walks the workgroup partials by index: no floating-point atomics, bit-reproducible); the focal term
+ * is fp64 throughout from the fp32 score (eps 1e-7; num_pos == 0 -> -neg_loss, decided on the device); the
+ * normalisers (P, P J, P V, the in-frame counts), nan_to_num (a NaN / +-inf term becomes 0), the alpha weights
+ * and the epoch gate (use_2d) are applied in fp64 and each value is rounded to fp32 once.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float *scores_hat, *offset_hat, *rotmat_hat, *shape_hat, *dist_hat, *transl_hat, *pelvis_hat, *j3d_hat, *v3d_hat, *j2d_hat,
+        *v2d_hat;
+    const float *scores, *offset, *rotmat, *shape, *dist, *transl, *pelvis, *j3d, *v3d, *j2d, *v2d;
+    int B, G, P, V, J, nrot, nb_hat, nb_gt;
+    float img_size;
+    int use_2d;               /* epoch >= start_2d_epoch (loss.py:96) */
+    double alpha[10];         /* alpha_bce, _offset, _rotmat, _shape, _dist, _transl, _j3d, _v3d, _j2d, _v2d (loss.py:121-136) */
+} mhmr_loss_desc;
+
+/* gradient outputs of mhmr_loss_backward, shaped like the predictions; NULL = not wanted */
+typedef struct {
+    float *scores, *offset, *rotmat, *shape, *dist, *transl, *pelvis, *j3d, *v3d, *j2d, *v2d;
+} mhmr_loss_grads;
+
+/* the device block `out` of mhmr_loss_forward: 32 four-byte words --
+ *   [0..10] fp32 the eleven values;  [12] int num_pos, [13] int in-frame j2d points, [14] int in-frame v2d points;
+ *   [16 + i] int: 1 if term i was finite before nan_to_num, 0 if it was replaced by 0 ([16] = 1). */
+#define MHMR_LOSS_OUT_BYTES 128
+
+/* bytes of the fp64 workgroup partials mhmr_loss_forward needs (the same for every shape: the grid is fixed) */
+long long mhmr_loss_workspace_bytes(void);
+/* loss.py:49-113.  Two launches on `stream`; ws is written before it is read (no clearing needed).  Validated
+ * before any launch: d, ws, out NULL or ws_bytes too small, a NULL scores pointer, a NULL person pointer with P > 0
+ * -> MHMR_ERR_BAD_ARG; B, G, V, J, nrot, nb_hat, nb_gt < 1, P < 0, or a tensor of 2^31 or more elements ->
+ * MHMR_ERR_BAD_ARG. */
+int mhmr_loss_forward(const mhmr_loss_desc* d, void* ws, long long ws_bytes, void* out, void* stream);
+/* d total / d prediction = grad_total (device scalar, the upstream gradient of `total`) * alpha_term * sign(element)
+ * / normaliser, for every non-NULL pointer of g; `out` is the block the forward of the SAME d left (normalisers,
+ * flags).  Signs are recomputed in fp32 as in the forward (sign(0) = 0); out-of-frame 2D points and shape columns
+ * >= min(nb_hat, nb_gt) get 0; the 2D gradients are 0 when use_2d == 0; pelvis[p][a] = -(sum_j j3d[p][j][a] +
+ * sum_v v3d[p][v][a]) from integer sign sums, scaled once in fp64 (exact, order-free); the score gradient is the
+ * analytic derivative of the focal term in fp64, rounded once.  A term whose finite flag is 0 has ALL its gradients
+ * 0 (torch: 0 behind an inf, NaN behind a NaN).  The gradient of the targets is never produced.  Validation as
+ * for the forward (plus out, grad_total, g NULL), before any launch. */
+int mhmr_loss_backward(const mhmr_loss_desc* d, const void* out, const float* grad_total, const mhmr_loss_grads* g, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement: hipEvent brackets around every launch of one kernel family (0 = GEMM, 1 = attention, 2 = LBS
  * vertex kernel), recorded on the launch stream.  enable(kind >= 0) starts a fresh window, enable(-1) stops;
  * collect() synchronises the recorded events and returns launches, summed milliseconds and summed work

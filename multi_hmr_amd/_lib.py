@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "anny.hip", "render.hip", "scene.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -35,7 +35,8 @@ class MhmrError(RuntimeError):
 COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: per-translation-unit extra flags.  render.hip: every step rounded on its own (the render contract's fp64 geometry and fp32 blend
 #: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  scene.hip: the same fp64 geometry.
-EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"]}
+#: loss.hip: every element of the training loss is the reference's fp32 subtraction(s), rounded one by one (its sign is the gradient).
+EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -158,6 +159,22 @@ class PreImage(C.Structure):
                 [(n, _vp) for n in ("kh", "bh", "kv", "bv", "tmp")])
 
 
+class LossDesc(C.Structure):
+    """include/mhmr.h mhmr_loss_desc."""
+    TENSORS = ("scores", "offset", "rotmat", "shape", "dist", "transl", "pelvis", "j3d", "v3d", "j2d", "v2d")
+    _fields_ = ([(n + "_hat", _vp) for n in TENSORS] + [(n, _vp) for n in TENSORS] +
+                [(n, _i) for n in ("B", "G", "P", "V", "J", "nrot", "nb_hat", "nb_gt")] + [("img_size", _f), ("use_2d", _i),
+                                                                                          ("alpha", C.c_double * 10)])
+
+
+class LossGrads(C.Structure):
+    """include/mhmr.h mhmr_loss_grads."""
+    _fields_ = [(n, _vp) for n in LossDesc.TENSORS]
+
+
+LOSS_OUT_BYTES = 128                # include/mhmr.h MHMR_LOSS_OUT_BYTES
+
+
 _SIGS = {
     "mhmr_version": ([], _i),
     "mhmr_source_hash": ([], C.c_char_p),
@@ -213,6 +230,9 @@ _SIGS = {
     "mhmr_render_views_workspace_bytes": ([C.POINTER(RenderDesc), _i], C.c_longlong),
     "mhmr_render_views": ([C.POINTER(RenderDesc), _i, _vp, _vp], _i),
     "mhmr_scene_pack": ([C.POINTER(SceneDesc), _vp], _i),
+    "mhmr_loss_workspace_bytes": ([], C.c_longlong),
+    "mhmr_loss_forward": ([C.POINTER(LossDesc), _vp, C.c_longlong, _vp, _vp], _i),
+    "mhmr_loss_backward": ([C.POINTER(LossDesc), _vp, _fp, C.POINTER(LossGrads), _vp], _i),
     "mhmr_prof_enable": ([_i], _i),
     "mhmr_prof_collect": ([C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)], _i),
 }

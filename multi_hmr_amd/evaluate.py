@@ -261,7 +261,7 @@ class Evaluator:
 
 
 @torch.no_grad()
-def evaluate_dataset(model, batches, gt_builder, det_thresh=0.3, nms_kernel_size=3, use_gt_idx=False, evaluator=None):
+def evaluate_dataset(model, batches, gt_builder, det_thresh=0.3, nms_kernel_size=3, use_gt_idx=False, evaluator=None, loss=None, epoch=0):
     """The reference's evaluation loop (train.py:346-429) over ``batches`` of ``(x, y)``: ``gt = gt_builder.prepare(y)``, the
     inference forward with ``K=gt['K']``, matching and metrics; returns ``Evaluator.summary()``.  ``evaluator``: an ``Evaluator`` carrying
     the regressors (a fresh plain one otherwise).  A batch without humans is skipped (``prepare`` returns None; the reference would fail
@@ -269,8 +269,15 @@ def evaluate_dataset(model, batches, gt_builder, det_thresh=0.3, nms_kernel_size
 
     ``use_gt_idx=True`` is OURS -- the reference has no such switch: the ground truth's own ``gt['idx']`` goes through the
     ``is_training=True`` forward, so every ground-truth person gets exactly one prediction at its own cell and the mesh metrics are
-    measured without the detector in the way."""
+    measured without the detector in the way.
+
+    ``loss``: a ``multi_hmr_amd.Loss`` (needs ``use_gt_idx=True``): the ``is_training`` output of every batch also goes through it with
+    ``epoch`` and the model's ``img_size``, and the summary gains ``loss/<key>`` -- the mean over the batches of each of its eleven
+    values, as the reference's validation meters keep them (train.py:346-429).  The sums stay on the device until the end."""
+    if loss is not None and not use_gt_idx:
+        raise _lib.MhmrError("evaluate_dataset(loss=...) needs use_gt_idx=True: the loss reads the is_training output at the ground truth's cells")
     ev = evaluator if evaluator is not None else Evaluator()
+    loss_sum, loss_n = None, 0
     dev = next(iter(model.parameters())).device if hasattr(model, "parameters") else torch.device("cuda")
     for x, y in batches:
         y = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in y.items()}
@@ -283,7 +290,14 @@ def evaluate_dataset(model, batches, gt_builder, det_thresh=0.3, nms_kernel_size
             n = int(gt["idx"][0].shape[0])
             pelvis = out["transl_pelvis"] if "transl_pelvis" in out else out["j3d"][:, :1]
             pred = [dict(v3d=out["v3d"][i], j3d=out["j3d"][i], j2d=out["j2d"][i], transl_pelvis=pelvis[i]) for i in range(n)]
+            if loss is not None:
+                _, dl = loss(out, gt, epoch=epoch, img_size=model.img_size)
+                vals = torch.stack([dl[k] for k in dl]).double()
+                loss_sum, loss_n, loss_keys = (vals if loss_sum is None else loss_sum + vals), loss_n + 1, list(dl)
         else:
             pred = model(x, is_training=False, K=gt["K"], det_thresh=det_thresh, nms_kernel_size=nms_kernel_size)
         ev.update(pred, gt)
-    return ev.summary()
+    summary = ev.summary()
+    if loss_n:
+        summary.update({"loss/" + k: v / loss_n for k, v in zip(loss_keys, loss_sum.tolist())})
+    return summary
