@@ -296,6 +296,7 @@ static const bool g_force_gemm128 = getenv("MHMR_GEMM128") != nullptr;
 bool mhmr_splitk_plan(int M, int N, int K, int* ksplit, int* nslices) {
     static const bool on = !(getenv("MHMR_SPLITK") && atoi(getenv("MHMR_SPLITK")) == 0);
     if (!on || g_force_gemm128 || M <= 0 || M % 256 || N % 256 || K % 128) return false;
+    if (N > 1024) return false;                 // widths the reduction has a kernel for (vit_misc.hip: mhmr_launch_splitk_resid, C = 256 .. 1024)
     const int ncu = mhmr_cu_count();
     const int tiles = (M / 256) * (N / 256), nt = K / 64;
     if (ncu <= 0 || tiles <= 0) return false;

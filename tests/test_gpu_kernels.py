@@ -921,6 +921,21 @@ def test_splitk_plan_declines_long_launches(L):
     assert L.mhmr_splitk_workspace_bytes(256 * 129, 1024, 4096) == 0      # 516 tiles
     assert L.mhmr_splitk_workspace_bytes(4352, 1024, 256) == 0             # four k tiles
     assert L.mhmr_splitk_workspace_bytes(4352 + 128, 1024, 4096) == 0      # M not a multiple of 256
+    # a width the row-wise reduction has no kernel for (256 .. 1024 only): no workspace is advertised, and the entry refuses BEFORE it
+    # launches the split GEMM -- the workspace and the residual stay as they were
+    M, N, K = 256, 1280, 4096
+    assert L.mhmr_splitk_workspace_bytes(M, N, K) == 0
+    g = torch.Generator(device=dev()).manual_seed(4)
+    A = torch.randn(M, K, generator=g, device=dev()).half()
+    W = (torch.randn(N, K, generator=g, device=dev()) / math.sqrt(K)).half()
+    bias, gamma = torch.randn(N, generator=g, device=dev()), torch.randn(N, generator=g, device=dev())
+    out32 = torch.full((M, N), 7.0, device=dev())
+    ws = torch.full((8 * M * N,), -3.0, device=dev())                      # room for the eight slices the plan used to hand out
+    rc = L.mhmr_gemm16_splitk_resid(A.data_ptr(), K, W.data_ptr(), K, M, N, K, 0, bias.data_ptr(), gamma.data_ptr(), out32.data_ptr(), None, 0, None,
+                                    1e-6, ws.data_ptr(), ws.numel() * 4, _lib.DT_F16, stream())
+    torch.cuda.synchronize()
+    assert rc != 0
+    assert bool(torch.all(ws == -3.0)) and bool(torch.all(out32 == 7.0))
 
 
 @pytest.mark.parametrize("name,dt,tdt,tol", DTYPES)
