@@ -213,7 +213,6 @@ _SIGS = {
     "mhmr_hph_cross_attn": ([_vp, _vp, _vp, _i, _vp, _i, _i, _vp], _i),
     "mhmr_hph_decode": ([_vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "mhmr_lbs_forward": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp], _i),
-    "mhmr_lbs_forward_fused": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp, _vp], _i),
     "mhmr_preprocess_u8": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i] + [_i] * 7 + [_vp, _vp, _vp, _vp], _i),
     "mhmr_preprocess_u8_batch": ([C.POINTER(PreImage), _vp, _i, _i, _vp, _vp, _vp], _i),
     "mhmr_eval_mesh_errors": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),

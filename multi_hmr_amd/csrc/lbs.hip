@@ -1,13 +1,16 @@
 // SMPL-X linear blend skinning + camera placement (reference blocks/smpl_layer.py:47-155 -> smplx.SMPLX.forward
 // -> lbs), two launches:
 //
-//  1. lbs_pose_kernel   (one wave per person)  Rodrigues x55, pose feature, joint regression from the
+//  1. lbs_pose4_kernel  (one workgroup of four waves per person)  Rodrigues x55, pose feature, joint regression from the
 //     pre-contracted regressor (J = J0 + JS.[betas, expr]), kinematic chain, root rotation / recentring /
 //     back-projected translation folded into the per-joint skinning transforms, 55 posed joints + projection.  It leaves the two
 //     matrix operands of the vertex kernel in MFMA order, each as an f16 pair hi + lo:
 //       F16   F[p] = [pose_feature(486) | betas | expr | 0]
 //       A16   component c of the folded transform [R0 R_w | R0 (t' - pelvis)] of joint j (joints 55..63 zero)
 //     (fragment-major: one 1 KiB block per (person group, part, k step), see the kernel)
+//     History: one wave per person took 9-10 us, the four waves take 7.6 us (round 6); the whole layer as ONE launch (pose role in
+//     the leading workgroups, ready flags in front of the vertex role) was correct and slower at every size -- 48.7 vs 40.2 us at 160
+//     persons, 38.3 vs 30.2 at 20, 32.2 vs 26.6 at 1 -- and is gone from this file.
 //  2. lbs_vertex_kernel (the HBM-bound one; algorithmic bytes = blend basis 64.5 MB + skin weights 2.7 MB once, 214 KB per person out)
 //     One workgroup = one 48-vertex tile for ALL persons of the launch: the tile's slice of the blend basis D = [posedirs ; shapedirs ;
 //     exprdirs] (x 2^10, f16, 162 KiB) streams through an LDS ring exactly once -- HBM sees every basis byte once per launch --
@@ -27,7 +30,6 @@
 //     vertices behind the real ones (packing.pack_smplx: copies of their corner vertices' operand columns, arranged so that ONE lane ends
 //     up with the three posed corners of an extra joint): they cost 5 of 224 workgroups on otherwise idle CUs instead of a third launch
 //     (round 2: lbs_extra_joints_kernel, 3.4 us + a launch gap behind the vertex kernel).
-#include <stdlib.h>
 #include <stddef.h>
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
@@ -37,7 +39,7 @@
 namespace {
 
 constexpr int NJ = 55;
-constexpr int LBS_KB_POSE = 512;      // = LBS_KB (declared below with the vertex kernel's constants; static_assert there)
+constexpr int LBS_KB = 512;           // padded blend depth (486 pose + betas + 10 expression <= 512)
 
 __device__ __forceinline__ void mat3_mul(const float* a, const float* b, float* c) {
 #pragma unroll
@@ -66,280 +68,25 @@ __device__ __forceinline__ void project(const float* K, const float* x, float* o
     o2[1] = K[3] * yx + K[4] * yy + K[5] * yz;
 }
 
-// One person = ONE WAVE: its staging lives in a PoseLds of its own and every synchronisation point is wave-local (LDS accesses of a wave
-// complete in order: a landing wait is all a wave needs to see its own lanes' writes), so the same code runs as a 64-thread workgroup
-// (lbs_pose_kernel) and as one of the twelve waves of a pose-role workgroup of the fused launch (lbs_fused_kernel).
-struct __attribute__((aligned(16))) PoseLds {
-    float sR[NJ][9], sJ[NJ][3], sRw[NJ][9], sTw[NJ][3], sX[36];
-    int sPar[56];
-    // the person's two operand rows are collected here and leave as 16-byte chunks (8 consecutive k / joints of one person are 8
-    // consecutive f16 of the fragment-major layouts): 2 + 2 x 1.5 wide stores per lane instead of ~50 two-byte ones (round 4)
-    __attribute__((aligned(16))) float sF[LBS_KB_POSE];
-    __attribute__((aligned(16))) float sA[12][64];
-};
-static_assert(sizeof(PoseLds) % 16 == 0 && offsetof(PoseLds, sF) % 16 == 0 && offsetof(PoseLds, sA) % 16 == 0, "16-byte chunks");
+// wave-local synchronisation (LDS accesses of a wave complete in order: a landing wait is all a wave needs to see its own lanes' writes)
 #define LBS_WAVE_SYNC()                                        \
     do {                                                       \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
         __builtin_amdgcn_wave_barrier();                       \
     } while (0)
 
-__device__ __forceinline__ void lbs_pose_person(const mhmr_lbs_consts& c, const float* __restrict__ rotvec,
-                                                const float* __restrict__ betas, const float* __restrict__ expr,
-                                                const float* __restrict__ loc, const float* __restrict__ dist,
-                                                const float* __restrict__ Kmat, const int* __restrict__ det_b, int P, int Pp,
-                                                _Float16* __restrict__ F16, _Float16* __restrict__ A16, float* __restrict__ xf,
-                                                float* __restrict__ j3d, float* __restrict__ j2d,
-                                                float* __restrict__ transl_out, int p, PoseLds& L) {
-    float (&sR)[NJ][9] = L.sR; float (&sJ)[NJ][3] = L.sJ; float (&sRw)[NJ][9] = L.sRw; float (&sTw)[NJ][3] = L.sTw; float (&sX)[36] = L.sX;
-    int (&sPar)[56] = L.sPar;
-    float (&sF)[LBS_KB_POSE] = L.sF; float (&sA)[12][64] = L.sA;
-    const int j = threadIdx.x & 63;
-    // Both operands are stored FRAGMENT-MAJOR: the 64 lanes of a wave read one (person group, part, k step) fragment as 1 KiB of
-    // consecutive bytes (16 B per lane, lane = 16 * (k group) + person-in-group), i.e. eight whole 128-byte lines per wave
-    // instruction; a row-major [person][k] image makes every fragment load touch 16 lines for 64 useful bytes each, and the TA,
-    // not the matrix pipe or HBM, then paces the vertex kernel (93 us at 160 persons).
-    //   F16 [group][hi|lo][Kb/32][64 lanes][8]      A16 [12 comps][hi|lo][group][2][64 lanes][8]
-    const int ngr = Pp / 16, grp = p >> 4, pin = p & 15, nst = c.Kb / 32;
-    auto put_f = [&](int k, float v) { sF[k] = v; };
-    auto put_a = [&](int comp, int joint, float v) { sA[comp][joint] = v; };
-    // chunk kb (k = 8 kb .. 8 kb + 7) of the feature row / chunk (comp, jb) of the transform rows -> hi and lo halves, 16 bytes each
-    typedef Op<MHMR_DT_F16>::V8 H8;
-    auto flush = [&](bool zero) {
-        for (int kb = j; kb < c.Kb / 8; kb += 64) {
-            H8 h, l;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = zero ? 0.f : sF[8 * kb + e];
-                h[e] = (_Float16)v;
-                l[e] = (_Float16)(v - (float)h[e]);
-            }
-            _Float16* f = F16 + ((((size_t)grp * 2) * nst + (kb >> 2)) * 64 + (kb & 3) * 16 + pin) * 8;
-            *(H8*)f = h;
-            *(H8*)(f + (size_t)nst * 512) = l;
-        }
-        for (int ch = j; ch < 96; ch += 64) {
-            const int comp = ch >> 3, jb = ch & 7;
-            H8 h, l;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = zero ? 0.f : sA[comp][8 * jb + e];
-                h[e] = (_Float16)v;
-                l[e] = (_Float16)(v - (float)h[e]);
-            }
-            _Float16* a = A16 + (((((size_t)comp * 2) * ngr + grp) * 2 + (jb >> 2)) * 64 + (jb & 3) * 16 + pin) * 8;
-            *(H8*)a = h;
-            *(H8*)(a + (size_t)ngr * 1024) = l;
-        }
-    };
-    if (p >= P) {  // padding rows of both operand matrices
-        flush(true);
-        return;
-    }
-    const int ncoef = c.nb + 10;
-    if (j < NJ) sPar[j] = c.parents[j];
-    if (j < NJ) {
-        // full_pose (55) from the reference's 53-vector (smpl_layer.py:88-101): 0 -> zero (root applied after LBS),
-        // 1..21 body, 22 jaw <- 52, 23/24 eyes zero, 25..39 left hand <- 22..36, 40..54 right hand <- 37..51
-        int src = -1;
-        if (j >= 1 && j <= 21) src = j;
-        else if (j == 22) src = 52;
-        else if (j >= 25) src = j - 3;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-        if (src >= 0) {
-            const float* rv = rotvec + ((size_t)p * 53 + src) * 3;
-            v0 = rv[0]; v1 = rv[1]; v2 = rv[2];
-        }
-        // smplx batch_rodrigues: angle = |v + 1e-8|, R = I + sin K + (1 - cos) K K
-        const float a0 = v0 + 1e-8f, a1 = v1 + 1e-8f, a2 = v2 + 1e-8f;
-        const float angle = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
-        const float rx = v0 / angle, ry = v1 / angle, rz = v2 / angle;
-        float sn, cs;
-        sincosf(angle, &sn, &cs);
-        const float omc = 1.f - cs;
-        const float Km[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
-        float KK[9];
-        mat3_mul(Km, Km, KK);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) {
-            const float id = (e == 0 || e == 4 || e == 8) ? 1.f : 0.f;
-            const float r = id + sn * Km[e] + omc * KK[e];
-            sR[j][e] = r;
-            if (j >= 1) put_f((j - 1) * 9 + e, r - id);
-        }
-        // joints from the pre-contracted regressor.  The usual 10 betas + 10 expression coefficients: the joint's three rows of JS are
-        // 15 independent 16-byte loads (a run-time loop of dependent scalar loads was most of this kernel's 15 us)
-        if (ncoef == 20) {
-            const f32x4* js = (const f32x4*)(c.JS + (size_t)(j * 3) * 20);
-            f32x4 row[15];
-#pragma unroll
-            for (int i = 0; i < 15; ++i) row[i] = js[i];
-            float cf[20];
-#pragma unroll
-            for (int l = 0; l < 10; ++l) { cf[l] = betas[(size_t)p * 10 + l]; cf[10 + l] = expr[(size_t)p * 10 + l]; }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                float s = c.J0[j * 3 + a];
-#pragma unroll
-                for (int l = 0; l < 20; ++l) s += row[5 * a + (l >> 2)][l & 3] * cf[l];     // (same order of additions as the loop below)
-                sJ[j][a] = s;
-            }
-        } else {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                float s = c.J0[j * 3 + a];
-                const float* js = c.JS + (size_t)(j * 3 + a) * ncoef;
-                for (int l = 0; l < c.nb; ++l) s += js[l] * betas[(size_t)p * c.nb + l];
-                for (int l = 0; l < 10; ++l) s += js[c.nb + l] * expr[(size_t)p * 10 + l];
-                sJ[j][a] = s;
-            }
-        }
-    }
-    if (j == 63) {
-        // (an otherwise idle lane, beside the Rodrigues / joint-regression work of the others: these loads and the sin / cos no longer
-        // sit behind the kinematic chain)  root orientation (roma.rotvec_to_rotmat), translation (inverse_perspective_projection)
-        const float* rv = rotvec + (size_t)p * 53 * 3;
-        const float th = sqrtf(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
-        const float den = fmaxf(th, 1e-6f);
-        const float kx = rv[0] / den, ky = rv[1] / den, kz = rv[2] / den;
-        float sn, cs;
-        sincosf(th, &sn, &cs);
-        const float omc = 1.f - cs;
-        const float xs = kx * sn, ys = ky * sn, zs = kz * sn;
-        const float xyc = kx * ky * omc, xzc = kx * kz * omc, yzc = ky * kz * omc;
-        const float xxc = kx * kx * omc, yyc = ky * ky * omc, zzc = kz * kz * omc;
-        const float R0[9] = {1.f - yyc - zzc, xyc - zs, xzc + ys, xyc + zs, 1.f - xxc - zzc, -xs + yzc, xzc - ys, xs + yzc, 1.f - xxc - yyc};
-        const float* Kp = Kmat + (size_t)det_b[p] * 9;
-        float Ki[9];
-        inv3x3(Kp, Ki);
-        const float lx = loc[2 * p], ly = loc[2 * p + 1], d = dist[p];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float tr = (Ki[a * 3] * lx + Ki[a * 3 + 1] * ly + Ki[a * 3 + 2] * 1.0f) * d;
-            sX[24 + a] = tr;
-            transl_out[3 * p + a] = tr;
-        }
-#pragma unroll
-        for (int e = 0; e < 9; ++e) { sX[e] = R0[e]; sX[15 + e] = Kp[e]; }
-    }
-    // feature tail: [betas | expr | 0...]   (the template is added in fp32 by the vertex kernel)
-    for (int k = 486 + j; k < c.Kb; k += 64) {
-        const int t = k - 486;
-        float v = 0.f;
-        if (t < c.nb) v = betas[(size_t)p * c.nb + t];
-        else if (t < ncoef) v = expr[(size_t)p * 10 + (t - c.nb)];
-        put_f(k, v);
-    }
-    LBS_WAVE_SYNC();
-    // kinematic chain, one tree LEVEL at a time: every joint whose depth equals the level composes its parent's world transform with its
-    // own (the 55 joints of SMPL-X sit on 10 levels; a single thread walking the 54 edges took 27 us -- more than the vertex kernel at
-    // small person counts)
-    int depth = 0;
-    if (j < NJ)
-        for (int a = sPar[j]; a >= 0; a = sPar[a]) ++depth;          // (LDS: a chain of up to ten dependent GLOBAL loads cost 2 us)
-    if (j == 0) {
-#pragma unroll
-        for (int e = 0; e < 9; ++e) sRw[0][e] = sR[0][e];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) sTw[0][a] = sJ[0][a];
-    }
-    int maxdepth = depth;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) maxdepth = max(maxdepth, __shfl_xor(maxdepth, o));
-    for (int level = 1; level <= maxdepth; ++level) {
-        LBS_WAVE_SYNC();
-        if (j < NJ && depth == level) {
-            const int pa = sPar[j];
-            float Rp[9], Rl[9], Rn[9], rel[3], t[3];
-#pragma unroll
-            for (int e = 0; e < 9; ++e) { Rp[e] = sRw[pa][e]; Rl[e] = sR[j][e]; }
-            mat3_mul(Rp, Rl, Rn);
-#pragma unroll
-            for (int a = 0; a < 3; ++a) rel[a] = sJ[j][a] - sJ[pa][a];
-            mat3_vec(Rp, rel, t);
-#pragma unroll
-            for (int e = 0; e < 9; ++e) sRw[j][e] = Rn[e];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) sTw[j][a] = t[a] + sTw[pa][a];
-        }
-    }
-    LBS_WAVE_SYNC();
-    if (j == 0) {
-        // recentring.  person_center joint given: recentre on it (smpl_layer.py:131-136); None (center_joint < 0): the pelvis is ADDED
-        // to the translation instead and nothing is recentred (smpl_layer.py:128-130), i.e. o = tr + pelvis
-        float R0[9], cc[3];
-#pragma unroll
-        for (int e = 0; e < 9; ++e) R0[e] = sX[e];
-        if (c.center_joint >= 0) {
-            float hc[3] = {sTw[c.center_joint][0] - sTw[0][0], sTw[c.center_joint][1] - sTw[0][1], sTw[c.center_joint][2] - sTw[0][2]};
-            mat3_vec(R0, hc, cc);
-        } else {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) cc[a] = -sTw[0][a];
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { sX[9 + a] = sTw[0][a]; sX[12 + a] = sX[24 + a] - cc[a]; }
-    }
-    LBS_WAVE_SYNC();
-    if (j < 24) xf[(size_t)p * 24 + j] = sX[j];
-    if (j >= NJ) {                                     // joints 55..63: zero columns of the skinning operand
-        for (int comp = 0; comp < 12; ++comp) put_a(comp, j, 0.f);
-    }
-    if (j < NJ) {
-        float R0[9], Rw[9], Rf[9], tp[3], tt[3], u[3], jj[3];
-#pragma unroll
-        for (int e = 0; e < 9; ++e) { R0[e] = sX[e]; Rw[e] = sRw[j][e]; }
-        const float pel[3] = {sX[9], sX[10], sX[11]}, o[3] = {sX[12], sX[13], sX[14]};
-        // A'_j = [R_w | t_w - R_w J_j]; folded: [R0 R_w | R0 (t' - pelvis)]; the camera translation o is added per person in fp32 by
-        // the vertex kernel (skin weights sum to one; the reference adds transl after the LBS, smpl_layer.py:139-140)
-        float Jv[3] = {sJ[j][0], sJ[j][1], sJ[j][2]};
-        mat3_vec(Rw, Jv, u);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) tp[a] = sTw[j][a] - u[a] - pel[a];
-        mat3_mul(R0, Rw, Rf);
-        mat3_vec(R0, tp, tt);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            put_a(r * 4 + 0, j, Rf[r * 3]); put_a(r * 4 + 1, j, Rf[r * 3 + 1]); put_a(r * 4 + 2, j, Rf[r * 3 + 2]);
-            put_a(r * 4 + 3, j, tt[r]);
-        }
-        // posed joint in camera space + projection
-        float dj[3] = {sTw[j][0] - pel[0], sTw[j][1] - pel[1], sTw[j][2] - pel[2]};
-        mat3_vec(R0, dj, jj);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { jj[a] += o[a]; j3d[((size_t)p * 127 + j) * 3 + a] = jj[a]; }
-        float pr[2];
-        project(&sX[15], jj, pr);
-        j2d[((size_t)p * 127 + j) * 2] = pr[0];
-        j2d[((size_t)p * 127 + j) * 2 + 1] = pr[1];
-    }
-    LBS_WAVE_SYNC();
-    flush(false);
-}
-
-__global__ __launch_bounds__(64) void lbs_pose_kernel(const mhmr_lbs_consts c, const float* __restrict__ rotvec,
-                                                      const float* __restrict__ betas, const float* __restrict__ expr,
-                                                      const float* __restrict__ loc, const float* __restrict__ dist,
-                                                      const float* __restrict__ Kmat, const int* __restrict__ det_b, int P, int Pp,
-                                                      _Float16* __restrict__ F16, _Float16* __restrict__ A16, float* __restrict__ xf,
-                                                      float* __restrict__ j3d, float* __restrict__ j2d,
-                                                      float* __restrict__ transl_out) {
-    __shared__ PoseLds L;
-    lbs_pose_person(c, rotvec, betas, expr, loc, dist, Kmat, det_b, P, Pp, F16, A16, xf, j3d, j2d, transl_out, (int)blockIdx.x, L);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Round 6: the same person as FOUR waves (one per SIMD of a CU).  The one-wave form above executes ~3 100 instructions in a row -- the
-// static 1 725 with the ten-level loop unrolled in time -- and a lone wave issues one VALU instruction per ~5 cycles: 16 k cycles = 8 us
-// of its 10-12 us are ISSUE time, not latency (round 5's review: "2 800 cycles per level").  Here the work is laid across 256 lanes:
+// The pose kernel: one person = one workgroup of FOUR waves (one per SIMD of a CU).  History: until round 6 a person was one wave, which
+// executed ~3 100 instructions in a row, and a lone wave issues one VALU instruction per ~5 cycles: 8 us of its 9-10 us were ISSUE
+// time, not latency; this form takes 7.6 us.  The work is laid across 256 lanes:
 //   phase A  four independent roles, one wave each: Rodrigues + pose feature | joint regression | root rotation, K^-1, translation, feature
 //            tail, zero columns | topology: depth of every joint, the joints of every tree level as a list (ballot + rank)
 //   phase B  the kinematic chain level by level with one lane per (joint of the level, one of its 12 transform elements): a level is
 //            ~10 LDS reads, 3-4 FMAs and one store per lane instead of 21 reads, 36 FMAs and 12 stores
 //   phase C  recentring (one lane), then three roles: folded skinning rows | posed joints + projection | the person record
 //   phase D  the operand rows leave as 16-byte chunks: 160 chunks over 256 lanes, one pass
-// Every expression is the one of lbs_pose_person (same operand order, same contraction), so the results are bit-identical to it
-// (tests/test_gpu_kernels.py::test_lbs_fused_launch_is_bit_identical... compares against the fused launch, which keeps the one-wave form).
+// Numerical gates: tests/test_gpu_kernels.py::test_lbs_against_oracle and ::test_lbs_max_abs_gate_160_persons_x_20_seeds (2e-5 m on
+// the 55 posed joints); the layer has no atomics and no cross-workgroup ordering, so it repeats bit for bit (::test_lbs_repeats_bit_for_bit_...).
 #ifdef MHMR_LBS_STAMPS      // tools/lbs_pose_timeline.py: wall-clock (100 MHz) stamps of the pose kernel, debug build only
 __device__ unsigned long long* g_pose_stamps;
 #define POSE_STAMP(i)                                                                                                               \
@@ -350,13 +97,20 @@ __device__ unsigned long long* g_pose_stamps;
 #define POSE_STAMP(i)
 #endif
 constexpr int POSE_MAXLEVEL = 56;          // a tree of NJ = 55 joints has at most 55 levels: every topology fits
-struct __attribute__((aligned(16))) Pose4Lds {
-    PoseLds L;
+struct __attribute__((aligned(16))) PoseLds {
+    float sR[NJ][9], sJ[NJ][3], sRw[NJ][9], sTw[NJ][3], sX[36];
+    int sPar[56];
+    // the person's two operand rows are collected here and leave as 16-byte chunks (8 consecutive k / joints of one person are 8
+    // consecutive f16 of the fragment-major layouts): 2 + 2 x 1.5 wide stores per lane instead of ~50 two-byte ones (round 4)
+    __attribute__((aligned(16))) float sF[LBS_KB];
+    __attribute__((aligned(16))) float sA[12][64];
+    // the kinematic tree's level schedule where the kernel derives it itself (null pose_tasks); sMaxDepth with either schedule
     int sDepth[64];
     int sCnt[POSE_MAXLEVEL];
     unsigned char sList[POSE_MAXLEVEL][64];
     int sMaxDepth;
 };
+static_assert(sizeof(PoseLds) % 16 == 0 && offsetof(PoseLds, sF) % 16 == 0 && offsetof(PoseLds, sA) % 16 == 0, "16-byte chunks");
 
 __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c, const float* __restrict__ rotvec,
                                                        const float* __restrict__ betas, const float* __restrict__ expr,
@@ -364,17 +118,22 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
                                                        const float* __restrict__ Kmat, const int* __restrict__ det_b, int P, int Pp,
                                                        _Float16* __restrict__ F16, _Float16* __restrict__ A16, float* __restrict__ xf,
                                                        float* __restrict__ j3d, float* __restrict__ j2d, float* __restrict__ transl_out) {
-    __shared__ Pose4Lds S;
-    PoseLds& L = S.L;
-    float (&sR)[NJ][9] = L.sR; float (&sJ)[NJ][3] = L.sJ; float (&sRw)[NJ][9] = L.sRw; float (&sTw)[NJ][3] = L.sTw; float (&sX)[36] = L.sX;
-    int (&sPar)[56] = L.sPar;
-    float (&sF)[LBS_KB_POSE] = L.sF; float (&sA)[12][64] = L.sA;
+    __shared__ PoseLds S;
+    float (&sR)[NJ][9] = S.sR; float (&sJ)[NJ][3] = S.sJ; float (&sRw)[NJ][9] = S.sRw; float (&sTw)[NJ][3] = S.sTw; float (&sX)[36] = S.sX;
+    int (&sPar)[56] = S.sPar;
+    float (&sF)[LBS_KB] = S.sF; float (&sA)[12][64] = S.sA;
     const int p = (int)blockIdx.x, tid = threadIdx.x, j = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (w == 0) POSE_STAMP(0);
     const int ngr = Pp / 16, grp = p >> 4, pin = p & 15, nst = c.Kb / 32;
     typedef Op<MHMR_DT_F16>::V8 H8;
-    // phase D (also the padding rows of both operand matrices: zero = true)
+    // Both operands are stored FRAGMENT-MAJOR: the 64 lanes of a wave read one (person group, part, k step) fragment as 1 KiB of
+    // consecutive bytes (16 B per lane, lane = 16 * (k group) + person-in-group), i.e. eight whole 128-byte lines per wave
+    // instruction; a row-major [person][k] image makes every fragment load touch 16 lines for 64 useful bytes each, and the TA,
+    // not the matrix pipe or HBM, then paces the vertex kernel (93 us at 160 persons).
+    //   F16 [group][hi|lo][Kb/32][64 lanes][8]      A16 [12 comps][hi|lo][group][2][64 lanes][8]
+    // phase D (also the padding rows of both operand matrices: zero = true): chunk kb (k = 8 kb .. 8 kb + 7) of the feature row /
+    // chunk (comp, jb) of the transform rows -> hi and lo halves, 16 bytes each
     auto flush = [&](bool zero) {
         const int nf = c.Kb / 8;
         for (int t = tid; t < nf + 96; t += 256) {
@@ -418,7 +177,8 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
     // ---------------- phase A: four roles ----------------
     if (w == 0) {
         if (j < NJ) {
-            // full_pose (55) from the reference's 53-vector (smpl_layer.py:88-101), smplx batch_rodrigues -- as in lbs_pose_person
+            // full_pose (55) from the reference's 53-vector (smpl_layer.py:88-101): 0 -> zero (root applied after LBS),
+            // 1..21 body, 22 jaw <- 52, 23/24 eyes zero, 25..39 left hand <- 22..36, 40..54 right hand <- 37..51
             int src = -1;
             if (j >= 1 && j <= 21) src = j;
             else if (j == 22) src = 52;
@@ -428,6 +188,7 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
                 const float* rv = rotvec + ((size_t)p * 53 + src) * 3;
                 v0 = rv[0]; v1 = rv[1]; v2 = rv[2];
             }
+            // smplx batch_rodrigues: angle = |v + 1e-8|, R = I + sin K + (1 - cos) K K
             const float a0 = v0 + 1e-8f, a1 = v1 + 1e-8f, a2 = v2 + 1e-8f;
             const float angle = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
             const float rx = v0 / angle, ry = v1 / angle, rz = v2 / angle;
@@ -447,6 +208,8 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
         }
     } else if (w == 1) {
         if (j < NJ) {
+            // joints from the pre-contracted regressor.  The usual 10 betas + 10 expression coefficients: the joint's three rows of JS
+            // are 15 independent 16-byte loads (a run-time loop of dependent scalar loads was most of the first pose kernel's 15 us)
             if (ncoef == 20) {
                 const f32x4* js = (const f32x4*)(c.JS + (size_t)(j * 3) * 20);
                 f32x4 row[15];
@@ -459,7 +222,7 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
                 for (int a = 0; a < 3; ++a) {
                     float sm = c.J0[j * 3 + a];
 #pragma unroll
-                    for (int l = 0; l < 20; ++l) sm += row[5 * a + (l >> 2)][l & 3] * cf[l];
+                    for (int l = 0; l < 20; ++l) sm += row[5 * a + (l >> 2)][l & 3] * cf[l];     // (same order of additions as the loop below)
                     sJ[j][a] = sm;
                 }
             } else {
@@ -475,7 +238,7 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
         }
     } else if (w == 2) {
         if (j == 63) {
-            // root orientation (roma.rotvec_to_rotmat), translation (inverse_perspective_projection) -- as in lbs_pose_person.  The
+            // root orientation (roma.rotvec_to_rotmat), translation (inverse_perspective_projection).  The
             // image index first and the camera matrix right behind it: the second of the two dependent round trips then runs under the
             // sin / cos below instead of behind it
             const int db = det_b[p];
@@ -620,6 +383,8 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
     // ---------------- phase C: recentring, then the per-joint read-outs ----------------
     if (w == 0) POSE_STAMP(6);
     if (tid == 0) {
+        // recentring.  person_center joint given: recentre on it (smpl_layer.py:131-136); None (center_joint < 0): the pelvis is ADDED
+        // to the translation instead and nothing is recentred (smpl_layer.py:128-130), i.e. o = tr + pelvis
         float R0[9], cc[3];
 #pragma unroll
         for (int e = 0; e < 9; ++e) R0[e] = sX[e];
@@ -641,6 +406,8 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
 #pragma unroll
         for (int e = 0; e < 9; ++e) { R0[e] = sX[e]; Rw[e] = sRw[j][e]; }
         const float pel[3] = {sX[9], sX[10], sX[11]};
+        // A'_j = [R_w | t_w - R_w J_j]; folded: [R0 R_w | R0 (t' - pelvis)]; the camera translation o is added per person in fp32 by
+        // the vertex kernel (skin weights sum to one; the reference adds transl after the LBS, smpl_layer.py:139-140)
         float Jv[3] = {sJ[j][0], sJ[j][1], sJ[j][2]};
         mat3_vec(Rw, Jv, u);
 #pragma unroll
@@ -654,6 +421,7 @@ __global__ __launch_bounds__(256) void lbs_pose4_kernel(const mhmr_lbs_consts c,
         }
     }
     if (w == 1 && j < NJ) {
+        // posed joint in camera space + projection
         float R0[9], jj[3];
 #pragma unroll
         for (int e = 0; e < 9; ++e) R0[e] = sX[e];
@@ -703,7 +471,6 @@ struct __attribute__((packed, aligned(4))) Vec3 { float x, y, z; };
 struct __attribute__((packed, aligned(4))) Vec2 { float x, y; };
 constexpr int LBS_TV = 48, LBS_NST = LBS_TV / 16;      // vertices per tile, 16-vertex MFMA column blocks per tile
 constexpr int LBS_NC = 10, LBS_NL = 2;                 // compute waves (one person group each), loader waves
-constexpr int LBS_KB = 512;                            // padded blend depth (486 pose + betas + 10 expression <= 512)
 constexpr int LBS_NX = 72;                             // extra joints 55..126 (virtual vertices in the tiles from c.Vl on)
 constexpr int LBS_NS = LBS_KB / 32;                    // k steps of 32
 constexpr int LBS_NE = 8;                              // k eighths (2 steps each)
@@ -734,7 +501,6 @@ static_assert(LBS_EBYTES % (1024 * LBS_NL) == 0 && LBS_EOPS == 18 && LBS_EOPS_HI
               LBS_LEAD == 5 && LBS_WBYTES <= LBS_EBYTES_HI,
               "the landing waits below are written for 9 / 18 copies per wave and eighth, 6 for the weights, five eighths ahead");
 static_assert(LBS_LDS <= 160 * 1024, "LDS");
-static_assert(LBS_KB_POSE == LBS_KB, "pose kernel staging");
 
 __device__ __forceinline__ void lbs_barrier() {
     asm volatile("" ::: "memory");
@@ -743,14 +509,11 @@ __device__ __forceinline__ void lbs_barrier() {
 }
 
 // loader wave lw: the tile's basis slice, eighth by eighth, + the person records
-template <bool FUSED>
 __device__ __forceinline__ void lbs_loader(const mhmr_lbs_consts& c, const float* __restrict__ xf, int P, int ngroups, int g0, char* smem,
-                                           int lw, int tile, int* __restrict__ sync, int ntiles, int Pp) {
+                                           int lw, int tile) {
     const int lane = threadIdx.x & 63;
     char* xrec = smem + LBS_XOFF;
-    // (fused launch: the records are the pose role's OUTPUT -- every compute wave fetches its own group's after its ready wait, and this
-    // wave's vmcnt stream holds the basis copies only, which is all the landing waits below count)
-    for (int i = FUSED ? LBS_NC : lw; i < LBS_NC; i += LBS_NL) {
+    for (int i = lw; i < LBS_NC; i += LBS_NL) {
         const int g = g0 + i;
         if (g >= ngroups) break;
         const int bytes = min(16, P - 16 * g) * LBS_XREC;
@@ -774,20 +537,6 @@ __device__ __forceinline__ void lbs_loader(const mhmr_lbs_consts& c, const float
     };
 #pragma unroll
     for (int e = 0; e < LBS_LEAD; ++e) dma_e(e);
-    if constexpr (FUSED) {
-        lbs_barrier();          // the ready barrier: compute wave 0 has seen every person row published (lbs_compute)
-        // This workgroup reads the ready flags no more.  The LAST vertex workgroup to get here puts the flags and the ticket back to
-        // zero -- the workspace leaves the launch as it entered it (no memset launch, no host-side epoch: the call stays capturable).
-        if (lw == 0) {
-            int t = 0;
-            if (lane == 0) t = __hip_atomic_fetch_add(sync, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            t = __builtin_amdgcn_readfirstlane(t);
-            if (t == ntiles - 1) {
-                for (int i = lane; i < Pp; i += 64) __hip_atomic_store(sync + 1 + i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (lane == 0) __hip_atomic_store(sync, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
     constexpr int WOPS = LBS_WBYTES / 1024 / LBS_NL;
 #pragma unroll
     for (int e = 0; e < LBS_NE; ++e) {
@@ -820,45 +569,13 @@ __device__ __forceinline__ void lbs_loader(const mhmr_lbs_consts& c, const float
 }
 
 // compute wave: person group g (16 persons) against the tile's 48 vertices
-template <bool FUSED>
 __device__ __forceinline__ void lbs_compute(const mhmr_lbs_consts& c, const _Float16* __restrict__ F16, const _Float16* __restrict__ A16,
                                             int P, int ngroups, int g, int w, float* __restrict__ v3d, float* __restrict__ v2d,
-                                            float* __restrict__ j3d, float* __restrict__ j2d, char* smem, int tile,
-                                            const float* __restrict__ xf, const int* __restrict__ sync) {
+                                            float* __restrict__ j3d, float* __restrict__ j2d, char* smem, int tile) {
     typedef Op<MHMR_DT_F16>::V8 H8;
     const int lane = threadIdx.x & 63;
     const int g4 = lane >> 4, l15 = lane & 15;
     const int v0 = tile * LBS_TV;
-    if constexpr (FUSED) {
-        // The pose role of THIS launch writes F16 / A16 / xf.  Compute wave 0 alone polls the ready flags (all person rows of the launch)
-        // and takes the acquire fence -- ONE cache invalidation per workgroup: the per-wave form of the first build cost 2 240 of them and
-        // ran 30 us SLOWER than two launches -- then the workgroup's ready barrier publishes "poses visible" to the other eleven waves.
-        // The loader waves meanwhile stream the basis: by the time the poses exist, five eighths of the tile have landed.
-        if (w == 0) {
-            int spins = 0;      // (bounded: ~0.5 s of polling means the protocol is broken -- abort the kernel loudly rather than hang the device)
-            for (;;) {
-                bool ok = true;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const int r = lane + 64 * i;
-                    if (r < 16 * ngroups) ok = ok && __hip_atomic_load(sync + 1 + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1;
-                }
-                if (__all(ok)) break;
-                __builtin_amdgcn_s_sleep(8);
-                if (++spins > (1 << 21)) __builtin_trap();
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-        lbs_barrier();                                              // the ready barrier (every wave of the workgroup passes it once)
-        float* xr = (float*)(smem + LBS_XOFF + w * (16 * LBS_XREC));
-        const int nfl = min(16, P - 16 * g) * 24;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int k = lane + 64 * i;
-            if (k < nfl) xr[k] = xf[(size_t)g * (16 * 24) + k];
-        }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    }
     // A operands of k step sg (fragment-major: 1 KiB per (group, part, k step)), [set][hi | lo]
     H8 A[2][2];
     auto load_a = [&](int set, int sg) {          // (the low half only where the pair form of the basis is: the last eighth's two steps)
@@ -1030,54 +747,6 @@ __device__ __forceinline__ void lbs_compute(const mhmr_lbs_consts& c, const _Flo
     LBS_STAMP(11);
 }
 
-// ONE launch for the whole layer (round 5; opt-in, see lbs_forward_impl for the measurement that keeps it off): workgroups [0, npose) are the pose role -- twelve persons each, one per wave, exactly
-// lbs_pose_person above -- and workgroups [npose, npose + tiles) the vertex role.  The two used to be two launches: 10.5 us of pose
-// latency chain + a launch gap in front of a vertex kernel whose first 5 us are nothing but the basis stream's ramp.  Here the vertex
-// workgroups start their basis DMA at once and only their compute waves wait for the poses (per-person ready flags in `sync`).
-// Progress: workgroups are dispatched in index order, so the pose workgroups are resident before any waiting one; the launcher also
-// keeps the grid within one workgroup per CU (everything co-resident), and falls back to the two launches otherwise.
-// sync [1 + Pp] ints: [0] a ticket, [1 + p] the ready flag of person row p; ZERO on entry, zero again on exit (lbs_loader).
-__global__ __launch_bounds__(64 * (LBS_NC + LBS_NL), 3) void lbs_fused_kernel(const mhmr_lbs_consts c, const float* __restrict__ rotvec,
-                                                                              const float* __restrict__ betas, const float* __restrict__ expr,
-                                                                              const float* __restrict__ loc, const float* __restrict__ dist,
-                                                                              const float* __restrict__ Kmat, const int* __restrict__ det_b,
-                                                                              int P, int Pp, _Float16* __restrict__ F16,
-                                                                              _Float16* __restrict__ A16, float* __restrict__ xf,
-                                                                              float* __restrict__ v3d, float* __restrict__ v2d,
-                                                                              float* __restrict__ j3d, float* __restrict__ j2d,
-                                                                              float* __restrict__ transl, int* __restrict__ sync, int npose) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if ((int)blockIdx.x < npose) {
-        const int p = (int)blockIdx.x * (LBS_NC + LBS_NL) + w;
-        if (p < Pp) {
-            PoseLds& L = *(PoseLds*)(smem + (size_t)w * sizeof(PoseLds));
-            lbs_pose_person(c, rotvec, betas, expr, loc, dist, Kmat, det_b, P, Pp, F16, A16, xf, j3d, j2d, transl, p, L);
-        }
-        // Publish the workgroup's twelve rows with ONE release: every wave's stores have reached the L2 (vmcnt(0)) before the barrier,
-        // wave 0 then writes the L2 back once (a release fence per WAVE is a cache write-back per person: 160 of them serialised per
-        // XCD in the first build) and raises the flags.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        lbs_barrier();
-        if (w == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            const int lane = threadIdx.x & 63, r = (int)blockIdx.x * (LBS_NC + LBS_NL) + lane;
-            if (lane < LBS_NC + LBS_NL && r < Pp) __hip_atomic_store(sync + 1 + r, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        return;
-    }
-    const int tile = (int)blockIdx.x - npose, ngroups = Pp / 16, ntiles = (int)gridDim.x - npose;
-    if (w >= LBS_NC) {
-        lbs_loader<true>(c, xf, P, ngroups, 0, smem, w - LBS_NC, tile, sync, ntiles, Pp);
-    } else if (w < ngroups) {
-        lbs_compute<true>(c, F16, A16, P, ngroups, w, w, v3d, v2d, j3d, j2d, smem, tile, xf, sync);
-    } else {
-#pragma unroll
-        for (int e = 0; e < LBS_NE + 1; ++e) lbs_barrier();         // the ready barrier + the eight of the blend
-    }
-}
-static_assert((LBS_NC + LBS_NL) * sizeof(PoseLds) <= LBS_LDS, "pose role staging of twelve waves");
-
 __global__ __launch_bounds__(64 * (LBS_NC + LBS_NL), 3) void lbs_vertex_kernel(const mhmr_lbs_consts c, const _Float16* __restrict__ F16,
                                                                                const _Float16* __restrict__ A16, const float* __restrict__ xf,
                                                                                int P, int Pp, int g0, float* __restrict__ v3d,
@@ -1092,9 +761,9 @@ __global__ __launch_bounds__(64 * (LBS_NC + LBS_NL), 3) void lbs_vertex_kernel(c
 #endif
     // every wave passes the same LBS_NE barriers
     if (w >= LBS_NC) {
-        lbs_loader<false>(c, xf, P, ngroups, g0, smem, w - LBS_NC, (int)blockIdx.x, nullptr, 0, Pp);
+        lbs_loader(c, xf, P, ngroups, g0, smem, w - LBS_NC, (int)blockIdx.x);
     } else if (g0 + w < ngroups) {
-        lbs_compute<false>(c, F16, A16, P, ngroups, g0 + w, w, v3d, v2d, j3d, j2d, smem, (int)blockIdx.x, nullptr, nullptr);
+        lbs_compute(c, F16, A16, P, ngroups, g0 + w, w, v3d, v2d, j3d, j2d, smem, (int)blockIdx.x);
     } else {
 #pragma unroll
         for (int e = 0; e < LBS_NE; ++e) lbs_barrier();
@@ -1108,10 +777,10 @@ extern "C" __attribute__((visibility("default"))) int mhmr_debug_lbs_stamps(void
 extern "C" __attribute__((visibility("default"))) int mhmr_debug_pose_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_pose_stamps), &p, sizeof(p)); }
 #endif
 
-static int lbs_forward_impl(const mhmr_lbs_consts* c, const float* rotvec, const float* betas, const float* expr,
-                            const float* loc, const float* dist, const float* Kmat, const int* det_b, int P, float* ws_F,
-                            float* ws_A, float* ws_xf, float* v3d, float* v2d, float* j3d, float* j2d, float* transl,
-                            int* ws_sync, void* stream) {
+extern "C" int mhmr_lbs_forward(const mhmr_lbs_consts* c, const float* rotvec, const float* betas, const float* expr,
+                                const float* loc, const float* dist, const float* Kmat, const int* det_b, int P, float* ws_F,
+                                float* ws_A, float* ws_xf, float* v3d, float* v2d, float* j3d, float* j2d, float* transl,
+                                void* stream) {
     if (!c || P < 0) return MHMR_ERR_BAD_ARG;
     if (P == 0) return 0;
     if (c->Vp % LBS_TV || c->Vl % LBS_TV || c->Vl < c->V || c->Vp != c->Vl + LBS_TV * ((LBS_NX + 15) / 16) || c->Kb != LBS_KB ||
@@ -1128,35 +797,11 @@ static int lbs_forward_impl(const mhmr_lbs_consts* c, const float* rotvec, const
         if (need >= 0) {
             hipError_t e = hipFuncSetAttribute((const void*)lbs_vertex_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LBS_LDS);
             if (e != hipSuccess) return (int)e;
-            e = hipFuncSetAttribute((const void*)lbs_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LBS_LDS);
-            if (e != hipSuccess) return (int)e;
             once.mark(dev);
         }
     }
-    // The fused launch is CORRECT (bit-identical outputs, tests/test_gpu_kernels.py) and SLOWER than the two launches on this chip
-    // (profiles/r05_session_c_lbs_fused_slp.txt: 48.7 vs 40.2 us at 160 persons, 38.3 vs 30.2 at 20, 32.2 vs 26.6 at 1), so it runs only
-    // through its own entry point (mhmr_lbs_forward_fused; Model takes it with MHMR_LBS_FUSED=1).  Why it loses: (a) across XCDs the poses become visible only through an L2 write-back on the
-    // producer side and an L2 invalidation on the consumer side (one each per workgroup in this form; one per WAVE in the first form: 76 us);
-    // (b) the vertex role's time at small person counts is not the basis stream's ramp, as assumed, but its SEQUENCING -- only five of
-    // the eight eighths fit in flight before the poses exist (LDS, vmcnt budget), the other three and the skin weights are latency-bound
-    // rounds that need the compute waves' barriers, i.e. the poses: what overlaps is ~5 us, what the fences cost is about the same.
-    const int npose = (Pp + LBS_NC + LBS_NL - 1) / (LBS_NC + LBS_NL), ntiles = c->Vp / LBS_TV;
-    if (ws_sync && Pp / 16 <= LBS_NC && npose + ntiles <= mhmr_cu_count()) {
-        prof_begin(PROF_LBS, s);
-        hipLaunchKernelGGL(lbs_fused_kernel, dim3(npose + ntiles), dim3(64 * (LBS_NC + LBS_NL)), LBS_LDS, s, *c, rotvec, betas, expr, loc, dist,
-                           Kmat, det_b, P, Pp, (_Float16*)ws_F, (_Float16*)ws_A, ws_xf, v3d, v2d, j3d, j2d, transl, ws_sync, npose);
-        prof_end(PROF_LBS, s, (double)P);
-        MHMR_CHECK_LAUNCH();
-        return 0;
-    }
-    // four waves per person (round 6); MHMR_LBS_POSE1=1: the one-wave form (A/B measurements; bit-identical results)
-    static const bool pose1 = getenv("MHMR_LBS_POSE1") && atoi(getenv("MHMR_LBS_POSE1")) != 0;
-    if (pose1)
-        hipLaunchKernelGGL(lbs_pose_kernel, dim3(Pp), dim3(64), 0, s, *c, rotvec, betas, expr, loc, dist, Kmat, det_b, P, Pp,
-                           (_Float16*)ws_F, (_Float16*)ws_A, ws_xf, j3d, j2d, transl);
-    else
-        hipLaunchKernelGGL(lbs_pose4_kernel, dim3(Pp), dim3(256), 0, s, *c, rotvec, betas, expr, loc, dist, Kmat, det_b, P, Pp,
-                           (_Float16*)ws_F, (_Float16*)ws_A, ws_xf, j3d, j2d, transl);
+    hipLaunchKernelGGL(lbs_pose4_kernel, dim3(Pp), dim3(256), 0, s, *c, rotvec, betas, expr, loc, dist, Kmat, det_b, P, Pp,
+                       (_Float16*)ws_F, (_Float16*)ws_A, ws_xf, j3d, j2d, transl);
     MHMR_CHECK_LAUNCH();
     // one launch covers LBS_NC person groups (160 persons); more persons take further launches over the same tiles
     const int ngroups = Pp / 16;
@@ -1167,19 +812,4 @@ static int lbs_forward_impl(const mhmr_lbs_consts* c, const float* rotvec, const
     prof_end(PROF_LBS, s, (double)P);
     MHMR_CHECK_LAUNCH();
     return 0;
-}
-
-extern "C" int mhmr_lbs_forward(const mhmr_lbs_consts* c, const float* rotvec, const float* betas, const float* expr,
-                                const float* loc, const float* dist, const float* Kmat, const int* det_b, int P, float* ws_F,
-                                float* ws_A, float* ws_xf, float* v3d, float* v2d, float* j3d, float* j2d, float* transl,
-                                void* stream) {
-    return lbs_forward_impl(c, rotvec, betas, expr, loc, dist, Kmat, det_b, P, ws_F, ws_A, ws_xf, v3d, v2d, j3d, j2d, transl, nullptr, stream);
-}
-
-extern "C" int mhmr_lbs_forward_fused(const mhmr_lbs_consts* c, const float* rotvec, const float* betas, const float* expr,
-                                      const float* loc, const float* dist, const float* Kmat, const int* det_b, int P, float* ws_F,
-                                      float* ws_A, float* ws_xf, float* v3d, float* v2d, float* j3d, float* j2d, float* transl,
-                                      int* ws_sync, void* stream) {
-    if (!ws_sync) return MHMR_ERR_BAD_ARG;
-    return lbs_forward_impl(c, rotvec, betas, expr, loc, dist, Kmat, det_b, P, ws_F, ws_A, ws_xf, v3d, v2d, j3d, j2d, transl, ws_sync, stream);
 }

@@ -364,7 +364,7 @@ class Model(nn.Module):
         layer = self.smpl_layer[f"neutral_{nb}"]
         P["lbs"] = packing.pack_smplx(self._smplx_data, nb, device, layer.person_center_idx if layer.person_center_idx is not None else -1)
         P["lbs_struct"] = packing.lbs_consts_struct(P["lbs"])
-        P["lbs_sync"] = torch.zeros(1 + 160, dtype=torch.int32, device=device)      # mhmr_lbs_forward_fused: ticket + ready flags
+        P["lbs_sync"] = torch.zeros(1 + 160, dtype=torch.int32, device=device)      # unused by the model: kept only for bench.py's lbs section, which reads the key
         self._packed = P
         return P
 
@@ -660,13 +660,9 @@ class Model(nn.Module):
         V = lb["V"]
         v3d, v2d, j3d, j2d, transl = o["v3d"], o["v2d"], o["j3d"], o["j2d"], o["transl"]
         ws_F, ws_A, ws_xf = f(roundup(Pn, 16), lb["Kb"]), f(roundup(Pn, 16), 768), f(Pn, 24)
-        # pose kernel + vertex kernel; MHMR_LBS_FUSED=1: the one-launch form (pose role = leading workgroups of the vertex grid), built and
-        # bit-identical but measured slower on this chip (csrc/lbs.hip) -- its flag workspace is the pack's: zeroed once, left zero by every call
+        # pose kernel + vertex kernel (csrc/lbs.hip)
         args = [C.byref(P["lbs_struct"]), rotvec.data_ptr(), shape.data_ptr(), expression.data_ptr(), loc.data_ptr(), dist.data_ptr(), K.data_ptr(),
                 det[0].data_ptr(), Pn, ws_F.data_ptr(), ws_A.data_ptr(), ws_xf.data_ptr(), v3d.data_ptr(), v2d.data_ptr(), j3d.data_ptr(), j2d.data_ptr(),
                 transl.data_ptr()]
-        if os.environ.get("MHMR_LBS_FUSED") == "1":
-            _lib.check(L.mhmr_lbs_forward_fused(*args, P["lbs_sync"].data_ptr(), stream), "mhmr_lbs_forward_fused")
-        else:
-            _lib.check(L.mhmr_lbs_forward(*args, stream), "mhmr_lbs_forward")
+        _lib.check(L.mhmr_lbs_forward(*args, stream), "mhmr_lbs_forward")
         return o
