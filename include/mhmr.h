@@ -537,6 +537,52 @@ typedef struct {
 int mhmr_body_forward(const mhmr_body_consts* c, const float* pose, const float* coef, const float* transl, const float* K, int G,
                       float* ws_F, float* ws_A, float* vertices, float* joints, float* v2d, float* j2d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Backward of mhmr_body_forward: cotangents of the outputs -> gradients of pose, coef and
+ * transl.  K and the model constants get no gradient.
+ *   saved from the forward of the SAME (c, G): its inputs pose, coef, transl, K and what it wrote: ws_F, ws_A,
+ *   vertices, joints;
+ *   cotangents g_vertices [G][V][3], g_joints [G][J + E + L][3], g_v2d [G][V][2], g_j2d [G][J + E + L][2]: any
+ *   may be NULL (= zero); the 2D ones need K;
+ *   outputs g_pose [G][J][3], g_coef [G][nc], g_transl [G][3]: any may be NULL (not wanted); g_transl needs transl.
+ * The picked-vertex joints and landmarks reach the vertices through mhmr_body_bwd_consts: their table inverted
+ * once at load time, CSR by vertex -- the entries of vertex v are inv_ptr[v] .. inv_ptr[v + 1], each an output
+ * joint (J <= joint < J + E + L) and its weight (1 for a picked vertex, the barycentric weight for a landmark
+ * corner), sorted by joint; n = E + 3 L entries.
+ * Two launches on `stream`, no allocation, no synchronisation, no floating-point atomic: sums over the 64 vertices
+ * of a tile are fp32 in a fixed tree, every sum above that is fp64 in an order that depends on (V, G) only, each
+ * output is rounded once.  Two calls give the same bits; a person's gradient does not depend on the other persons
+ * of the batch.  The pose gradient differentiates batch_rodrigues as the forward evaluates it (angle = |v + 1e-8|):
+ * a zero rotation vector is an ordinary input.
+ * Validated before any launch: d, c, a required pointer or the workspace NULL, G < 0, workspace_bytes too small,
+ * g_v2d / g_j2d without K, g_transl without transl, bc->n != E + 3 L -> MHMR_ERR_BAD_ARG; the shape limits of
+ * mhmr_body_forward -> MHMR_ERR_BAD_SHAPE; G == 0 launches nothing.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int n;                    /* E + 3 L                                                                              */
+    const int* inv_ptr;       /* [V + 1]                                                                              */
+    const int* inv_joint;     /* [n]                                                                                  */
+    const float* inv_w;       /* [n]                                                                                  */
+} mhmr_body_bwd_consts;
+
+typedef struct {
+    const mhmr_body_consts* c;
+    const mhmr_body_bwd_consts* bc;
+    int G;
+    const float *pose, *coef, *transl, *K;
+    const float *ws_F, *ws_A, *vertices, *joints;
+    const float *g_vertices, *g_joints, *g_v2d, *g_j2d;
+    float *g_pose, *g_coef, *g_transl;
+    void* workspace;
+    long long workspace_bytes;
+} mhmr_body_backward_desc;
+
+/* bytes of the fp64 partial sums mhmr_body_backward needs: a function of the shapes in c and of G only (the number
+ * of tile ranges per group of 8 persons grows when there are few groups); written before it is read.  A negative
+ * value is MHMR_ERR_BAD_ARG (c NULL, G < 0) or MHMR_ERR_BAD_SHAPE. */
+long long mhmr_body_backward_workspace_bytes(const mhmr_body_consts* c, int G);
+int mhmr_body_backward(const mhmr_body_backward_desc* d, void* stream);
+
 /* Sparse vertex regressor: out [M][R][3] = A . (in [M][Vin][3] - center [M][3]) for A in CSR form (rowptr [R + 1],
  * col, val); center NULL = none.  Each row is summed in the order of its entries (the loaders sort them by column) in
  * fp64 and rounded once: deterministic.  A row without entries gives zeros; an entry whose column is outside

@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -153,6 +153,18 @@ class BodyConsts(C.Structure):
                 [(n, _vp) for n in ("vtemp", "basis", "J0", "JS", "parents", "weights", "extra_idx", "lmk_idx", "lmk_bary")])
 
 
+class BodyBwdConsts(C.Structure):
+    """include/mhmr.h mhmr_body_bwd_consts."""
+    _fields_ = [("n", _i), ("inv_ptr", _vp), ("inv_joint", _vp), ("inv_w", _vp)]
+
+
+class BodyBackwardDesc(C.Structure):
+    """include/mhmr.h mhmr_body_backward_desc."""
+    _fields_ = ([("c", C.POINTER(BodyConsts)), ("bc", C.POINTER(BodyBwdConsts)), ("G", _i)] +
+                [(n, _vp) for n in ("pose", "coef", "transl", "K", "ws_F", "ws_A", "vertices", "joints", "g_vertices", "g_joints", "g_v2d",
+                                    "g_j2d", "g_pose", "g_coef", "g_transl", "workspace")] + [("workspace_bytes", C.c_longlong)])
+
+
 class PreImage(C.Structure):
     """include/mhmr.h mhmr_pre_image: one image of mhmr_preprocess_u8_batch (device pointers + the geometry of its plan)."""
     _fields_ = ([("img", _vp)] + [(n, _i) for n in ("H", "W", "ow", "oh", "y0", "rows", "pad_x", "pad_y", "ksh", "ksv")] +
@@ -217,6 +229,8 @@ _SIGS = {
     "mhmr_preprocess_u8_batch": ([C.POINTER(PreImage), _vp, _i, _i, _vp, _vp, _vp], _i),
     "mhmr_eval_mesh_errors": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),
     "mhmr_body_forward": ([C.POINTER(BodyConsts), _vp, _vp, _vp, _vp, _i] + [_vp] * 6 + [_vp], _i),
+    "mhmr_body_backward_workspace_bytes": ([C.POINTER(BodyConsts), _i], C.c_longlong),
+    "mhmr_body_backward": ([C.POINTER(BodyBackwardDesc), _vp], _i),
     "mhmr_sparse_regress": ([_ip, _ip, _fp, _i, _i, _fp, _fp, _i, _fp, _vp], _i),
     "mhmr_gt_targets": ([_fp, _i, _i, _fp, _ip, _i, _i, _i, _i, _f, _i] + [_vp] * 7 + [_vp], _i),
     "mhmr_project_points": ([_fp, _fp, _i, _i, _fp, _vp], _i),

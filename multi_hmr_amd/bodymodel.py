@@ -6,6 +6,7 @@
 There is no CPU path: calling a ``BodyModel`` with CPU tensors raises."""
 from __future__ import annotations
 
+import ctypes as C
 import os
 import pickle
 from types import SimpleNamespace
@@ -137,6 +138,37 @@ class BodyModel:
         self._packed[key] = p
         return p
 
+    def inverted_list(self):
+        """The picked-vertex joints and the landmark corners, inverted for the backward: CSR by vertex -> ``(ptr [V + 1], joint [n],
+        weight [n])`` with ``n = E + 3 L``; the entries of a vertex are sorted by output joint (a face that names a vertex twice keeps both
+        entries, in corner order), so the order in which a vertex sums what its joints send back is fixed by the model alone."""
+        V, J, E = self.num_vertices, self.num_joints, len(self.extra_joint_verts)
+        vert = np.concatenate([self.extra_joint_verts, self.lmk_vidx.reshape(-1)]).astype(np.int64)
+        joint = np.concatenate([J + np.arange(E), J + E + np.repeat(np.arange(len(self.lmk_vidx)), 3)]).astype(np.int64)
+        w = np.concatenate([np.ones(E, dtype=np.float32), self.lmk_bary.reshape(-1)]).astype(np.float32)
+        if vert.size and not (0 <= vert.min() and vert.max() < V):
+            raise ValueError("inverted list: a picked vertex or landmark corner lies outside the mesh")
+        if joint.size and not (J <= joint.min() and joint.max() < self.num_out_joints):
+            raise ValueError("inverted list: an output joint outside [J, J + E + L)")
+        order = np.lexsort((np.arange(vert.size), joint, vert))                   # by vertex, then joint, then corner
+        ptr = np.zeros(V + 1, dtype=np.int32)
+        np.cumsum(np.bincount(vert, minlength=V), out=ptr[1:])
+        return ptr, joint[order].astype(np.int32), w[order]
+
+    def _bwd_consts(self, device):
+        key = ("bwd", device.type, device.index)
+        if key not in self._packed:
+            ptr, joint, w = self.inverted_list()
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            p = dict(inv_ptr=t(ptr), inv_joint=t(joint), inv_w=t(w))
+            bc = _lib.BodyBwdConsts()
+            bc.n = int(joint.size)
+            for k, v in p.items():
+                setattr(bc, k, v.data_ptr() if v.numel() else None)
+            p["struct"] = bc
+            self._packed[key] = p
+        return self._packed[key]
+
     @property
     def basis_bytes(self) -> int:
         """Bytes of the blend basis one pass of the vertex kernel streams (the roofline's numerator, per 8 persons)."""
@@ -197,3 +229,88 @@ class BodyModel:
         return out
 
     forward = __call__
+
+    def differentiable(self, global_orient=None, body_pose=None, jaw_pose=None, leye_pose=None, reye_pose=None, left_hand_pose=None,
+                       right_hand_pose=None, betas=None, expression=None, transl=None, K=None, **unused):
+        """``__call__`` attached to autograd: the same keywords, the same namespace and bit for bit the same values, with gradients for
+        whichever of the pose, ``betas``, ``expression`` and ``transl`` tensors require them (``mhmr_body_backward``; once differentiable;
+        ``K`` gets none).  Assembling the full pose and the coefficient row stays ordinary torch."""
+        given = [t for t in (global_orient, body_pose, betas, transl, jaw_pose, left_hand_pose) if t is not None]
+        if not given:
+            raise ValueError("BodyModel needs at least one of global_orient, body_pose, betas, transl to know the batch")
+        dev = given[0].device
+        if dev.type != "cuda":
+            raise _lib.MhmrError("BodyModel runs on the HIP device only (no CPU fallback)")
+        G = int(given[0].shape[0])
+        if self.model_type == "smpl" and expression is not None:
+            raise TypeError("SMPL has no expression")
+        ne = self.num_expression_coeffs
+        pose = self.full_pose(G, dev, global_orient, body_pose, jaw_pose, leye_pose, reye_pose, left_hand_pose, right_hand_pose)
+        f = lambda t, n: (torch.zeros(G, n, device=dev) if t is None else t.to(device=dev, dtype=torch.float32).reshape(G, n))
+        coef = f(betas, self.num_betas)
+        if ne:
+            coef = torch.cat([coef, f(expression, ne)], dim=1)
+        tr = None if transl is None else transl.to(device=dev, dtype=torch.float32).reshape(G, 3)
+        Kc = None if K is None else K.detach().to(device=dev, dtype=torch.float32).reshape(G, 3, 3).contiguous()
+        res = _BodyFunction.apply(self, pose, coef, tr, Kc)
+        return SimpleNamespace(vertices=res[0], joints=res[1], v2d=res[2] if K is not None else None, j2d=res[3] if K is not None else None)
+
+
+class _BodyFunction(torch.autograd.Function):
+    """``mhmr_body_forward`` / ``mhmr_body_backward`` over (full pose, coef, transl).  The forward's workspaces and outputs are saved."""
+
+    @staticmethod
+    def forward(ctx, model, pose, coef, transl, K):
+        dev, G = pose.device, int(pose.shape[0])
+        pose, coef = pose.contiguous(), coef.contiguous()
+        transl = None if transl is None else transl.contiguous()
+        V, NJ, J = model.num_vertices, model.num_out_joints, model.num_joints
+        p = model._consts(dev)
+        vertices, joints = torch.empty(G, V, 3, device=dev), torch.empty(G, NJ, 3, device=dev)
+        v2d = torch.empty(G, V, 2, device=dev) if K is not None else None
+        j2d = torch.empty(G, NJ, 2, device=dev) if K is not None else None
+        ws_F = torch.empty(-(-G // PERSON_GROUP), p["K"], PERSON_GROUP, device=dev)
+        ws_A = torch.empty(G, J, 12, device=dev)
+        if G:
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().mhmr_body_forward(p["struct"], pose.data_ptr(), coef.data_ptr(), _lib.ptr(transl), _lib.ptr(K), G,
+                                                        ws_F.data_ptr(), ws_A.data_ptr(), vertices.data_ptr(), joints.data_ptr(), _lib.ptr(v2d),
+                                                        _lib.ptr(j2d), torch.cuda.current_stream(dev).cuda_stream), "mhmr_body_forward")
+        ctx.model, ctx.has_transl, ctx.has_K = model, transl is not None, K is not None
+        ctx.save_for_backward(pose, coef, transl, K, ws_F, ws_A, vertices, joints)
+        ctx.set_materialize_grads(False)
+        if K is None:                                            # autograd wants tensors: empty stand-ins the caller never sees
+            v2d, j2d = vertices.new_empty(0), vertices.new_empty(0)
+            ctx.mark_non_differentiable(v2d, j2d)
+        return vertices, joints, v2d, j2d
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_vertices, g_joints, g_v2d, g_j2d):
+        pose, coef, transl, K, ws_F, ws_A, vertices, joints = ctx.saved_tensors
+        model, dev, G = ctx.model, pose.device, int(pose.shape[0])
+        if not ctx.has_K:
+            g_v2d = g_j2d = None
+        cot = [None if t is None else t.to(dtype=torch.float32).contiguous() for t in (g_vertices, g_joints, g_v2d, g_j2d)]
+        need = ctx.needs_input_grad                                # (model, pose, coef, transl, K)
+        g_pose = torch.empty_like(pose) if need[1] else None
+        g_coef = torch.empty_like(coef) if need[2] else None
+        g_transl = torch.empty_like(transl) if ctx.has_transl and need[3] else None
+        if G and any(t is not None for t in (g_pose, g_coef, g_transl)):
+            p, pb = model._consts(dev), model._bwd_consts(dev)
+            lib = _lib.lib()
+            nbytes = int(lib.mhmr_body_backward_workspace_bytes(p["struct"], G))
+            if nbytes < 0:
+                _lib.check(nbytes, "mhmr_body_backward_workspace_bytes")
+            ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+            d = _lib.BodyBackwardDesc()
+            d.c, d.bc, d.G = C.pointer(p["struct"]), C.pointer(pb["struct"]), G
+            for name, t in (("pose", pose), ("coef", coef if coef.numel() else None), ("transl", transl), ("K", K), ("ws_F", ws_F), ("ws_A", ws_A),
+                            ("vertices", vertices), ("joints", joints), ("g_vertices", cot[0]), ("g_joints", cot[1]), ("g_v2d", cot[2]),
+                            ("g_j2d", cot[3]), ("g_pose", g_pose), ("g_coef", g_coef if coef.numel() else None), ("g_transl", g_transl),
+                            ("workspace", ws)):
+                setattr(d, name, _lib.ptr(t))
+            d.workspace_bytes = nbytes
+            with torch.cuda.device(dev):
+                _lib.check(lib.mhmr_body_backward(C.byref(d), torch.cuda.current_stream(dev).cuda_stream), "mhmr_body_backward")
+        return None, g_pose, g_coef, g_transl, None
