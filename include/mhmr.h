@@ -583,6 +583,71 @@ typedef struct {
 long long mhmr_body_backward_workspace_bytes(const mhmr_body_consts* c, int G);
 int mhmr_body_backward(const mhmr_body_backward_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Differentiable prediction decode: from the HPH read-out row
+ *   readout [P][ldr] = [pose6d(318) | betas(nb) | cam(3) | expr(10)]  (decoder output + init, reference model.py:571-575)
+ * and the 2-vector of mlp_offset to the training-mode outputs, and the cotangents of those outputs back.
+ *
+ * mhmr_heads_decode: the forward, for given readout / offset / det_* / K [B][3][3] -- reference model.py:272-275
+ *   (loc = (cell + 0.5 + offset) patch), utils/humans.py:12-22 + roma.special_gramschmidt (6D -> rotmat),
+ *   model.py:287-298 + roma.rotmat_to_rotvec, utils/camera.py:71-90 + model.py:196-203 (distance: focal
+ *   normalisation, exp, clamp to [0, 50]).  It launches the kernels of mhmr_hph_forward, so loc, rotmat [P][53][3][3],
+ *   rotvec [P][53][3], shape [P][nb], expression [P][10], dist_postprocessed [P], dist [P] are bit-equal to what
+ *   that entry leaves for the same read-out.
+ * mhmr_heads_place_backward: the derivative of the SMPL-X layer's placement, blocks/smpl_layer.py:116-144 --
+ *   x = u - u_joint[center_joint] + transl for the V vertices and NJ output joints u of mhmr_body_forward run
+ *   without transl and K (center_joint < 0: x = u + transl, :128-130), v2d / j2d = utils/camera.py:14-27 of x with
+ *   K[det_b[p]] (det_b NULL: K[p]).  Cotangents g_v3d [P][V][3], g_j3d [P][NJ][3], g_v2d [P][V][2], g_j2d [P][NJ][2],
+ *   g_transl [P][3]: any may be NULL (= zero).  Written: gx_v [P][V][3], gx_j [P][NJ][3] (the cotangents of u: feed
+ *   them to mhmr_body_backward as g_vertices / g_joints) and g_transl_total [P][3] = sum of a person's gx + g_transl.
+ *   One streaming pass + a finishing launch; elements fp32, sums fp64 in an order that depends on (V, NJ) only
+ *   (lane in index order, wave butterfly, waves in index order, tiles in index order), no floating-point atomic:
+ *   two calls give the same bits and a person's numbers do not depend on the rest of the batch.
+ * mhmr_heads_decode_backward: the derivative of mhmr_heads_decode joined with transl = dist K^-1 [loc; 1]
+ *   (utils/camera.py:30-48, smpl_layer.py:117-123).  The decode is recomputed from readout in fp64 and that evaluation
+ *   is differentiated (quaternion branch by the argmax of R00, R11, R22, trace; the w < 0 flip; the series of the
+ *   scale for |angle| <= 1e-3); every output is rounded to fp32 once.  Cotangents (any may be NULL): g_rotmat,
+ *   g_rotvec (the caller's own plus what the body backward sends to the 53 rotations), g_shape, g_expression,
+ *   g_dist [P], g_dist_postprocessed [P], g_transl [P][3] (g_transl_total above), g_loc [P][2], g_offset_direct [P][2].
+ *   Written: g_readout [P][318 + nb + 13] (cam[1:3] exactly 0; the clamp passes the gradient for 0 <= d <= 50) and
+ *   g_offset [P][2].  An exact identity 6D is an ordinary input; a degenerate 6D is NaN as in the forward.
+ * Validated before any launch: a NULL descriptor or required pointer, P < 0, 2D cotangents without K, a short
+ * workspace, center_joint >= NJ -> MHMR_ERR_BAD_ARG; nb outside [0, 64], ldr < 318 + nb + 13, P > 65535 (placement)
+ * -> MHMR_ERR_BAD_SHAPE; P == 0 launches nothing and returns 0.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int P, nb, ldr, patch, nearness;
+    float fn;
+    const float *readout, *offset, *K;
+    const int *det_b, *det_y, *det_x;
+    float *loc, *rotmat, *rotvec, *shape, *expression, *dist_postprocessed, *dist;
+} mhmr_heads_decode_desc;
+
+typedef struct {
+    int P, V, NJ, center_joint;
+    const float *verts_u, *joints_u, *transl, *K;
+    const int* det_b;
+    const float *g_v3d, *g_j3d, *g_v2d, *g_j2d, *g_transl;
+    float *gx_v, *gx_j, *g_transl_total;
+    void* workspace;
+    long long workspace_bytes;
+} mhmr_heads_place_desc;
+
+typedef struct {
+    int P, nb, ldr, patch, nearness;
+    double fn;                /* the normalising focal length in full precision (the forward's float is its rounding) */
+    const float *readout, *offset, *K;
+    const int *det_b, *det_y, *det_x;
+    const float *g_rotmat, *g_rotvec, *g_shape, *g_expression, *g_dist, *g_dist_postprocessed, *g_transl, *g_loc, *g_offset_direct;
+    float *g_readout, *g_offset;
+} mhmr_heads_decode_backward_desc;
+
+int mhmr_heads_decode(const mhmr_heads_decode_desc* d, void* stream);
+/* bytes of the per-tile fp64 sums of the placement backward: 24 per (person, tile of 1024 points); negative = MHMR_ERR_BAD_ARG */
+long long mhmr_heads_place_workspace_bytes(int V, int NJ, int P);
+int mhmr_heads_place_backward(const mhmr_heads_place_desc* d, void* stream);
+int mhmr_heads_decode_backward(const mhmr_heads_decode_backward_desc* d, void* stream);
+
 /* Sparse vertex regressor: out [M][R][3] = A . (in [M][Vin][3] - center [M][3]) for A in CSR form (rowptr [R + 1],
  * col, val); center NULL = none.  Each row is summed in the order of its entries (the loaders sort them by column) in
  * fp64 and rounded once: deterministic.  A row without entries gives zeros; an entry whose column is outside

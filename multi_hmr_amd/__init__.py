@@ -11,8 +11,9 @@ from .bodymodel import BodyModel, load_body_data  # noqa: F401
 from .evaluate import Evaluator, SparseRegressor, evaluate_dataset, load_h36m_regressor, load_smplx2smpl  # noqa: F401
 from .groundtruth import GroundTruth  # noqa: F401
 from .loss import Loss, loss_and_grads  # noqa: F401
+from . import heads  # noqa: F401
 
 __all__ = ["BodyModel", "Evaluator", "GroundTruth", "Loss", "Model", "GraphedForward", "SparseRegressor", "evaluate_dataset", "load_body_data",
            "load_h36m_regressor", "load_smplx2smpl", "loss_and_grads", "ImageResult", "PipelineError", "Preprocessor", "create_rotating_video", "create_scene", "export_batch", "forward_model", "get_bbox",
-           "get_camera_parameters", "load_model", "open_image", "overlay_human_meshes", "pack_meshes", "predict_images", "print_distance_on_image",
+           "get_camera_parameters", "heads", "load_model", "open_image", "overlay_human_meshes", "pack_meshes", "predict_images", "print_distance_on_image",
            "read_glb", "render_batch", "render_meshes", "render_views"]

@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -165,6 +165,27 @@ class BodyBackwardDesc(C.Structure):
                                     "g_j2d", "g_pose", "g_coef", "g_transl", "workspace")] + [("workspace_bytes", C.c_longlong)])
 
 
+class HeadsDecodeDesc(C.Structure):
+    """include/mhmr.h mhmr_heads_decode_desc."""
+    _fields_ = ([(n, _i) for n in ("P", "nb", "ldr", "patch", "nearness")] + [("fn", _f)] +
+                [(n, _vp) for n in ("readout", "offset", "K", "det_b", "det_y", "det_x", "loc", "rotmat", "rotvec", "shape", "expression",
+                                    "dist_postprocessed", "dist")])
+
+
+class HeadsPlaceDesc(C.Structure):
+    """include/mhmr.h mhmr_heads_place_desc."""
+    _fields_ = ([(n, _i) for n in ("P", "V", "NJ", "center_joint")] +
+                [(n, _vp) for n in ("verts_u", "joints_u", "transl", "K", "det_b", "g_v3d", "g_j3d", "g_v2d", "g_j2d", "g_transl", "gx_v", "gx_j",
+                                    "g_transl_total", "workspace")] + [("workspace_bytes", C.c_longlong)])
+
+
+class HeadsDecodeBackwardDesc(C.Structure):
+    """include/mhmr.h mhmr_heads_decode_backward_desc."""
+    _fields_ = ([(n, _i) for n in ("P", "nb", "ldr", "patch", "nearness")] + [("fn", C.c_double)] +
+                [(n, _vp) for n in ("readout", "offset", "K", "det_b", "det_y", "det_x", "g_rotmat", "g_rotvec", "g_shape", "g_expression", "g_dist",
+                                    "g_dist_postprocessed", "g_transl", "g_loc", "g_offset_direct", "g_readout", "g_offset")])
+
+
 class PreImage(C.Structure):
     """include/mhmr.h mhmr_pre_image: one image of mhmr_preprocess_u8_batch (device pointers + the geometry of its plan)."""
     _fields_ = ([("img", _vp)] + [(n, _i) for n in ("H", "W", "ow", "oh", "y0", "rows", "pad_x", "pad_y", "ksh", "ksv")] +
@@ -231,6 +252,10 @@ _SIGS = {
     "mhmr_body_forward": ([C.POINTER(BodyConsts), _vp, _vp, _vp, _vp, _i] + [_vp] * 6 + [_vp], _i),
     "mhmr_body_backward_workspace_bytes": ([C.POINTER(BodyConsts), _i], C.c_longlong),
     "mhmr_body_backward": ([C.POINTER(BodyBackwardDesc), _vp], _i),
+    "mhmr_heads_decode": ([C.POINTER(HeadsDecodeDesc), _vp], _i),
+    "mhmr_heads_place_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_heads_place_backward": ([C.POINTER(HeadsPlaceDesc), _vp], _i),
+    "mhmr_heads_decode_backward": ([C.POINTER(HeadsDecodeBackwardDesc), _vp], _i),
     "mhmr_sparse_regress": ([_ip, _ip, _fp, _i, _i, _fp, _fp, _i, _fp, _vp], _i),
     "mhmr_gt_targets": ([_fp, _i, _i, _fp, _ip, _i, _i, _i, _i, _f, _i] + [_vp] * 7 + [_vp], _i),
     "mhmr_project_points": ([_fp, _fp, _i, _i, _fp, _vp], _i),

@@ -701,6 +701,20 @@ int mhmr_hph_decode(const float* dec, int ldd, int nb, const float* K, const int
     return mhmr_launch_hph_decode(dec, ldd, nb, K, det_b, fn, nearness, rotmat, rotvec, betas, expr, dist_pp, dist, P, (hipStream_t)stream);
 }
 
+// The decode + loc of mhmr_hph_forward on a caller's read-out: the same two kernels, hence the same bits.
+int mhmr_heads_decode(const mhmr_heads_decode_desc* d, void* stream) {
+    if (!d || d->P < 0) return MHMR_ERR_BAD_ARG;
+    if (d->nb < 0 || d->nb > 64 || d->ldr < 318 + d->nb + 3 + 10) return MHMR_ERR_BAD_SHAPE;
+    if (d->P == 0) return 0;
+    if (!d->readout || !d->offset || !d->K || !d->det_b || !d->det_y || !d->det_x || !d->loc || !d->rotmat || !d->rotvec || !d->shape ||
+        !d->expression || !d->dist_postprocessed || !d->dist)
+        return MHMR_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(mhmr_launch_loc(d->offset, d->det_y, d->det_x, d->patch, d->loc, d->P, s));
+    return mhmr_launch_hph_decode(d->readout, d->ldr, d->nb, d->K, d->det_b, d->fn, d->nearness, d->rotmat, d->rotvec, d->shape, d->expression,
+                                  d->dist_postprocessed, d->dist, d->P, s);
+}
+
 // `depth` x (pre-norm self-attention among the queries of one image, cross-attention over that image's N context
 // tokens, GELU feed-forward), each with a residual.  Shared by the Multi-HMR HPH (dim 1024, 8 heads, mlp 1024, depth 2,
 // blocks/cross_attn_transformer.py:239-261) and the Anny HPH (dim 512, 16 heads, mlp 2048, depth 8,

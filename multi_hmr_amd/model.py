@@ -467,17 +467,41 @@ class Model(nn.Module):
         """Same contract as the reference ``Model.forward`` (model.py:205-349): inference -> list of per-person dicts
         (empty list if nobody is detected); ``is_training=True`` (needs ``idx``) -> dict of batched tensors.
         Extension used by ``distributed.forward_sharded``: ``return_image_index=True`` (inference only) -> (persons, image id [P]);
-        ``return_batched=True`` (inference only) -> (dict of batched tensors [P, ...], image id [P]) instead of the per-person list."""
+        ``return_batched=True`` (inference only) -> (dict of batched tensors [P, ...], image id [P]) instead of the per-person list.
+        ``return_readout=True`` (training mode only) adds ``out["readout"]``: a contiguous ``[P, 318 + num_betas + 3 + 10]`` copy of the
+        decoder's read-out rows ``pose6d | betas | cam | expr`` (what ``decode_readout`` takes)."""
         with self._lock, torch.autocast("cuda", enabled=False):     # demo.forward_model wraps us in fp16 autocast (demo.py:117)
             return self._forward(x.float().contiguous(), idx, det_thresh, nms_kernel_size, K, is_training,
-                                 bool(kwargs.get("return_image_index", False)), bool(kwargs.get("return_batched", False)))
+                                 bool(kwargs.get("return_image_index", False)), bool(kwargs.get("return_batched", False)),
+                                 bool(kwargs.get("return_readout", False)))
 
     supports_image_index = True
     supports_batched = True
     #: keys of a person dict, in the reference's order (model.py:330-346)
     PERSON_KEYS = ("scores", "loc", "transl", "transl_pelvis", "rotvec", "expression", "shape", "v3d", "j3d", "j2d")
 
-    def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, with_ids=False, batched=False):
+    def decode_readout(self, readout, offset, idx, K):
+        """The training-mode dict from a read-out: ``readout [P, 318 + num_betas + 3 + 10]`` and ``offset [P, 2]`` (what
+        ``forward(..., is_training=True, return_readout=True)`` returns under those keys, or any tensors of that shape), ``idx`` the (image,
+        y, x) triple of each person, ``K [B, 3, 3]`` -> ``offset, loc, rotmat, rotvec, shape, expression, dist_postprocessed, dist, v3d, v2d,
+        j3d, j2d, transl, transl_pelvis``, attached to autograd with respect to ``readout`` and ``offset`` (once differentiable).
+
+        The values come from the kernels ``forward`` runs and are bit-equal to its outputs for that call's read-out and offset.  The
+        gradient is that of the fp32 body layer (``BodyModel``) at the same parameters; the returned meshes are
+        ``lbs.hip``'s, which differ from that layer by at most the 5e-5 m of DESIGN section 5.  The fp32 body forward runs at backward time,
+        so a call that is never differentiated costs what the decode and the SMPL-X layer cost in ``forward``.  ``K`` and the model's
+        constants get no gradient.  CPU tensors raise; no person (P = 0) is an ordinary input."""
+        from . import heads
+        return heads.decode_readout(self, readout, offset, idx, K)
+
+    def _body_model(self):
+        """The fp32 body model of the prediction's parameters (built on first use: only ``decode_readout``'s backward needs it)."""
+        if getattr(self, "_bm32", None) is None:
+            from .bodymodel import BodyModel
+            self._bm32 = BodyModel(self._smplx_data, "smplx", num_betas=self.num_betas)
+        return self._bm32
+
+    def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, with_ids=False, batched=False, with_readout=False):
         L = _lib.lib()
         P, ws, stream = self._prepare(x)
         dev, B, G = x.device, x.shape[0], P["G"]
@@ -494,13 +518,18 @@ class Model(nn.Module):
             Pn = int(idx[0].shape[0])
             out = {"scores": scores.clone()}
             if Pn == 0:
+                if with_readout:
+                    out["readout"] = torch.empty(0, 318 + P["hph"]["nb"] + 13, dtype=torch.float32, device=dev)
                 return out
             det = torch.stack([idx[0], idx[1], idx[2]]).to(torch.int32).contiguous()
             gstart_t, chunks_t, info, ngc, ncc = self._tables(B, Pn, dev)
             _lib.check(L.mhmr_person_groups(None, det[0].data_ptr(), Pn, B, Pn, None, gstart_t.data_ptr(), ngc, chunks_t.data_ptr(), ncc,
                                             info.data_ptr(), stream), "mhmr_person_groups")
-            heads = self._heads(P, ws, K, det, Pn, gstart_t, ngc, chunks_t, ncc, None, stream)
+            keep = {} if with_readout else None
+            heads = self._heads(P, ws, K, det, Pn, gstart_t, ngc, chunks_t, ncc, None, stream, keep=keep)
             out.update({n: t for n, t in heads.items() if n not in ("scores", "_flat")})      # (scores here = the [B, G, G, 1] map, model.py:349)
+            if with_readout:
+                out["readout"] = keep["dec"][:, :318 + P["hph"]["nb"] + 13].contiguous()
             return out
 
         # NMS + threshold + ordered compaction (model.py:141-149)
@@ -623,7 +652,7 @@ class Model(nn.Module):
         o["_flat"] = flat
         return o
 
-    def _heads(self, P, ws, K, det, Pn, gstart_t, ngc, chunks_t, ncc, info, stream, o=None):
+    def _heads(self, P, ws, K, det, Pn, gstart_t, ngc, chunks_t, ncc, info, stream, o=None, keep=None):
         """HPH (model.py:258-283, 287-298) + SMPL-X layer (model.py:319-321) for Pn person rows -> dict of batched tensors (written
         into ``o`` when the caller allocated them: _alloc_outputs)."""
         L = _lib.lib()
@@ -646,6 +675,8 @@ class Model(nn.Module):
         d.kv = ws["kv"].data_ptr()
         d.nvalid = info.data_ptr() if info is not None else None
         d.cam_dim = P["E"]
+        if keep is not None:
+            keep["dec"] = wsp["dec"]                       # the read-out rows [Pn, Ndec] (forward(..., return_readout=True))
         if o is None:
             o = self._alloc_outputs(P, Pn, dev)
         offset, loc, rotmat, rotvec, shape, expression = o["offset"], o["loc"], o["rotmat"], o["rotvec"], o["shape"], o["expression"]
