@@ -394,6 +394,118 @@ int mhmr_hph_decode(const float* dec, int ldd, int nb, const float* K, const int
                     float* rotmat, float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Backward of the decoder layer stack: the derivative of mhmr_xattn_layers_forward as its kernels
+ * evaluate it, fp32; ctx16 and to_kv16 are 16-bit values taken as exact numbers (the gradient of to_kv is that of the
+ * rounded weight).  Sums across persons, rows or tiles are fp64 or fp32 MFMA chains of a shape fixed by the sizes and
+ * tables alone, there are no floating-point atomics, every element of every output is written, and two calls give the
+ * same bits.  No entry allocates or synchronises; all validation happens before any launch.
+ *
+ * Building blocks (act = MHMR_ACT_*; Z = the TAPED pre-activation of the linear, read only when act != NONE):
+ *   mhmr_linear_f32_backward_input:   dX[m][k] = sum_n dZ[row(m)][n] W[n][k] (+ dR[m][k]),  dZ = dY * act'(Z).  W [N, K];
+ *       row_idx (nullable) gathers the rows of dY and Z; dR (nullable) is a residual cotangent added in the epilogue.
+ *   mhmr_linear_f32_backward_weight:  dW[n][k] = sum_m dZ[m][n] X[m][k] (persons in index order, zero-padded to a
+ *       multiple of 4), db[n] = sum_m dZ[m][n] in fp64.  dW or db may be NULL (not both).  M == 0 writes zeros.
+ *   mhmr_layernorm_f32_backward:      dx (+ dR, nullable) of mhmr_layernorm_f32, one wave per row; dw, db = fp64 sums over
+ *       the rows through two fixed stages.  C % 64 == 0, C <= 2048.
+ *   mhmr_hph_self_attn_backward:      qkv [P, 3 inner], dOut [P, inner] -> dqkv [P, 3 inner] for the groups of gstart
+ *       (as mhmr_hph_self_attn: groups of any size, empty groups allowed); lse_d [P, heads, 2] is scratch.
+ *   mhmr_hph_cross_attn_backward:     q [P, inner], kv [B N, 2 inner], dOut [P, inner], chunks as mhmr_hph_cross_attn
+ *       (count <= 8, count-0 padding items only at the tail; any number of items: one launch per 512) -> dq [P, inner] (rows
+ *       of no work item are not written) and dkv [B N, 2 inner] (ALL rows written; rows of images without queries hold
+ *       zeros).  dq or dkv may be NULL (not both).  lse_d [P, heads, 2] is scratch.  Items of one image must be
+ *       consecutive and in person order (as mhmr_person_groups emits them).
+ *   mhmr_grad_ctx_gemm:               dW[n][c] = sum_rows G[row][n] * op16[row][c], [Nn, Kc]; the row range is split into
+ *       at most 16 slices whose partial products are added in slice order; columns c >= cvalid are exact zeros.
+ * Return codes: MHMR_ERR_BAD_ARG for a negative count (M, rows, P, ngroups, nmax, nchunks), a NULL pointer that would be read
+ * or written, or a short workspace; MHMR_ERR_BAD_SHAPE for the shape rules above, a leading dimension smaller than its row,
+ * heads, B or a row-tile count above 65535 (launch limits: M > 16 * 65535 on the input side, LayerNorm rows > 32 * 65535),
+ * B N >= 2^31.  An empty problem (M, rows, P == 0) returns 0.
+ * ---------------------------------------------------------------------------------------------------------- */
+int mhmr_linear_f32_backward_input(const float* dY, int lddy, const int* row_idx, const float* Z, int ldz, const float* W,
+                                   int ldw, const float* dR, int lddr, float* dX, int lddx, int M, int N, int K, int act,
+                                   void* stream);
+int mhmr_linear_f32_backward_weight(const float* dY, int lddy, const float* Z, int ldz, const float* X, int ldx, float* dW,
+                                    int lddw, float* db, int M, int N, int K, int act, void* stream);
+long long mhmr_layernorm_f32_backward_workspace_bytes(int rows, int C);
+int mhmr_layernorm_f32_backward(const float* x, const float* w, const float* dy, const float* dR, float* dx, float* dw,
+                                float* db, int rows, int C, float eps, void* workspace, long long workspace_bytes,
+                                void* stream);
+int mhmr_hph_self_attn_backward(const float* qkv, const float* dOut, const int* gstart, float* dqkv, float* lse_d,
+                                int ngroups, int nmax, int heads, void* stream);
+int mhmr_hph_cross_attn_backward(const float* q, const float* kv, const float* dOut, const int* chunks, int nchunks,
+                                 float* dq, float* dkv, float* lse_d, int heads, int N, int B, void* stream);
+long long mhmr_grad_ctx_gemm_workspace_bytes(int rows, int Nn, int Kc);
+int mhmr_grad_ctx_gemm(const float* G, int ldg, const void* op16, int ld16, float* dW, int rows, int Nn, int Kc,
+                       int cvalid, int dtype, void* workspace, long long workspace_bytes, void* stream);
+
+/* One gradient buffer per field of mhmr_hph_layer, in the field's shape; to_kv is fp32 [2 inner, Kc]. */
+typedef struct {
+    float *ln_sa_w, *ln_sa_b, *to_qkv, *sa_out_w, *sa_out_b, *ln_ca_w, *ln_ca_b, *to_kv, *to_q, *ca_out_w, *ca_out_b,
+          *ln_ff_w, *ln_ff_b, *ff1_w, *ff1_b, *ff2_w, *ff2_b;
+} mhmr_hph_layer_grads;
+
+typedef struct {
+    const mhmr_hph_layer* layers;       /* HOST array of `depth`: the weights mhmr_xattn_layers_forward ran with */
+    const mhmr_hph_layer_grads* grads;  /* HOST array of `depth`: outputs                                       */
+    int depth, dim, heads, mlp, Kc, N, B, dtype;
+    int P, ngroups, nmax, nchunks;      /* as mhmr_xattn_layers_forward                                          */
+    int ctx_valid;                      /* columns >= ctx_valid of every g_to_kv are exact zeros (0 = Kc)        */
+    const float* x0;                    /* [P, dim] the stack's INPUT (the forward overwrote its copy)           */
+    const void* ctx16;                  /* op16 [roundup(B N, 128), Kc]                                          */
+    const int *gstart, *chunks;
+    const float* g_x_out;               /* [P, dim] cotangent of the stack's output                              */
+    float* g_x0;                        /* [P, dim] out: cotangent of x0                                         */
+    const int* det_row;                 /* [P] context row of each person (needed with g_ctx), else NULL         */
+    float* g_ctx;                       /* [P, Kc] out, nullable: sum over the layers of dkv[det_row[p]] . to_kv */
+    void* workspace;
+    long long workspace_bytes;
+} mhmr_xattn_backward_desc;
+
+/* The forward overwrites x in place, so the backward first re-runs the forward's own launchers, out of place, into a tape
+ * inside the workspace (the inputs of the three sub-blocks, qkv, q, both attention outputs, the feed-forward's
+ * pre-activation and its GELU), and recomputes kv per layer from ctx16 on the way back.  The workspace also holds dkv
+ * [B N, 2 inner]: at 32 images of 4096 tokens and 8 heads that is 268 MB of the total.  The cotangent of the context is
+ * returned only at the persons' own cells (g_ctx with det_row; straight-through past the 16-bit rounding), not for the
+ * other rows.  mhmr_xattn_layers_backward_workspace_bytes: bytes for these shapes (monotone in P and depth); negative =
+ * MHMR_ERR_BAD_ARG (depth, P < 0) or MHMR_ERR_BAD_SHAPE (the forward's shape rules, heads or B above 65535).
+ * mhmr_xattn_layers_backward: MHMR_ERR_BAD_ARG for a NULL descriptor, a NULL pointer in it or in layers / grads, P < 0,
+ * a short workspace, or P > 0 with ngroups, nmax or nchunks == 0 (persons that no group or no work item covers);
+ * MHMR_ERR_BAD_SHAPE as above and for P > 16 * 65535; P == 0 launches nothing and returns 0. */
+long long mhmr_xattn_layers_backward_workspace_bytes(int depth, int dim, int heads, int mlp, int Kc, int N, int B, int P);
+int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream);
+
+/* The whole of mhmr_hph_forward up to the read-out, from g_readout [P, ldg >= Ndec] and g_offset [P, 2]: the dec linear, the stack, the
+ * token embedding (g_tok_b is also the gradient of pos_embedding[0, 0], which the forward folds into that bias; the padding columns of
+ * g_tok_w are zeros), the four tables of the HPH inputs and mlp_offset.  `fwd` is the descriptor mhmr_hph_forward ran with for THESE
+ * persons: the backward reads its weights and the workspaces zc, token, x (the stack's output) and det_row as that call left them, and
+ * ctx16 as it left it (context rows of the detected cells included) -- so it must run before the next forward into the same buffers.
+ * Gradient buffers have the packed shapes: g_off1_w [C, C], g_off1_b [C], g_off2_w [2, C], g_off2_b [2], g_tok_w [dim, Ktok], g_tok_b
+ * [dim], g_dec_w [Ndec, dim], g_dec_b [Ndec] (the init_* added into dec_b are buffers and get nothing), g_cq_x / g_cq_y / g_cv_x /
+ * g_cv_y [G, C + E] (the *_x tables are indexed by the ROW y, the *_y tables by the COLUMN x, as in the forward; rows nobody indexes
+ * are zeros), layer_grads as in mhmr_xattn_layers_backward.  g_zc [P, C] and g_token [P, Ktok] are the cotangents of the gathered
+ * features, returned for a backbone backward.  Every row of fwd is a person (fwd->nvalid is not read).  Two persons in one cell of one
+ * image are outside the contract, as they are for the reference's indexed assignment; nothing checks for them.
+ * MHMR_ERR_BAD_ARG: NULL descriptor / fwd / pointer, P < 0, short workspace, P > 0 with ngroups, nmax or nchunks == 0; MHMR_ERR_BAD_SHAPE: the forward's shape rules, Ndec !=
+ * 318 + nb + 13, ldg < Ndec, the launch limits of mhmr_xattn_layers_backward.  P == 0 launches nothing and returns 0. */
+typedef struct {
+    const mhmr_hph_desc* fwd;
+    const void* ctx16;
+    const int *det_y, *det_x;           /* [P]                                                                   */
+    const int *gstart, *chunks;
+    int ngroups, nmax, nchunks, P, B;   /* as mhmr_hph_forward                                                   */
+    const float* g_readout;             /* [P, ldg]                                                              */
+    int ldg;
+    const float* g_offset;              /* [P, 2]                                                                */
+    float *g_off1_w, *g_off1_b, *g_off2_w, *g_off2_b, *g_tok_w, *g_tok_b, *g_dec_w, *g_dec_b, *g_cq_x, *g_cq_y, *g_cv_x, *g_cv_y;
+    const mhmr_hph_layer_grads* layer_grads;  /* HOST array of fwd->depth                                        */
+    float *g_zc, *g_token;
+    void* workspace;
+    long long workspace_bytes;
+} mhmr_hph_backward_desc;
+long long mhmr_hph_backward_workspace_bytes(const mhmr_hph_desc* fwd, int B, int P);
+int mhmr_hph_backward(const mhmr_hph_backward_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * SMPL-X layer.  Replaces SMPL_Layer.forward (blocks/smpl_layer.py:47-155) -> smplx.SMPLX.forward / lbs,
  * roma.rotvec_to_rotmat (:107), inverse_perspective_projection (:117-123), perspective_projection (:143-144).
  * ---------------------------------------------------------------------------------------------------------- */

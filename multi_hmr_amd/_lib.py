@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -125,6 +125,29 @@ class HphDesc(C.Structure):
                                     "tok_w", "tok_b")] + [("layers", C.POINTER(HphLayer))] +
                 [(n, _vp) for n in ("dec_w", "dec_b", "zc", "token", "x", "xn", "t1", "t2", "kv", "dec", "det_row", "nvalid")] +
                 [("cam_dim", _i)])
+
+
+class HphLayerGrads(C.Structure):
+    """include/mhmr.h mhmr_hph_layer_grads: one fp32 gradient buffer per field of HphLayer (to_kv fp32 [2 inner, Kc])."""
+    FIELDS = ("ln_sa_w", "ln_sa_b", "to_qkv", "sa_out_w", "sa_out_b", "ln_ca_w", "ln_ca_b", "to_kv", "to_q", "ca_out_w", "ca_out_b",
+              "ln_ff_w", "ln_ff_b", "ff1_w", "ff1_b", "ff2_w", "ff2_b")
+    _fields_ = [(n, _vp) for n in FIELDS]
+
+
+class XattnBackwardDesc(C.Structure):
+    """include/mhmr.h mhmr_xattn_backward_desc."""
+    _fields_ = ([("layers", C.POINTER(HphLayer)), ("grads", C.POINTER(HphLayerGrads))] +
+                [(n, _i) for n in ("depth", "dim", "heads", "mlp", "Kc", "N", "B", "dtype", "P", "ngroups", "nmax", "nchunks", "ctx_valid")] +
+                [(n, _vp) for n in ("x0", "ctx16", "gstart", "chunks", "g_x_out", "g_x0", "det_row", "g_ctx", "workspace")] + [("workspace_bytes", C.c_longlong)])
+
+
+class HphBackwardDesc(C.Structure):
+    """include/mhmr.h mhmr_hph_backward_desc."""
+    GRADS = ("g_off1_w", "g_off1_b", "g_off2_w", "g_off2_b", "g_tok_w", "g_tok_b", "g_dec_w", "g_dec_b", "g_cq_x", "g_cq_y", "g_cv_x", "g_cv_y")
+    _fields_ = ([("fwd", C.POINTER(HphDesc))] + [(n, _vp) for n in ("ctx16", "det_y", "det_x", "gstart", "chunks")] +
+                [(n, _i) for n in ("ngroups", "nmax", "nchunks", "P", "B")] + [("g_readout", _vp), ("ldg", _i), ("g_offset", _vp)] +
+                [(n, _vp) for n in GRADS] + [("layer_grads", C.POINTER(HphLayerGrads)), ("g_zc", _vp), ("g_token", _vp), ("workspace", _vp),
+                                             ("workspace_bytes", C.c_longlong)])
 
 
 class LbsConsts(C.Structure):
@@ -245,6 +268,18 @@ _SIGS = {
     "mhmr_hph_self_attn": ([_vp, _vp, _vp, _i, _i, _i, _vp], _i),
     "mhmr_hph_cross_attn": ([_vp, _vp, _vp, _i, _vp, _i, _i, _vp], _i),
     "mhmr_hph_decode": ([_vp, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "mhmr_linear_f32_backward_input": ([_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "mhmr_linear_f32_backward_weight": ([_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp], _i),
+    "mhmr_layernorm_f32_backward_workspace_bytes": ([_i, _i], C.c_longlong),
+    "mhmr_layernorm_f32_backward": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, C.c_longlong, _vp], _i),
+    "mhmr_hph_self_attn_backward": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
+    "mhmr_hph_cross_attn_backward": ([_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
+    "mhmr_grad_ctx_gemm_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_grad_ctx_gemm": ([_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
+    "mhmr_xattn_layers_backward_workspace_bytes": ([_i] * 8, C.c_longlong),
+    "mhmr_xattn_layers_backward": ([C.POINTER(XattnBackwardDesc), _vp], _i),
+    "mhmr_hph_backward_workspace_bytes": ([C.POINTER(HphDesc), _i, _i], C.c_longlong),
+    "mhmr_hph_backward": ([C.POINTER(HphBackwardDesc), _vp], _i),
     "mhmr_lbs_forward": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp], _i),
     "mhmr_preprocess_u8": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i] + [_i] * 7 + [_vp, _vp, _vp, _vp], _i),
     "mhmr_preprocess_u8_batch": ([C.POINTER(PreImage), _vp, _i, _i, _vp, _vp, _vp], _i),

@@ -326,38 +326,18 @@ class Model(nn.Module):
         P["freq"] = torch.stack([torch.linspace(1.0, self._camera_max_resolution / 2, nbands) for _ in range(3)]).to(device).contiguous()
 
         # HPH
-        hp = self.x_attention_head
         heads, depth, dim, mlp, nb = self.xat_num_heads, self.xat_depth, 1024, 1024, self.num_betas
         inner = 32 * heads
         n_kv = roundup(2 * inner, 128)
         Ktok = roundup(Cc + 318 + nb + 3, 16)
-        tok_w = torch.zeros(dim, Ktok, device=device)
-        tok_w[:, : Cc + 321 + nb] = f32(hp.transformer.to_token_embedding.weight)
-        tok_b = f32(hp.transformer.to_token_embedding.bias) + f32(hp.transformer.pos_embedding[0, 0])
+        ht = self._head_tensors(device, tdt, Cc, Kc)
         layers = (_lib.HphLayer * depth)()
-        for l, (sa, ca, ff) in enumerate(hp.transformer.transformer.layers):
-            y = layers[l]
-            y.ln_sa_w, y.ln_sa_b, y.to_qkv = k(f32(sa.norm.weight)), k(f32(sa.norm.bias)), k(f32(sa.fn.to_qkv.weight))
-            y.sa_out_w, y.sa_out_b = k(f32(sa.fn.to_out[0].weight)), k(f32(sa.fn.to_out[0].bias))
-            y.ln_ca_w, y.ln_ca_b = k(f32(ca.norm.weight)), k(f32(ca.norm.bias))
-            kvw = torch.zeros(n_kv, Kc, device=device)
-            kvw[: 2 * inner, :Cc] = f32(ca.fn.to_kv.weight)
-            y.to_kv16, y.to_q = k(kvw.to(tdt).contiguous()), k(f32(ca.fn.to_q.weight))
-            y.ca_out_w, y.ca_out_b = k(f32(ca.fn.to_out[0].weight)), k(f32(ca.fn.to_out[0].bias))
-            y.ln_ff_w, y.ln_ff_b = k(f32(ff.norm.weight)), k(f32(ff.norm.bias))
-            y.ff1_w, y.ff1_b = k(f32(ff.fn.net[0].weight)), k(f32(ff.fn.net[0].bias))
-            y.ff2_w, y.ff2_b = k(f32(ff.fn.net[3].weight)), k(f32(ff.fn.net[3].bias))
-        dec_w = torch.cat([f32(m.weight) for m in (hp.decpose, hp.decshape, hp.deccam, hp.decexpression)], 0).contiguous()
-        dec_b = (torch.cat([f32(m.bias) for m in (hp.decpose, hp.decshape, hp.deccam, hp.decexpression)], 0) +
-                 torch.cat([f32(hp.init_body_pose[0]), f32(hp.init_betas[0]), f32(hp.init_cam[0]), f32(hp.init_expression[0])], 0))
-        init_tail = torch.cat([f32(hp.init_body_pose[0]), f32(hp.init_betas[0]), f32(hp.init_cam[0])], 0).contiguous()
+        for l, lt in enumerate(ht["layers"]):
+            for n, _ in _lib.HphLayer._fields_:
+                setattr(layers[l], n, k(lt[n]))
         P["hph"] = dict(layers=layers, heads=heads, depth=depth, dim=dim, mlp=mlp, nb=nb, inner=inner, n_kv=n_kv, Ktok=Ktok,
-                        Ndec=318 + nb + 13,
-                        off1_w=k(f32(self.mlp_offset[0].weight)), off1_b=k(f32(self.mlp_offset[0].bias)),
-                        off2_w=k(f32(self.mlp_offset[2].weight)), off2_b=k(f32(self.mlp_offset[2].bias)),
-                        cq_x=k(f32(hp.cross_queries_x)), cq_y=k(f32(hp.cross_queries_y)), cv_x=k(f32(hp.cross_values_x)),
-                        cv_y=k(f32(hp.cross_values_y)), init_tail=k(init_tail), tok_w=k(tok_w.contiguous()), tok_b=k(tok_b.contiguous()),
-                        dec_w=k(dec_w), dec_b=k(dec_b.contiguous()))
+                        Ndec=318 + nb + 13, **{n: k(ht[n]) for n in self.HEAD_TENSORS})
+        P["hph_t"], P["heads_generation"] = ht, 0
         assert n_kv == 2 * inner, "xat_num_heads must be even (to_kv rows are tiled by 128)"
 
         # SMPL-X
@@ -367,6 +347,70 @@ class Model(nn.Module):
         P["lbs_sync"] = torch.zeros(1 + 160, dtype=torch.int32, device=device)      # unused by the model: kept only for bench.py's lbs section, which reads the key
         self._packed = P
         return P
+
+    #: packed head tensors outside the layer stack (fields of mhmr_hph_desc)
+    HEAD_TENSORS = ("off1_w", "off1_b", "off2_w", "off2_b", "cq_x", "cq_y", "cv_x", "cv_y", "init_tail", "tok_w", "tok_b", "dec_w", "dec_b")
+
+    def _head_tensors(self, device, tdt, Cc, Kc):
+        """The packed copies of the head parameters: fp32, the 16-bit to_kv, the padded token embedding and the folded biases
+        (tok_b = bias + pos_embedding[0, 0]; dec_b = the four read-out biases + init_*).  -> {name: tensor, "layers": [{field: tensor}]}."""
+        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        hp = self.x_attention_head
+        heads, dim, nb = self.xat_num_heads, 1024, self.num_betas
+        inner = 32 * heads
+        n_kv = roundup(2 * inner, 128)
+        Ktok = roundup(Cc + 318 + nb + 3, 16)
+        tok_w = torch.zeros(dim, Ktok, device=device)
+        tok_w[:, : Cc + 321 + nb] = f32(hp.transformer.to_token_embedding.weight)
+        tok_b = f32(hp.transformer.to_token_embedding.bias) + f32(hp.transformer.pos_embedding[0, 0])
+        layers = []
+        for sa, ca, ff in hp.transformer.transformer.layers:
+            kvw = torch.zeros(n_kv, Kc, device=device)
+            kvw[: 2 * inner, :Cc] = f32(ca.fn.to_kv.weight)
+            layers.append(dict(ln_sa_w=f32(sa.norm.weight), ln_sa_b=f32(sa.norm.bias), to_qkv=f32(sa.fn.to_qkv.weight),
+                               sa_out_w=f32(sa.fn.to_out[0].weight), sa_out_b=f32(sa.fn.to_out[0].bias), ln_ca_w=f32(ca.norm.weight),
+                               ln_ca_b=f32(ca.norm.bias), to_kv16=kvw.to(tdt).contiguous(), to_q=f32(ca.fn.to_q.weight),
+                               ca_out_w=f32(ca.fn.to_out[0].weight), ca_out_b=f32(ca.fn.to_out[0].bias), ln_ff_w=f32(ff.norm.weight),
+                               ln_ff_b=f32(ff.norm.bias), ff1_w=f32(ff.fn.net[0].weight), ff1_b=f32(ff.fn.net[0].bias),
+                               ff2_w=f32(ff.fn.net[3].weight), ff2_b=f32(ff.fn.net[3].bias)))
+        dec_w = torch.cat([f32(m.weight) for m in (hp.decpose, hp.decshape, hp.deccam, hp.decexpression)], 0).contiguous()
+        dec_b = (torch.cat([f32(m.bias) for m in (hp.decpose, hp.decshape, hp.deccam, hp.decexpression)], 0) +
+                 torch.cat([f32(hp.init_body_pose[0]), f32(hp.init_betas[0]), f32(hp.init_cam[0]), f32(hp.init_expression[0])], 0))
+        init_tail = torch.cat([f32(hp.init_body_pose[0]), f32(hp.init_betas[0]), f32(hp.init_cam[0])], 0).contiguous()
+        return dict(layers=layers, off1_w=f32(self.mlp_offset[0].weight), off1_b=f32(self.mlp_offset[0].bias),
+                    off2_w=f32(self.mlp_offset[2].weight), off2_b=f32(self.mlp_offset[2].bias), cq_x=f32(hp.cross_queries_x),
+                    cq_y=f32(hp.cross_queries_y), cv_x=f32(hp.cross_values_x), cv_y=f32(hp.cross_values_y), init_tail=init_tail,
+                    tok_w=tok_w.contiguous(), tok_b=tok_b.contiguous(), dec_w=dec_w, dec_b=dec_b.contiguous())
+
+    def repack_heads(self):
+        """Re-pack ONLY the head weights (``mlp_offset``, ``x_attention_head``) into the buffers the descriptors already point to --
+        after an optimiser step on ``heads_parameters()``.  The ViT pack and the workspaces stay (``repack()`` drops both).  Outputs of
+        the next forward are bit-equal to ``repack()`` + forward.  A pending ``backward`` of a ``train_heads`` forward must run first."""
+        with self._lock:
+            P = self._packed
+            if P is None:
+                return                                   # nothing packed yet: the next forward packs everything
+            new, old = self._head_tensors(P["device"], P["tdt"], P["Cc"], P["Kc"]), P["hph_t"]
+            with torch.no_grad():
+                for n in self.HEAD_TENSORS:
+                    old[n].copy_(new[n])
+                for lo, ln in zip(old["layers"], new["layers"]):
+                    for n, t in ln.items():
+                        lo[n].copy_(t)
+            P["heads_generation"] += 1
+
+    def heads_parameters(self):
+        """Every parameter of ``mlp_offset`` and ``x_attention_head``: what ``train_heads=True`` differentiates, the list an optimiser
+        takes.  They stay ``requires_grad=False`` until ``train_heads_(True)``."""
+        from .heads_train import head_parameter_names
+        params = dict(self.named_parameters())
+        return [params[n] for n in head_parameter_names(self.xat_depth)]
+
+    def train_heads_(self, flag=True):
+        """Set ``requires_grad`` of ``heads_parameters()``; returns self."""
+        for p in self.heads_parameters():
+            p.requires_grad_(bool(flag))
+        return self
 
     @property
     def packed_precision(self):
@@ -418,6 +462,7 @@ class Model(nn.Module):
         everything enqueued after sees every block's output)."""
         L = _lib.lib()
         dev, parts, Kc, N, Cd = x.device, ws["parts"], P["Kc"], P["N"], P["C"]
+        ws["generation"] = ws.get("generation", 0) + 1      # the features and the context operand a pending train_heads backward reads are overwritten
         main = torch.cuda.current_stream(dev)
         esz_ctx = ws["ctx16"].element_size()
         img_elems = x.shape[1] * x.shape[2] * x.shape[3]
@@ -469,11 +514,18 @@ class Model(nn.Module):
         Extension used by ``distributed.forward_sharded``: ``return_image_index=True`` (inference only) -> (persons, image id [P]);
         ``return_batched=True`` (inference only) -> (dict of batched tensors [P, ...], image id [P]) instead of the per-person list.
         ``return_readout=True`` (training mode only) adds ``out["readout"]``: a contiguous ``[P, 318 + num_betas + 3 + 10]`` copy of the
-        decoder's read-out rows ``pose6d | betas | cam | expr`` (what ``decode_readout`` takes)."""
+        decoder's read-out rows ``pose6d | betas | cam | expr`` (what ``decode_readout`` takes).
+        ``train_heads=True`` (needs ``is_training=True`` and ``return_readout=True``): the same dict, key for key and bit for bit, with
+        ``out["readout"]`` and ``out["offset"]`` attached to autograd with respect to ``heads_parameters()`` (those that require grad:
+        ``train_heads_(True)``) -- ``decode_readout`` and ``Loss`` on top, ``backward()``, an optimiser step, ``repack_heads()``.  The
+        backward reads this call's workspace: run it before the next forward of the same batch size (it raises otherwise).  With no
+        person the gradients are zeros."""
+        if kwargs.get("train_heads", False) and not (is_training and kwargs.get("return_readout", False)):
+            raise ValueError("train_heads=True needs is_training=True and return_readout=True")
         with self._lock, torch.autocast("cuda", enabled=False):     # demo.forward_model wraps us in fp16 autocast (demo.py:117)
             return self._forward(x.float().contiguous(), idx, det_thresh, nms_kernel_size, K, is_training,
                                  bool(kwargs.get("return_image_index", False)), bool(kwargs.get("return_batched", False)),
-                                 bool(kwargs.get("return_readout", False)))
+                                 bool(kwargs.get("return_readout", False)), bool(kwargs.get("train_heads", False)))
 
     supports_image_index = True
     supports_batched = True
@@ -501,7 +553,8 @@ class Model(nn.Module):
             self._bm32 = BodyModel(self._smplx_data, "smplx", num_betas=self.num_betas)
         return self._bm32
 
-    def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, with_ids=False, batched=False, with_readout=False):
+    def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, with_ids=False, batched=False, with_readout=False,
+                 train_heads=False):
         L = _lib.lib()
         P, ws, stream = self._prepare(x)
         dev, B, G = x.device, x.shape[0], P["G"]
@@ -520,6 +573,10 @@ class Model(nn.Module):
             if Pn == 0:
                 if with_readout:
                     out["readout"] = torch.empty(0, 318 + P["hph"]["nb"] + 13, dtype=torch.float32, device=dev)
+                if train_heads:
+                    from . import heads_train
+                    out["readout"], _ = heads_train.attach(self, dict(P=P, dev=dev, Pn=0, readout=out["readout"],
+                                                                      offset=torch.empty(0, 2, dtype=torch.float32, device=dev)))
                 return out
             det = torch.stack([idx[0], idx[1], idx[2]]).to(torch.int32).contiguous()
             gstart_t, chunks_t, info, ngc, ncc = self._tables(B, Pn, dev)
@@ -530,6 +587,12 @@ class Model(nn.Module):
             out.update({n: t for n, t in heads.items() if n not in ("scores", "_flat")})      # (scores here = the [B, G, G, 1] map, model.py:349)
             if with_readout:
                 out["readout"] = keep["dec"][:, :318 + P["hph"]["nb"] + 13].contiguous()
+            if train_heads:
+                from . import heads_train
+                st = dict(P=P, ws=ws, dev=dev, Pn=Pn, B=B, generation=ws["generation"], heads_generation=P["heads_generation"],
+                          desc=keep["desc"], wsp=keep["wsp"], det=det, gstart=gstart_t, chunks=chunks_t, ngc=ngc, ncc=ncc,
+                          readout=out["readout"], offset=out["offset"].clone())
+                out["readout"], out["offset"] = heads_train.attach(self, st)
             return out
 
         # NMS + threshold + ordered compaction (model.py:141-149)
@@ -677,6 +740,7 @@ class Model(nn.Module):
         d.cam_dim = P["E"]
         if keep is not None:
             keep["dec"] = wsp["dec"]                       # the read-out rows [Pn, Ndec] (forward(..., return_readout=True))
+            keep["desc"], keep["wsp"] = d, wsp             # what a train_heads backward reads: zc, token, x (the stack's output), det_row
         if o is None:
             o = self._alloc_outputs(P, Pn, dev)
         offset, loc, rotmat, rotvec, shape, expression = o["offset"], o["loc"], o["rotmat"], o["rotvec"], o["shape"], o["expression"]
