@@ -160,6 +160,23 @@ typedef struct {
  * ctx16: op16 [>= B*N rows, ldctx]; columns [0, C) receive the 16-bit copy of feat32.                       */
 int mhmr_vit_forward(const mhmr_vit_desc* d, const float* x, float* feat32, void* ctx16, int ldctx, void* stream);
 
+/* Which launch sequence mhmr_vit_forward runs for this description on this stream, on this device, under the environment switches of this
+ * process: decided by the very function the forward calls, so the answer is what a forward issued now would run.  Host only: launches
+ * nothing and reads no device memory (tests assert the form they meant to exercise; a NULL optional workspace steps a form down silently
+ * otherwise).  Returns what mhmr_vit_forward would return before its first launch (MHMR_ERR_BAD_SHAPE / MHMR_ERR_BAD_ARG). */
+#define MHMR_VIT_FORM_ROWMAP 0x001u      /* block GEMMs over the B*N patch rows, class rows through mhmr_cls_linear16's kernel  */
+#define MHMR_VIT_FORM_ALLROWS256 0x002u  /* every block linear on the 256x256 kernel over all B*Tp rows                          */
+#define MHMR_VIT_FORM_NMASK 0x004u       /* C = 384: C-wide linears as N = 512 with masked columns (cpad)                        */
+#define MHMR_VIT_FORM_FOLD 0x008u        /* LayerNorm folded into the consuming linears                                          */
+#define MHMR_VIT_FORM_LO8_RANGES 0x010u  /* fp8 low-half ranges of v_w8 / proj_w8 run                                            */
+#define MHMR_VIT_FORM_CST 0x020u         /* row statistics inside the class-row launches (cls_pstats)                            */
+#define MHMR_VIT_FORM_AO 0x040u          /* any-order launches                                                                   */
+#define MHMR_VIT_FORM_SPLITK 0x080u      /* split-k residual linears                                                             */
+#define MHMR_VIT_FORM_QKV_MERGE 0x100u   /* Q | K | V as one launch + transpose (blocks whose V has no low half)                 */
+#define MHMR_VIT_FORM_FC1MAP 0x200u      /* fc1 alone under the token-row map                                                    */
+#define MHMR_VIT_FORM_X3 0x400u          /* the f16x3 forward: none of the other bits                                            */
+int mhmr_vit_form_bits(const mhmr_vit_desc* d, void* stream, unsigned* bits);
+
 /* Building blocks, exported for unit tests and bisecting. */
 int mhmr_gemm16(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,
                 const float* gamma, void* out, int ldo, const float* pos, int Np, int Tp, int H, int Mvalid, int epi,

@@ -21,6 +21,9 @@ ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 EPI_OP16, EPI_OP16_GELU, EPI_OP16_RELU, EPI_RESID, EPI_PATCH, EPI_F32, EPI_VT, EPI_OP16_QK = range(8)
 ATTN_QSCALE = 0.18033688011112042   # include/mhmr.h MHMR_ATTN_QSCALE
 
+#: include/mhmr.h MHMR_VIT_FORM_*: the bits of mhmr_vit_form_bits, in bit order
+VIT_FORM_BITS = ("rowmap", "allrows256", "nmask", "fold", "lo8_ranges", "cst", "ao", "splitk", "qkv_merge", "fc1map", "x3")
+
 _vp, _fp, _ip, _i, _f = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float  # all device pointers are void*
 
 
@@ -235,6 +238,7 @@ _SIGS = {
     "mhmr_version": ([], _i),
     "mhmr_source_hash": ([], C.c_char_p),
     "mhmr_vit_forward": ([C.POINTER(VitDesc), _vp, _vp, _vp, _i, _vp], _i),
+    "mhmr_vit_form_bits": ([C.POINTER(VitDesc), _vp, C.POINTER(C.c_uint)], _i),
     "mhmr_gemm16": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mhmr_gemm16_ex": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mhmr_gemm16_ln": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),

@@ -386,6 +386,8 @@ struct VitForm {
     // token-row map and its class rows the skinny kernel; the padding rows of `hid` are then never written (they stay as allocated:
     // zero) and nobody reads what the padding rows of the residual stream become.
     bool fc1map = false;
+    // mhmr_vit_desc.x3: the f16x3 forward (vit_forward_x3) runs, and nothing above applies
+    bool x3 = false;
 };
 
 VitForm vit_form(const mhmr_vit_desc* d, const VitSwitches& w, int ncu, bool anyorder_stream) {
@@ -637,21 +639,41 @@ int vit_launch(const mhmr_vit_desc* d, const VitForm& f, const float* x, float* 
     return mhmr_launch_final_norm(d->resid, d->norm_w, d->norm_b, ctx16, ldctx, feat32, B, d->N, Tp, C, 1e-6f, dt, s);
 }
 
+// The shape rules of a description and its form: what mhmr_vit_forward runs and what mhmr_vit_form_bits reports.
+int vit_form_of(const mhmr_vit_desc* d, hipStream_t s, VitForm* f) {
+    if (d->S % 14 || d->G * 14 != d->S || d->N != d->G * d->G || d->T != d->N + 1 || d->Tp % 64 || d->Tp < d->T ||
+        d->C != d->H * 64 || d->Kp % 64 || d->Kp < 588 || (d->C != 384 && d->C != 768 && d->C != 1024))
+        return MHMR_ERR_BAD_SHAPE;
+    if (d->x3) { *f = VitForm{}; f->x3 = true; return 0; }      // vit_forward_x3: none of the choices below exists there
+    const VitSwitches w = vit_switches();
+    *f = vit_form(d, w, mhmr_cu_count(), w.anyorder && stream_takes_anyorder(s));
+    return f->rc;
+}
+
 }  // namespace
 
 extern "C" {
 
 int mhmr_vit_forward(const mhmr_vit_desc* d, const float* x, float* feat32, void* ctx16, int ldctx, void* stream) {
     if (!d || !x || !feat32 || !ctx16) return MHMR_ERR_BAD_ARG;
-    if (d->S % 14 || d->G * 14 != d->S || d->N != d->G * d->G || d->T != d->N + 1 || d->Tp % 64 || d->Tp < d->T ||
-        d->C != d->H * 64 || d->Kp % 64 || d->Kp < 588 || (d->C != 384 && d->C != 768 && d->C != 1024))
-        return MHMR_ERR_BAD_SHAPE;
     hipStream_t s = (hipStream_t)stream;
-    if (d->x3) return vit_forward_x3(d, x, feat32, ctx16, ldctx, s);
-    const VitSwitches w = vit_switches();
-    const VitForm f = vit_form(d, w, mhmr_cu_count(), w.anyorder && stream_takes_anyorder(s));
-    if (f.rc) return f.rc;
+    VitForm f;
+    const int rc = vit_form_of(d, s, &f);
+    if (rc) return rc;
+    if (f.x3) return vit_forward_x3(d, x, feat32, ctx16, ldctx, s);
     return vit_launch(d, f, x, feat32, ctx16, ldctx, s);
+}
+
+int mhmr_vit_form_bits(const mhmr_vit_desc* d, void* stream, unsigned* bits) {
+    if (!d || !bits) return MHMR_ERR_BAD_ARG;
+    VitForm f;
+    const int rc = vit_form_of(d, (hipStream_t)stream, &f);
+    if (rc) return rc;
+    *bits = (f.rowmap ? MHMR_VIT_FORM_ROWMAP : 0u) | (f.allrows256 ? MHMR_VIT_FORM_ALLROWS256 : 0u) | (f.nmask ? MHMR_VIT_FORM_NMASK : 0u) |
+            (f.fold ? MHMR_VIT_FORM_FOLD : 0u) | (f.lo8_ranges ? MHMR_VIT_FORM_LO8_RANGES : 0u) | (f.cst ? MHMR_VIT_FORM_CST : 0u) |
+            (f.ao ? MHMR_VIT_FORM_AO : 0u) | (f.splitk ? MHMR_VIT_FORM_SPLITK : 0u) | (f.qkv_merge ? MHMR_VIT_FORM_QKV_MERGE : 0u) |
+            (f.fc1map ? MHMR_VIT_FORM_FC1MAP : 0u) | (f.x3 ? MHMR_VIT_FORM_X3 : 0u);
+    return 0;
 }
 
 int mhmr_detect_scores(const void* hid16, int ld, const float* w2, const float* b2, float* scores, int rows, int C, int dtype,

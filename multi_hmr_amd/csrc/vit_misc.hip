@@ -109,8 +109,13 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         [[maybe_unused]] hv hl;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-            y[e] = v[i][e] * rstd * w[e] + bb[e];
-            h[e] = (T)y[e];
+            float ye = v[i][e] * rstd * w[e] + bb[e];
+            // final norm: ctx16 is the 16-bit copy OF feat32 (include/mhmr.h).  Left to itself the f16 conversion fuses with the multiply-add
+            // (v_fma_mixlo_f16: ONE rounding of the exact sum), which differs from op16 of the stored fp32 value where that value sits on a
+            // 16-bit tie -- one element in 2^14 by expectation, one unit in the last place (tests/test_gpu_vit_forms.py, check D)
+            if constexpr (FINAL) asm volatile("" : "+v"(ye));
+            y[e] = ye;
+            h[e] = (T)ye;
             if constexpr (PAIR) hl[e] = (T)(y[e] - (float)h[e]);
         }
         *(hv*)(o16 + c) = h;
