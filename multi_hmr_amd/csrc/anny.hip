@@ -2,6 +2,7 @@
 // person parameters).  Tiny per-image / per-person kernels; all fp32.
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
+#include "hph_shared.h"
 
 namespace {
 
@@ -25,20 +26,10 @@ template <int DT>
 __global__ __launch_bounds__(256) void anny_score_kernel(const void* __restrict__ hid_, int ld, const float* __restrict__ w2,
                                                          const float* __restrict__ b2, float* __restrict__ scores,
                                                          float* __restrict__ logits, int rows, int C) {
-    typedef typename Op<DT>::T T;
-    typedef typename Op<DT>::V2 V2;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const T* hp = (const T*)hid_ + (size_t)row * ld;
-    float s = 0.f;
-    for (int c = lane * 2; c < C; c += 128) {
-        const V2 h = *(const V2*)(hp + c);
-        s += (float)h[0] * w2[c] + (float)h[1] * w2[c + 1];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    s += b2[0];
+    const float s = score_dot<DT>(hid_, ld, w2, row, lane, C) + b2[0];
     if (lane == 0) {
         logits[row] = s;
         scores[row] = 1.0f / (1.0f + expf(-s));
@@ -60,49 +51,15 @@ __global__ void anny_decode_kernel(const float* __restrict__ rot6d, const float*
     const int p = blockIdx.x, j = threadIdx.x;
     if (j < J) {
         const float* dp = rot6d + ((size_t)p * J + j) * 6;
-        float x0 = dp[0], x1 = dp[2], x2 = dp[4];
-        float y0 = dp[1], y1 = dp[3], y2 = dp[5];
-        const float nx = sqrtf(x0 * x0 + x1 * x1 + x2 * x2);
-        x0 /= nx; x1 /= nx; x2 /= nx;
-        const float dxy = x0 * y0 + x1 * y1 + x2 * y2;
-        y0 -= dxy * x0; y1 -= dxy * x1; y2 -= dxy * x2;
-        const float ny = sqrtf(y0 * y0 + y1 * y1 + y2 * y2);
-        y0 /= ny; y1 /= ny; y2 /= ny;
-        const float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
-        float R[9] = {x0, y0, z0, x1, y1, z1, x2, y2, z2};
+        float R[9];
+        rot6d_to_rotmat(dp[0], dp[2], dp[4], dp[1], dp[3], dp[5], R);
         const float u = useful[j];
 #pragma unroll
         for (int e = 0; e < 9; ++e) R[e] = u * R[e] + (1.f - u) * ((e % 4 == 0) ? 1.f : 0.f);
         float* rp = rotmat + ((size_t)p * J + j) * 9;
 #pragma unroll
         for (int e = 0; e < 9; ++e) rp[e] = R[e];
-        const float tr = R[0] + R[4] + R[8];
-        float qx, qy, qz, qw;
-        int choice = 0;
-        float best = R[0];
-        if (R[4] > best) { best = R[4]; choice = 1; }
-        if (R[8] > best) { best = R[8]; choice = 2; }
-        if (tr > best) { best = tr; choice = 3; }
-        if (choice == 3) {
-            qx = R[7] - R[5]; qy = R[2] - R[6]; qz = R[3] - R[1]; qw = 1.f + tr;
-        } else {
-            const int i = choice, jj = (i + 1) % 3, kk = (jj + 1) % 3;
-            float qq[3];
-            qq[i] = 1.f - tr + 2.f * R[i * 3 + i];
-            qq[jj] = R[jj * 3 + i] + R[i * 3 + jj];
-            qq[kk] = R[kk * 3 + i] + R[i * 3 + kk];
-            qw = R[kk * 3 + jj] - R[jj * 3 + kk];
-            qx = qq[0]; qy = qq[1]; qz = qq[2];
-        }
-        const float qn = sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
-        qx /= qn; qy /= qn; qz /= qn; qw /= qn;
-        if (qw < 0.f) { qx = -qx; qy = -qy; qz = -qz; qw = -qw; }
-        const float angle = 2.f * atan2f(sqrtf(qx * qx + qy * qy + qz * qz), qw);
-        float sc;
-        if (fabsf(angle) <= 1e-3f) sc = 2.f + angle * angle / 12.f + 7.f * angle * angle * angle * angle / 2880.f;
-        else sc = angle / sinf(angle / 2.f);
-        float* vp = rotvec + ((size_t)p * J + j) * 3;
-        vp[0] = sc * qx; vp[1] = sc * qy; vp[2] = sc * qz;
+        rotmat_to_rotvec(R, rotvec + ((size_t)p * J + j) * 3);
     }
     if (j < nb) shape[(size_t)p * nb + j] = 1.0f / (1.0f + expf(-shape_logit[(size_t)p * nb + j]));
     if (j == 0) {
@@ -113,7 +70,7 @@ __global__ void anny_decode_kernel(const float* __restrict__ rot6d, const float*
         const float* k = Kmat + 9 * det_b[p];
         const float d = k[0] / fmaxf(expf(dist_logit[p]), 1e-5f);
         dist[p] = d;
-        // inverse of the 3x3 K by the adjugate (torch.inverse in the reference)
+        // inverse of the 3x3 K by the adjugate (torch.inverse in the reference); every cofactor DIVIDED by det: not inv3x3, which rounds otherwise
         const float a = k[0], b = k[1], c = k[2], dd = k[3], e = k[4], f = k[5], g = k[6], h = k[7], i = k[8];
         const float A = e * i - f * h, Bc = -(dd * i - f * g), Cc = dd * h - e * g;
         const float det = a * A + b * Bc + c * Cc;

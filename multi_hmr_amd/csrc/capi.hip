@@ -1,5 +1,5 @@
-// extern "C" entry points of libmhmr.so (declared in include/mhmr.h): the ViT and HPH forward orchestration
-// (pure launch sequences on the caller's stream, no allocation, no synchronisation) and the hipEvent profiler.
+// extern "C" entry points of libmhmr.so (declared in include/mhmr.h): the ViT forward orchestration (pure launch sequences on the
+// caller's stream, no allocation, no synchronisation) and the hipEvent profiler.  The person head's entry points are in hph.hip.
 #include <vector>
 #include <mutex>
 #include "mhmr_common.h"
@@ -48,12 +48,6 @@ void prof_end(int kind, hipStream_t s, double work) {
     if (e) (void)hipEventRecord(e, s);
     g_prof.work += work;
 }
-
-#define TRY(expr)                 \
-    do {                          \
-        int rc__ = (expr);        \
-        if (rc__ != 0) return rc__; \
-    } while (0)
 
 extern "C" {
 
@@ -674,134 +668,6 @@ int mhmr_vit_form_bits(const mhmr_vit_desc* d, void* stream, unsigned* bits) {
             (f.ao ? MHMR_VIT_FORM_AO : 0u) | (f.splitk ? MHMR_VIT_FORM_SPLITK : 0u) | (f.qkv_merge ? MHMR_VIT_FORM_QKV_MERGE : 0u) |
             (f.fc1map ? MHMR_VIT_FORM_FC1MAP : 0u) | (f.x3 ? MHMR_VIT_FORM_X3 : 0u);
     return 0;
-}
-
-int mhmr_detect_scores(const void* hid16, int ld, const float* w2, const float* b2, float* scores, int rows, int C, int dtype,
-                       void* stream) {
-    return mhmr_launch_scores(hid16, ld, w2, b2, scores, rows, C, dtype, (hipStream_t)stream);
-}
-int mhmr_detect_count(const float* scores, int B, int G, int nms_kernel, float thr, int* counts, void* stream) {
-    if (nms_kernel < 1 || B <= 0) return MHMR_ERR_BAD_ARG;
-    return mhmr_launch_detect_count(scores, B, G, nms_kernel, thr, counts, (hipStream_t)stream);
-}
-int mhmr_detect_write(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b, int* det_y,
-                      int* det_x, float* det_score, void* stream) {
-    if (nms_kernel < 1 || B <= 0) return MHMR_ERR_BAD_ARG;
-    return mhmr_launch_detect_write(scores, B, G, nms_kernel, thr, base, det_b, det_y, det_x, det_score, 0x7fffffff, (hipStream_t)stream);
-}
-int mhmr_detect_write_cap(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b, int* det_y,
-                          int* det_x, float* det_score, int cap, void* stream) {
-    if (nms_kernel < 1 || B <= 0 || cap < 0) return MHMR_ERR_BAD_ARG;
-    return mhmr_launch_detect_write(scores, B, G, nms_kernel, thr, base, det_b, det_y, det_x, det_score, cap, (hipStream_t)stream);
-}
-int mhmr_person_groups(const int* counts, const int* det_b, int P, int B, int cap, int* base, int* gstart, int ngroups_cap, int* chunks,
-                       int nchunks_cap, int* info, void* stream) {
-    return mhmr_launch_person_groups(counts, det_b, P, B, cap, base, gstart, ngroups_cap, chunks, nchunks_cap, info, (hipStream_t)stream);
-}
-int mhmr_camera_embed(const float* K, const float* freq, int B, int G, int patch, float* zK, void* ctx16, int ldctx, int C,
-                      int dtype, int num_bands, void* stream) {
-    return mhmr_launch_camera_embed(K, freq, B, G, patch, zK, ctx16, ldctx, C, dtype, num_bands, (hipStream_t)stream);
-}
-int mhmr_linear_f32(const float* X, int ldx, const int* row_idx, const float* W, int ldw, const float* bias, const float* R,
-                    int ldr, float* Y, int ldy, int M, int N, int K, int act, void* stream) {
-    return mhmr_launch_linear_f32(X, ldx, row_idx, W, ldw, bias, R, ldr, Y, ldy, M, N, K, act, (hipStream_t)stream);
-}
-int mhmr_layernorm_f32(const float* in, const float* w, const float* b, float* out, int rows, int C, float eps, void* stream) {
-    return mhmr_launch_layernorm_f32(in, w, b, out, rows, C, eps, (hipStream_t)stream);
-}
-int mhmr_hph_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads, void* stream) {
-    if (heads <= 0) return MHMR_ERR_BAD_SHAPE;
-    return mhmr_launch_hph_self_attn(qkv, gstart, out, ngroups, nmax, heads, (hipStream_t)stream);
-}
-int mhmr_hph_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N, void* stream) {
-    if (heads <= 0 || N <= 0) return MHMR_ERR_BAD_SHAPE;
-    return mhmr_launch_hph_cross_attn(q, kv, chunks, nchunks, out, heads, N, (hipStream_t)stream);
-}
-int mhmr_hph_decode(const float* dec, int ldd, int nb, const float* K, const int* det_b, float fn, int nearness, float* rotmat,
-                    float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, void* stream) {
-    if (nb < 0 || nb > 64 || ldd < 318 + nb + 3 + 10) return MHMR_ERR_BAD_SHAPE;      // one thread per beta in a 64-thread block
-    return mhmr_launch_hph_decode(dec, ldd, nb, K, det_b, fn, nearness, rotmat, rotvec, betas, expr, dist_pp, dist, P, (hipStream_t)stream);
-}
-
-// The decode + loc of mhmr_hph_forward on a caller's read-out: the same two kernels, hence the same bits.
-int mhmr_heads_decode(const mhmr_heads_decode_desc* d, void* stream) {
-    if (!d || d->P < 0) return MHMR_ERR_BAD_ARG;
-    if (d->nb < 0 || d->nb > 64 || d->ldr < 318 + d->nb + 3 + 10) return MHMR_ERR_BAD_SHAPE;
-    if (d->P == 0) return 0;
-    if (!d->readout || !d->offset || !d->K || !d->det_b || !d->det_y || !d->det_x || !d->loc || !d->rotmat || !d->rotvec || !d->shape ||
-        !d->expression || !d->dist_postprocessed || !d->dist)
-        return MHMR_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    TRY(mhmr_launch_loc(d->offset, d->det_y, d->det_x, d->patch, d->loc, d->P, s));
-    return mhmr_launch_hph_decode(d->readout, d->ldr, d->nb, d->K, d->det_b, d->fn, d->nearness, d->rotmat, d->rotvec, d->shape, d->expression,
-                                  d->dist_postprocessed, d->dist, d->P, s);
-}
-
-// `depth` x (pre-norm self-attention among the queries of one image, cross-attention over that image's N context
-// tokens, GELU feed-forward), each with a residual.  Shared by the Multi-HMR HPH (dim 1024, 8 heads, mlp 1024, depth 2,
-// blocks/cross_attn_transformer.py:239-261) and the Anny HPH (dim 512, 16 heads, mlp 2048, depth 8,
-// multi_hmr_anny/hph.py:114-151).  Queries are ragged groups (no padding), so the reference's mask arithmetic vanishes.
-int mhmr_xattn_layers_forward(const mhmr_hph_layer* layers, int depth, int dim, int heads, int mlp, int Kc, int N, int B,
-                              int dtype, float* x, float* xn, float* t1, float* t2, float* kv, const void* ctx16,
-                              const int* gstart, int ngroups, int nmax, const int* chunks, int nchunks, int P, void* stream) {
-    if (!layers || P < 0 || depth < 0) return MHMR_ERR_BAD_ARG;
-    if (P == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int inner = heads * 32;
-    if (Kc % 64 || dim % 64 || dim > 2048 || mlp % 16 || (2 * inner) % 128) return MHMR_ERR_BAD_SHAPE;
-    const int Mctx = (B * N + 127) / 128 * 128;
-    for (int l = 0; l < depth; ++l) {
-        const mhmr_hph_layer& L = layers[l];
-        // self-attention among the queries of one image
-        TRY(mhmr_launch_layernorm_f32(x, L.ln_sa_w, L.ln_sa_b, xn, P, dim, 1e-5f, s));
-        TRY(mhmr_launch_linear_f32(xn, dim, nullptr, L.to_qkv, dim, nullptr, nullptr, 0, t1, 3 * inner, P, 3 * inner, dim, MHMR_ACT_NONE, s));
-        TRY(mhmr_launch_hph_self_attn(t1, gstart, t2, ngroups, nmax, heads, s));
-        TRY(mhmr_launch_linear_f32(t2, inner, nullptr, L.sa_out_w, inner, L.sa_out_b, x, dim, x, dim, P, dim, inner, MHMR_ACT_NONE, s));
-        // cross-attention over the (un-normalised) per-image context
-        {
-            GemmArgs g{ctx16, Kc, L.to_kv16, Kc, Mctx, 2 * inner, Kc, nullptr, nullptr, kv, 2 * inner, nullptr, 0, 128, 1, Mctx, EPI_F32};
-            TRY(mhmr_launch_gemm(g, dtype, s));
-        }
-        TRY(mhmr_launch_layernorm_f32(x, L.ln_ca_w, L.ln_ca_b, xn, P, dim, 1e-5f, s));
-        TRY(mhmr_launch_linear_f32(xn, dim, nullptr, L.to_q, dim, nullptr, nullptr, 0, t1, inner, P, inner, dim, MHMR_ACT_NONE, s));
-        TRY(mhmr_launch_hph_cross_attn(t1, kv, chunks, nchunks, t2, heads, N, s));
-        TRY(mhmr_launch_linear_f32(t2, inner, nullptr, L.ca_out_w, inner, L.ca_out_b, x, dim, x, dim, P, dim, inner, MHMR_ACT_NONE, s));
-        // feed-forward
-        TRY(mhmr_launch_layernorm_f32(x, L.ln_ff_w, L.ln_ff_b, xn, P, dim, 1e-5f, s));
-        TRY(mhmr_launch_linear_f32(xn, dim, nullptr, L.ff1_w, dim, L.ff1_b, nullptr, 0, t1, mlp, P, mlp, dim, MHMR_ACT_GELU, s));
-        TRY(mhmr_launch_linear_f32(t1, mlp, nullptr, L.ff2_w, mlp, L.ff2_b, x, dim, x, dim, P, dim, mlp, MHMR_ACT_NONE, s));
-    }
-    return 0;
-}
-
-int mhmr_hph_forward(const mhmr_hph_desc* d, const float* feat32, const float* zK, void* ctx16, const int* det_b,
-                     const int* det_y, const int* det_x, int P, const int* gstart, int ngroups, int nmax, const int* chunks,
-                     int nchunks, const float* K, int B, float* offset, float* loc, float* rotmat, float* rotvec, float* betas,
-                     float* expr, float* dist_pp, float* dist, void* stream) {
-    if (!d || P < 0) return MHMR_ERR_BAD_ARG;
-    if (P == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int C = d->C, dim = d->dim;
-    if (d->Ktok % 16 || d->Kc % 64 || C % 16 || dim % 64 || d->mlp % 16 || (2 * d->heads * 32) % 128) return MHMR_ERR_BAD_SHAPE;
-    if (d->nb < 0 || d->nb > 64) return MHMR_ERR_BAD_SHAPE;          // the decode writes betas with one thread each of 64
-
-    // queries, mlp_offset input, context rows of the detected cells  (model.py:255-265, 500-517, 541-552)
-    TRY(mhmr_launch_hph_inputs(feat32, zK, det_b, det_y, det_x, d->cq_x, d->cq_y, d->cv_x, d->cv_y, d->init_tail,
-                               318 + d->nb + 3, d->zc, d->token, d->Ktok, ctx16, d->Kc, d->det_row, P, d->G, C, d->dtype, d->nvalid,
-                               d->cam_dim > 0 ? d->cam_dim : 99, s));
-    // mlp_offset (model.py:258) and loc (272-275)
-    TRY(mhmr_launch_linear_f32(d->zc, C, nullptr, d->off1_w, C, d->off1_b, nullptr, 0, d->t1, C, P, C, C, MHMR_ACT_RELU, s));
-    TRY(mhmr_launch_linear_f32(d->t1, C, nullptr, d->off2_w, C, d->off2_b, nullptr, 0, offset, 2, P, 2, C, MHMR_ACT_NONE, s));
-    TRY(mhmr_launch_loc(offset, det_y, det_x, d->patch, loc, P, s));
-    // token embedding (+ pos_embedding folded into the bias)  (cross_attn_transformer.py:352-357)
-    TRY(mhmr_launch_linear_f32(d->token, d->Ktok, nullptr, d->tok_w, d->Ktok, d->tok_b, nullptr, 0, d->x, dim, P, dim, d->Ktok,
-                               MHMR_ACT_NONE, s));
-    TRY(mhmr_xattn_layers_forward(d->layers, d->depth, dim, d->heads, d->mlp, d->Kc, d->N, B, d->dtype, d->x, d->xn, d->t1, d->t2, d->kv,
-                                  ctx16, gstart, ngroups, nmax, chunks, nchunks, P, stream));
-    // read-outs + init (model.py:571-575), 6D -> rotmat -> rotvec, distance post-processing
-    TRY(mhmr_launch_linear_f32(d->x, dim, nullptr, d->dec_w, dim, d->dec_b, nullptr, 0, d->dec, d->Ndec, P, d->Ndec, dim, MHMR_ACT_NONE, s));
-    return mhmr_launch_hph_decode(d->dec, d->Ndec, d->nb, K, det_b, d->fn, d->nearness, rotmat, rotvec, betas, expr, dist_pp,
-                                  dist, P, s);
 }
 
 }  // extern "C"

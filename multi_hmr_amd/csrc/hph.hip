@@ -4,16 +4,13 @@
 // (v_mfma_f32_16x16x4_f32 == an fmaf chain), attention over the ragged per-image query groups is done with
 // lanes = queries (self-attention) or lanes = 8 queries x 8 key slices (cross-attention over the N patch
 // tokens) and an online softmax; padded queries of the reference never exist here.
+// The person head's extern "C" entry points and its one decoder layer (forward and the backward's tape) are at the end of this file; what
+// the backward's kernels recompute of the forward is in hph_shared.h.
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
+#include "hph_shared.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // Y[m][n] = act( sum_k X[row(m)][k] * W[n][k] + bias[n] ) (+ R[m][n]);  K % 16 == 0 (callers pad with zeros).
@@ -127,19 +124,9 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* ip = in + (size_t)row * C;
-    float v[32];
+    float v[32], mean, rstd;
     const int n = C / 64;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        if (i < n) { v[i] = ip[i * 64 + lane]; s += v[i]; }
-    const float mean = wave_sum(s) / C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        if (i < n) { v[i] -= mean; q += v[i] * v[i]; }
-    const float rstd = rsqrtf(wave_sum(q) / C + eps);
+    ln_row_stats(in + (size_t)row * C, lane, C, eps, v, mean, rstd);
 #pragma unroll
     for (int i = 0; i < 32; ++i)
         if (i < n) out[(size_t)row * C + i * 64 + lane] = v[i] * rstd * gw[i * 64 + lane] + gb[i * 64 + lane];
@@ -151,18 +138,10 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
 template <int DT>
 __global__ __launch_bounds__(256) void score_kernel(const void* __restrict__ hid_, int ld, const float* __restrict__ w2,
                                                     const float* __restrict__ b2, float* __restrict__ scores, int rows, int C) {
-    typedef typename Op<DT>::T T;
-    typedef typename Op<DT>::V2 V2;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const T* hp = (const T*)hid_ + (size_t)row * ld;
-    float s = 0.f;
-    for (int c = lane * 2; c < C; c += 128) {
-        const V2 h = *(const V2*)(hp + c);
-        s += (float)h[0] * w2[c] + (float)h[1] * w2[c + 1];
-    }
-    s = wave_sum(s) + b2[0];
+    const float s = score_dot<DT>(hid_, ld, w2, row, lane, C) + b2[0];
     if (lane == 0) scores[row] = fminf(fmaxf(1.0f / (1.0f + expf(-s)), 1e-4f), 1.0f - 1e-4f);
 }
 
@@ -289,16 +268,6 @@ __global__ __launch_bounds__(256) void person_groups_kernel(const int* __restric
 // z_K = [ray(3), sin(pi*ray_a*f_k) (a*16+k), cos(...)] = 99 channels.  Also writes the 16-bit copy into the
 // cross-attention context operand ctx16[:, C : C+99] and zeros ctx16[:, C+99 : Kc].
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void inv3x3(const float* k, float* o) {
-    const float a = k[0], b = k[1], c = k[2], d = k[3], e = k[4], f = k[5], g = k[6], h = k[7], i = k[8];
-    const float A = e * i - f * h, B = -(d * i - f * g), Cc = d * h - e * g;
-    const float det = a * A + b * B + c * Cc;
-    const float id = 1.0f / det;
-    o[0] = A * id; o[1] = -(b * i - c * h) * id; o[2] = (b * f - c * e) * id;
-    o[3] = B * id; o[4] = (a * i - c * g) * id;  o[5] = -(a * f - c * d) * id;
-    o[6] = Cc * id; o[7] = -(a * h - b * g) * id; o[8] = (a * e - b * d) * id;
-}
-
 template <int DT>
 __global__ __launch_bounds__(128) void camera_embed_kernel(const float* __restrict__ Kmat, const float* __restrict__ freq,
                                                            int G, int patch, float* __restrict__ zK, void* __restrict__ ctx16_,
@@ -385,25 +354,8 @@ __global__ __launch_bounds__(64) void hph_self_attn_kernel(const float* __restri
     const int qi = blockIdx.z * 64 + threadIdx.x;
     if (blockIdx.z * 64 >= n) return;
     const bool active = qi < n;
-    const int ld = 3 * inner;
-    const float* qp = qkv + (size_t)(s0 + (active ? qi : 0)) * ld + h * 32;
-    float q[32], o[32];
-#pragma unroll
-    for (int d = 0; d < 32; ++d) { q[d] = qp[d] * scale; o[d] = 0.f; }
-    float m = -INFINITY, l = 0.f;
-    for (int j = 0; j < n; ++j) {
-        const float* kp = qkv + (size_t)(s0 + j) * ld + inner + h * 32;
-        const float* vp = kp + inner;
-        float s = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) s += q[d] * kp[d];
-        const float mn = fmaxf(m, s);
-        const float a = expf(m - mn), pj = expf(s - mn);
-        l = l * a + pj;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) o[d] = o[d] * a + pj * vp[d];
-        m = mn;
-    }
+    float q[32], o[32], m, l;
+    self_attn_row(qkv, qkv + (size_t)(s0 + (active ? qi : 0)) * (3 * inner) + h * 32, s0, n, inner, h, scale, q, o, m, l);
     if (active) {
         const float inv = 1.0f / l;
         float* op = out + (size_t)(s0 + qi) * inner + h * 32;
@@ -413,100 +365,20 @@ __global__ __launch_bounds__(64) void hph_self_attn_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Cross-attention of the queries of image b over its N context tokens (CrossAttention.forward :185-205).
-// q: [P, inner]; kv: [B*N, 2*inner] (k | v) fp32.  One workgroup of CA_WAVES waves per (chunk of <= 8 queries, head):
-// lane = slice*8 + qi, wave w's slice s handles keys j = s + 8 w (mod 8 CA_WAVES); the 8 partial (m, l, o) per query of a
-// wave are merged with 3 xor-shuffle rounds, the CA_WAVES wave results through LDS in wave order (deterministic).  The loop
-// is latency-bound (one 256-byte K|V row pair per lane-slice per trip): a single wave per (chunk, head) walked 512 trips at
-// N = 4096 (0.56 ms per layer); 8 waves walk 64 each.
+// Cross-attention of the queries of image b over its N context tokens (CrossAttention.forward :185-205): cross_attn_row
+// (hph_shared.h) with one workgroup of CA_WAVES waves per (work item of <= 8 queries, head); out = o / l.
 // chunks: (image b, first query, count) int triples (person_groups_kernel, or the host); count 0 = padding of the work list.
 // ------------------------------------------------------------------------------------------------------------
-constexpr int CA_WAVES = 8;
 __global__ __launch_bounds__(64 * CA_WAVES) void hph_cross_attn_kernel(const float* __restrict__ q, const float* __restrict__ kv,
                                                             const int* __restrict__ chunks, int ncap, float* __restrict__ out, int inner,
                                                             int N, float scale) {
-    // 1-D grid of ncap x heads workgroups over a work list of ncap entries whose tail may be padding (count 0: person_groups_kernel
-    // pads up to the launch's upper bound).  The real work is the FIRST nc x heads workgroups: the dispatcher hands out workgroups in
-    // index order, two per CU -- with the padding interleaved (a 2-D grid, real chunks 0..31 of 64 in every row) half of the CUs
-    // received two real workgroups and the other half two that return at once: 221 instead of 118 us per layer.
-    const int nc = __syncthreads_count(threadIdx.x < ncap && chunks[3 * threadIdx.x + 2] > 0);      // (ncap <= 512: the launcher)
-    const int heads = inner >> 5;
-    if ((int)blockIdx.x >= nc * heads) return;
-    const int ch = blockIdx.x % nc, h = blockIdx.x / nc;
-    const int b = chunks[3 * ch], q0 = chunks[3 * ch + 1], nq = chunks[3 * ch + 2];
-    __shared__ float part[CA_WAVES][8][34];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, qi = lane & 7, sl = lane >> 3;
-    const bool active = qi < nq;
-    const float* qp = q + (size_t)(q0 + (active ? qi : 0)) * inner + h * 32;
-    float qv[32], o[32];
+    CrossAttnItem it;
+    float mt, lt, o[32];
+    if (!cross_attn_row(q, kv, chunks, ncap, inner, N, scale, it, mt, lt, o)) return;
+    const float inv = 1.0f / lt;
+    float* op = out + it.qrow * inner + it.h * 32;
 #pragma unroll
-    for (int d = 0; d < 32; ++d) { qv[d] = qp[d] * scale; o[d] = 0.f; }
-    float m = -INFINITY, l = 0.f;
-    const int ld = 2 * inner;
-    const float* kbase = kv + (size_t)b * N * ld + h * 32;
-    for (int j = sl + 8 * wv; j < N; j += 8 * CA_WAVES) {
-        const float* kp = kbase + (size_t)j * ld;
-        const float* vp = kp + inner;
-        float kk[32];
-#pragma unroll
-        for (int d = 0; d < 32; d += 4) *(f32x4*)(kk + d) = *(const f32x4*)(kp + d);
-        float s = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) s += qv[d] * kk[d];
-        if (s > m) {  // rare after the first few keys
-            const float a = expf(m - s);
-            l *= a;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) o[d] *= a;
-            m = s;
-        }
-        const float pj = expf(s - m);
-        l += pj;
-#pragma unroll
-        for (int d = 0; d < 32; d += 4) {
-            const f32x4 vv = *(const f32x4*)(vp + d);
-            o[d] += pj * vv[0]; o[d + 1] += pj * vv[1]; o[d + 2] += pj * vv[2]; o[d + 3] += pj * vv[3];
-        }
-    }
-    // merge the 8 key slices (lanes differing in bits 3..5)
-#pragma unroll
-    for (int off = 8; off < 64; off <<= 1) {
-        const float m2 = __shfl_xor(m, off), l2 = __shfl_xor(l, off);
-        const float mn = fmaxf(m, m2);
-        const float a1 = (m == -INFINITY) ? 0.f : expf(m - mn), a2 = (m2 == -INFINITY) ? 0.f : expf(m2 - mn);
-        l = l * a1 + l2 * a2;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) o[d] = o[d] * a1 + __shfl_xor(o[d], off) * a2;
-        m = mn;
-    }
-    // merge the waves: lanes 0..7 of every wave hold (m, l, o) of query qi over that wave's keys
-    if (sl == 0) {
-        part[wv][qi][32] = m;
-        part[wv][qi][33] = l;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) part[wv][qi][d] = o[d];
-    }
-    __syncthreads();
-    if (wv == 0 && active && sl == 0) {
-        float mt = part[0][qi][32];
-#pragma unroll
-        for (int w2 = 1; w2 < CA_WAVES; ++w2) mt = fmaxf(mt, part[w2][qi][32]);
-        float lt = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) o[d] = 0.f;
-#pragma unroll
-        for (int w2 = 0; w2 < CA_WAVES; ++w2) {
-            const float mw = part[w2][qi][32];
-            const float a = (mw == -INFINITY) ? 0.f : expf(mw - mt);
-            lt += part[w2][qi][33] * a;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) o[d] += part[w2][qi][d] * a;
-        }
-        const float inv = 1.0f / lt;
-        float* op = out + (size_t)(q0 + qi) * inner + h * 32;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) op[d] = o[d] * inv;
-    }
+    for (int d = 0; d < 32; ++d) op[d] = o[d] * inv;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -524,47 +396,14 @@ __global__ __launch_bounds__(64) void hph_decode_kernel(const float* __restrict_
     const float* dp = dec + (size_t)p * ldd;
     if (j < 53) {
         // 6D -> (2,3) -> transpose: first three numbers = column 0, next three = column 1
-        float x0 = dp[6 * j], x1 = dp[6 * j + 1], x2 = dp[6 * j + 2];
-        float y0 = dp[6 * j + 3], y1 = dp[6 * j + 4], y2 = dp[6 * j + 5];
-        const float nx = sqrtf(x0 * x0 + x1 * x1 + x2 * x2);
-        x0 /= nx; x1 /= nx; x2 /= nx;
-        const float dxy = x0 * y0 + x1 * y1 + x2 * y2;
-        y0 -= dxy * x0; y1 -= dxy * x1; y2 -= dxy * x2;
-        const float ny = sqrtf(y0 * y0 + y1 * y1 + y2 * y2);
-        y0 /= ny; y1 /= ny; y2 /= ny;
-        const float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
-        float R[9] = {x0, y0, z0, x1, y1, z1, x2, y2, z2};  // columns [x y z]
+        const float x0 = dp[6 * j], x1 = dp[6 * j + 1], x2 = dp[6 * j + 2];
+        const float y0 = dp[6 * j + 3], y1 = dp[6 * j + 4], y2 = dp[6 * j + 5];
+        float R[9];
+        rot6d_to_rotmat(x0, x1, x2, y0, y1, y2, R);
         float* rp = rotmat + ((size_t)p * 53 + j) * 9;
 #pragma unroll
         for (int e = 0; e < 9; ++e) rp[e] = R[e];
-        // rotmat -> unit quaternion (XYZW), branch on the largest of (R00, R11, R22, trace)
-        const float tr = R[0] + R[4] + R[8];
-        float qx, qy, qz, qw;
-        int choice = 0;  // argmax over (R00, R11, R22, trace), first maximal index wins
-        float best = R[0];
-        if (R[4] > best) { best = R[4]; choice = 1; }
-        if (R[8] > best) { best = R[8]; choice = 2; }
-        if (tr > best) { best = tr; choice = 3; }
-        if (choice == 3) {
-            qx = R[7] - R[5]; qy = R[2] - R[6]; qz = R[3] - R[1]; qw = 1.f + tr;
-        } else {
-            const int i = choice, jj = (i + 1) % 3, kk = (jj + 1) % 3;
-            float qq[3];
-            qq[i] = 1.f - tr + 2.f * R[i * 3 + i];
-            qq[jj] = R[jj * 3 + i] + R[i * 3 + jj];
-            qq[kk] = R[kk * 3 + i] + R[i * 3 + kk];
-            qw = R[kk * 3 + jj] - R[jj * 3 + kk];
-            qx = qq[0]; qy = qq[1]; qz = qq[2];
-        }
-        const float qn = sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
-        qx /= qn; qy /= qn; qz /= qn; qw /= qn;
-        if (qw < 0.f) { qx = -qx; qy = -qy; qz = -qz; qw = -qw; }
-        const float angle = 2.f * atan2f(sqrtf(qx * qx + qy * qy + qz * qz), qw);
-        float sc;
-        if (fabsf(angle) <= 1e-3f) sc = 2.f + angle * angle / 12.f + 7.f * angle * angle * angle * angle / 2880.f;
-        else sc = angle / sinf(angle / 2.f);
-        float* vp = rotvec + ((size_t)p * 53 + j) * 3;
-        vp[0] = sc * qx; vp[1] = sc * qy; vp[2] = sc * qz;
+        rotmat_to_rotvec(R, rotvec + ((size_t)p * 53 + j) * 3);
     }
     if (j < nb) betas[(size_t)p * nb + j] = dp[318 + j];
     if (j < 10) expr[(size_t)p * 10 + j] = dp[318 + nb + 3 + j];
@@ -589,7 +428,7 @@ __global__ void loc_kernel(const float* __restrict__ offset, const int* __restri
 
 }  // namespace
 
-// ---------------------------------------------------------------- launchers
+// ---------------------------------------------------------------- launchers that hph_bwd.hip also calls
 int mhmr_launch_linear_f32(const float* X, int ldx, const int* row_idx, const float* W, int ldw, const float* bias,
                            const float* R, int ldr, float* Y, int ldy, int M, int N, int K, int act, hipStream_t s) {
     if (M <= 0 || N <= 0 || K <= 0 || K % 16 || ldx % 4 || ldw % 4) return MHMR_ERR_BAD_SHAPE;
@@ -611,59 +450,23 @@ int mhmr_launch_layernorm_f32(const float* in, const float* w, const float* b, f
     return 0;
 }
 
-int mhmr_launch_scores(const void* hid, int ld, const float* w2, const float* b2, float* scores, int rows, int C, int dtype,
-                       hipStream_t s) {
-    if (C % 128) return MHMR_ERR_BAD_SHAPE;
-    if (dtype == MHMR_DT_F16)
-        hipLaunchKernelGGL((score_kernel<MHMR_DT_F16>), dim3((rows + 3) / 4), dim3(256), 0, s, hid, ld, w2, b2, scores, rows, C);
-    else
-        hipLaunchKernelGGL((score_kernel<MHMR_DT_BF16>), dim3((rows + 3) / 4), dim3(256), 0, s, hid, ld, w2, b2, scores, rows, C);
-    MHMR_CHECK_LAUNCH();
-    return 0;
-}
+// ---------------------------------------------------------------- launchers of this file alone
+namespace {
 
-static inline int nms_pad(int k) { return (k == 2) ? 1 : (k == 4) ? 2 : (k - 1) / 2; }
+inline int nms_pad(int k) { return (k == 2) ? 1 : (k == 4) ? 2 : (k - 1) / 2; }
 
-int mhmr_launch_detect_count(const float* scores, int B, int G, int nms_kernel, float thr, int* counts, hipStream_t s) {
-    hipLaunchKernelGGL(detect_count_kernel, dim3(B), dim3(256), 0, s, scores, G, nms_kernel, nms_pad(nms_kernel), thr, counts);
-    MHMR_CHECK_LAUNCH();
-    return 0;
-}
-
-int mhmr_launch_detect_write(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b,
-                             int* det_y, int* det_x, float* det_score, int cap, hipStream_t s) {
+int launch_detect_write(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b, int* det_y, int* det_x,
+                        float* det_score, int cap, hipStream_t s) {
     hipLaunchKernelGGL(detect_write_kernel, dim3(B), dim3(256), 0, s, scores, G, nms_kernel, nms_pad(nms_kernel), thr, base,
                        det_b, det_y, det_x, det_score, cap);
     MHMR_CHECK_LAUNCH();
     return 0;
 }
 
-int mhmr_launch_person_groups(const int* counts, const int* det_b, int P, int B, int cap, int* base, int* gstart, int ngcap, int* chunks,
-                              int nccap, int* info, hipStream_t s) {
-    if (B <= 0 || B > 8192 || P < 0 || cap < 0 || ngcap < 0 || nccap < 0 || !gstart || !info || (nccap > 0 && !chunks)) return MHMR_ERR_BAD_ARG;
-    if (!counts && P > 0 && !det_b) return MHMR_ERR_BAD_ARG;
-    const size_t lds = ((size_t)2 * B + (size_t)ngcap + 1 + (size_t)3 * nccap) * sizeof(int);
-    if (lds > 60 * 1024) return MHMR_ERR_BAD_SHAPE;          // (B = 8192 with the sufficient bounds is 160 KB: far beyond any batch)
-    hipLaunchKernelGGL(person_groups_kernel, dim3(1), dim3(256), lds, s, counts, det_b, P, B, cap, base, gstart, ngcap, chunks, nccap, info);
-    MHMR_CHECK_LAUNCH();
-    return 0;
-}
-
-int mhmr_launch_camera_embed(const float* Kmat, const float* freq, int B, int G, int patch, float* zK, void* ctx16, int Kc,
-                             int C, int dtype, int nbands, hipStream_t s) {
-    if (nbands < 1 || Kc - C > 128 || Kc - C < 3 + 6 * nbands) return MHMR_ERR_BAD_SHAPE;      // one thread per camera column: <= 20 bands
-    if (dtype == MHMR_DT_F16)
-        hipLaunchKernelGGL((camera_embed_kernel<MHMR_DT_F16>), dim3(B * G * G), dim3(128), 0, s, Kmat, freq, G, patch, zK, ctx16, Kc, C, nbands);
-    else
-        hipLaunchKernelGGL((camera_embed_kernel<MHMR_DT_BF16>), dim3(B * G * G), dim3(128), 0, s, Kmat, freq, G, patch, zK, ctx16, Kc, C, nbands);
-    MHMR_CHECK_LAUNCH();
-    return 0;
-}
-
-int mhmr_launch_hph_inputs(const float* feat32, const float* zK, const int* det_b, const int* det_y, const int* det_x,
-                           const float* cq_x, const float* cq_y, const float* cv_x, const float* cv_y, const float* init_tail,
-                           int ntail, float* zc, float* token, int Ktok, void* ctx16, int Kc, int* det_row, int P, int G, int C,
-                           int dtype, const int* nvalid, int cam_dim, hipStream_t s) {
+int launch_hph_inputs(const float* feat32, const float* zK, const int* det_b, const int* det_y, const int* det_x,
+                      const float* cq_x, const float* cq_y, const float* cv_x, const float* cv_y, const float* init_tail,
+                      int ntail, float* zc, float* token, int Ktok, void* ctx16, int Kc, int* det_row, int P, int G, int C,
+                      int dtype, const int* nvalid, int cam_dim, hipStream_t s) {
     if (P <= 0) return 0;
     if (cam_dim < 3 || C + cam_dim > Kc) return MHMR_ERR_BAD_SHAPE;
     if (dtype == MHMR_DT_F16)
@@ -676,32 +479,26 @@ int mhmr_launch_hph_inputs(const float* feat32, const float* zK, const int* det_
     return 0;
 }
 
-int mhmr_launch_hph_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads,
-                              hipStream_t s) {
+int launch_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads, hipStream_t s) {
     if (ngroups <= 0) return 0;
-    const int inner = heads * 32;
-    hipLaunchKernelGGL(hph_self_attn_kernel, dim3(ngroups, heads, (nmax + 63) / 64), dim3(64), 0, s, qkv, gstart, out, inner,
-                       0.17677669529663688110f);
+    hipLaunchKernelGGL(hph_self_attn_kernel, dim3(ngroups, heads, (nmax + 63) / 64), dim3(64), 0, s, qkv, gstart, out, heads * 32,
+                       HPH_ATT_SCALE);
     MHMR_CHECK_LAUNCH();
     return 0;
 }
 
-int mhmr_launch_hph_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N,
-                               hipStream_t s) {
+int launch_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N, hipStream_t s) {
     if (nchunks <= 0) return 0;
-    // work lists longer than one workgroup can count (512 entries = 4096 persons in one batch) take one launch per 512 entries
-    for (int c0 = 0; c0 < nchunks; c0 += 64 * CA_WAVES) {
-        const int n = nchunks - c0 < 64 * CA_WAVES ? nchunks - c0 : 64 * CA_WAVES;
+    for_each_work_list_launch(nchunks, [&](int c0, int n) {
         hipLaunchKernelGGL(hph_cross_attn_kernel, dim3(n * heads), dim3(64 * CA_WAVES), 0, s, q, kv, chunks + 3 * c0, n, out, heads * 32, N,
-                           0.17677669529663688110f);
-    }
+                           HPH_ATT_SCALE);
+    });
     MHMR_CHECK_LAUNCH();
     return 0;
 }
 
-int mhmr_launch_hph_decode(const float* dec, int ldd, int nb, const float* Kmat, const int* det_b, float fn, int nearness,
-                           float* rotmat, float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P,
-                           hipStream_t s) {
+int launch_decode(const float* dec, int ldd, int nb, const float* Kmat, const int* det_b, float fn, int nearness, float* rotmat,
+                  float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, hipStream_t s) {
     if (P <= 0) return 0;
     hipLaunchKernelGGL(hph_decode_kernel, dim3(P), dim3(64), 0, s, dec, ldd, nb, Kmat, det_b, fn, nearness, rotmat, rotvec,
                        betas, expr, dist_pp, dist);
@@ -709,9 +506,193 @@ int mhmr_launch_hph_decode(const float* dec, int ldd, int nb, const float* Kmat,
     return 0;
 }
 
-int mhmr_launch_loc(const float* offset, const int* det_y, const int* det_x, int patch, float* loc, int P, hipStream_t s) {
+int launch_loc(const float* offset, const int* det_y, const int* det_x, int patch, float* loc, int P, hipStream_t s) {
     if (P <= 0) return 0;
     hipLaunchKernelGGL(loc_kernel, dim3((P + 127) / 128), dim3(128), 0, s, offset, det_y, det_x, (float)patch, loc, P);
     MHMR_CHECK_LAUNCH();
     return 0;
 }
+
+}  // namespace
+
+// ---------------------------------------------------------------- the decoder stack: shape rules and ONE layer, for forward and tape
+bool mhmr_hph_stack_shape_ok(int dim, int heads, int mlp, int Kc) {
+    return !(Kc % 64 || dim % 64 || dim > 2048 || mlp % 16 || (2 * heads * 32) % 128);
+}
+
+bool mhmr_hph_head_shape_ok(const mhmr_hph_desc* d) {
+    if (d->Ktok % 16 || d->C % 16 || !mhmr_hph_stack_shape_ok(d->dim, d->heads, d->mlp, d->Kc)) return false;
+    return d->nb >= 0 && d->nb <= 64;          // the decode writes betas with one thread each of 64
+}
+
+// kv = ctx16 . to_kv16^T over the (un-normalised) context rows of all images, padded to a multiple of 128 rows
+int mhmr_launch_to_kv(const HphStack& t, const mhmr_hph_layer& W, float* kv, hipStream_t s) {
+    const int inner = t.heads * 32, Mctx = (t.B * t.N + 127) / 128 * 128;
+    GemmArgs g{t.ctx16, t.Kc, W.to_kv16, t.Kc, Mctx, 2 * inner, t.Kc, nullptr, nullptr, kv, 2 * inner, nullptr, 0, 128, 1, Mctx, EPI_F32};
+    return mhmr_launch_gemm(g, t.dtype, s);
+}
+
+int mhmr_launch_hph_layer(const HphStack& t, const mhmr_hph_layer& W, const HphLayerBufs& b, hipStream_t s) {
+    const int P = t.P, dim = t.dim, mlp = t.mlp, heads = t.heads, inner = heads * 32;
+    // self-attention among the queries of one image
+    TRY(mhmr_launch_layernorm_f32(b.x_sa, W.ln_sa_w, W.ln_sa_b, b.xn, P, dim, HPH_LN_EPS, s));
+    TRY(mhmr_launch_linear_f32(b.xn, dim, nullptr, W.to_qkv, dim, nullptr, nullptr, 0, b.qkv, 3 * inner, P, 3 * inner, dim, MHMR_ACT_NONE, s));
+    TRY(launch_self_attn(b.qkv, t.gstart, b.o_sa, t.ngroups, t.nmax, heads, s));
+    TRY(mhmr_launch_linear_f32(b.o_sa, inner, nullptr, W.sa_out_w, inner, W.sa_out_b, b.x_sa, dim, b.x_ca, dim, P, dim, inner, MHMR_ACT_NONE, s));
+    // cross-attention over the (un-normalised) per-image context
+    TRY(mhmr_launch_to_kv(t, W, b.kv, s));
+    TRY(mhmr_launch_layernorm_f32(b.x_ca, W.ln_ca_w, W.ln_ca_b, b.xn, P, dim, HPH_LN_EPS, s));
+    TRY(mhmr_launch_linear_f32(b.xn, dim, nullptr, W.to_q, dim, nullptr, nullptr, 0, b.q, inner, P, inner, dim, MHMR_ACT_NONE, s));
+    TRY(launch_cross_attn(b.q, b.kv, t.chunks, t.nchunks, b.o_ca, heads, t.N, s));
+    TRY(mhmr_launch_linear_f32(b.o_ca, inner, nullptr, W.ca_out_w, inner, W.ca_out_b, b.x_ca, dim, b.x_ff, dim, P, dim, inner, MHMR_ACT_NONE, s));
+    // feed-forward (the tape also keeps the pre-activation)
+    TRY(mhmr_launch_layernorm_f32(b.x_ff, W.ln_ff_w, W.ln_ff_b, b.xn, P, dim, HPH_LN_EPS, s));
+    if (b.z1) TRY(mhmr_launch_linear_f32(b.xn, dim, nullptr, W.ff1_w, dim, W.ff1_b, nullptr, 0, b.z1, mlp, P, mlp, dim, MHMR_ACT_NONE, s));
+    TRY(mhmr_launch_linear_f32(b.xn, dim, nullptr, W.ff1_w, dim, W.ff1_b, nullptr, 0, b.h1, mlp, P, mlp, dim, MHMR_ACT_GELU, s));
+    if (b.x_out) TRY(mhmr_launch_linear_f32(b.h1, mlp, nullptr, W.ff2_w, mlp, W.ff2_b, b.x_ff, dim, b.x_out, dim, P, dim, mlp, MHMR_ACT_NONE, s));
+    return 0;
+}
+
+// ---------------------------------------------------------------- entry points (include/mhmr.h)
+extern "C" {
+
+int mhmr_detect_scores(const void* hid16, int ld, const float* w2, const float* b2, float* scores, int rows, int C, int dtype,
+                       void* stream) {
+    if (C % 128) return MHMR_ERR_BAD_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == MHMR_DT_F16)
+        hipLaunchKernelGGL((score_kernel<MHMR_DT_F16>), dim3((rows + 3) / 4), dim3(256), 0, s, hid16, ld, w2, b2, scores, rows, C);
+    else
+        hipLaunchKernelGGL((score_kernel<MHMR_DT_BF16>), dim3((rows + 3) / 4), dim3(256), 0, s, hid16, ld, w2, b2, scores, rows, C);
+    MHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+int mhmr_detect_count(const float* scores, int B, int G, int nms_kernel, float thr, int* counts, void* stream) {
+    if (nms_kernel < 1 || B <= 0) return MHMR_ERR_BAD_ARG;
+    hipLaunchKernelGGL(detect_count_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, G, nms_kernel, nms_pad(nms_kernel), thr, counts);
+    MHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+int mhmr_detect_write(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b, int* det_y,
+                      int* det_x, float* det_score, void* stream) {
+    if (nms_kernel < 1 || B <= 0) return MHMR_ERR_BAD_ARG;
+    return launch_detect_write(scores, B, G, nms_kernel, thr, base, det_b, det_y, det_x, det_score, 0x7fffffff, (hipStream_t)stream);
+}
+
+int mhmr_detect_write_cap(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b, int* det_y,
+                          int* det_x, float* det_score, int cap, void* stream) {
+    if (nms_kernel < 1 || B <= 0 || cap < 0) return MHMR_ERR_BAD_ARG;
+    return launch_detect_write(scores, B, G, nms_kernel, thr, base, det_b, det_y, det_x, det_score, cap, (hipStream_t)stream);
+}
+
+int mhmr_person_groups(const int* counts, const int* det_b, int P, int B, int cap, int* base, int* gstart, int ngcap, int* chunks,
+                       int nccap, int* info, void* stream) {
+    if (B <= 0 || B > 8192 || P < 0 || cap < 0 || ngcap < 0 || nccap < 0 || !gstart || !info || (nccap > 0 && !chunks)) return MHMR_ERR_BAD_ARG;
+    if (!counts && P > 0 && !det_b) return MHMR_ERR_BAD_ARG;
+    const size_t lds = ((size_t)2 * B + (size_t)ngcap + 1 + (size_t)3 * nccap) * sizeof(int);
+    if (lds > 60 * 1024) return MHMR_ERR_BAD_SHAPE;          // (B = 8192 with the sufficient bounds is 160 KB: far beyond any batch)
+    hipLaunchKernelGGL(person_groups_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, counts, det_b, P, B, cap, base, gstart, ngcap, chunks,
+                       nccap, info);
+    MHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+int mhmr_camera_embed(const float* Kmat, const float* freq, int B, int G, int patch, float* zK, void* ctx16, int Kc, int C,
+                      int dtype, int nbands, void* stream) {
+    if (nbands < 1 || Kc - C > 128 || Kc - C < 3 + 6 * nbands) return MHMR_ERR_BAD_SHAPE;      // one thread per camera column: <= 20 bands
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == MHMR_DT_F16)
+        hipLaunchKernelGGL((camera_embed_kernel<MHMR_DT_F16>), dim3(B * G * G), dim3(128), 0, s, Kmat, freq, G, patch, zK, ctx16, Kc, C, nbands);
+    else
+        hipLaunchKernelGGL((camera_embed_kernel<MHMR_DT_BF16>), dim3(B * G * G), dim3(128), 0, s, Kmat, freq, G, patch, zK, ctx16, Kc, C, nbands);
+    MHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+int mhmr_linear_f32(const float* X, int ldx, const int* row_idx, const float* W, int ldw, const float* bias, const float* R,
+                    int ldr, float* Y, int ldy, int M, int N, int K, int act, void* stream) {
+    return mhmr_launch_linear_f32(X, ldx, row_idx, W, ldw, bias, R, ldr, Y, ldy, M, N, K, act, (hipStream_t)stream);
+}
+
+int mhmr_layernorm_f32(const float* in, const float* w, const float* b, float* out, int rows, int C, float eps, void* stream) {
+    return mhmr_launch_layernorm_f32(in, w, b, out, rows, C, eps, (hipStream_t)stream);
+}
+
+int mhmr_hph_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads, void* stream) {
+    if (heads <= 0) return MHMR_ERR_BAD_SHAPE;
+    return launch_self_attn(qkv, gstart, out, ngroups, nmax, heads, (hipStream_t)stream);
+}
+
+int mhmr_hph_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N, void* stream) {
+    if (heads <= 0 || N <= 0) return MHMR_ERR_BAD_SHAPE;
+    return launch_cross_attn(q, kv, chunks, nchunks, out, heads, N, (hipStream_t)stream);
+}
+
+int mhmr_hph_decode(const float* dec, int ldd, int nb, const float* K, const int* det_b, float fn, int nearness, float* rotmat,
+                    float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, void* stream) {
+    if (nb < 0 || nb > 64 || ldd < 318 + nb + 3 + 10) return MHMR_ERR_BAD_SHAPE;      // one thread per beta in a 64-thread block
+    return launch_decode(dec, ldd, nb, K, det_b, fn, nearness, rotmat, rotvec, betas, expr, dist_pp, dist, P, (hipStream_t)stream);
+}
+
+// The decode + loc of mhmr_hph_forward on a caller's read-out: the same two kernels, hence the same bits.
+int mhmr_heads_decode(const mhmr_heads_decode_desc* d, void* stream) {
+    if (!d || d->P < 0) return MHMR_ERR_BAD_ARG;
+    if (d->nb < 0 || d->nb > 64 || d->ldr < 318 + d->nb + 3 + 10) return MHMR_ERR_BAD_SHAPE;
+    if (d->P == 0) return 0;
+    if (!d->readout || !d->offset || !d->K || !d->det_b || !d->det_y || !d->det_x || !d->loc || !d->rotmat || !d->rotvec || !d->shape ||
+        !d->expression || !d->dist_postprocessed || !d->dist)
+        return MHMR_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(launch_loc(d->offset, d->det_y, d->det_x, d->patch, d->loc, d->P, s));
+    return launch_decode(d->readout, d->ldr, d->nb, d->K, d->det_b, d->fn, d->nearness, d->rotmat, d->rotvec, d->shape, d->expression,
+                         d->dist_postprocessed, d->dist, d->P, s);
+}
+
+// `depth` x (pre-norm self-attention among the queries of one image, cross-attention over that image's N context
+// tokens, GELU feed-forward), each with a residual.  Shared by the Multi-HMR HPH (dim 1024, 8 heads, mlp 1024, depth 2,
+// blocks/cross_attn_transformer.py:239-261) and the Anny HPH (dim 512, 16 heads, mlp 2048, depth 8,
+// multi_hmr_anny/hph.py:114-151).  Queries are ragged groups (no padding), so the reference's mask arithmetic vanishes.
+// In place: every sub-block reads and writes x, the temporaries are reused (t1 = qkv, q, gelu(ff1); t2 = both attention outputs).
+int mhmr_xattn_layers_forward(const mhmr_hph_layer* layers, int depth, int dim, int heads, int mlp, int Kc, int N, int B,
+                              int dtype, float* x, float* xn, float* t1, float* t2, float* kv, const void* ctx16,
+                              const int* gstart, int ngroups, int nmax, const int* chunks, int nchunks, int P, void* stream) {
+    if (!layers || P < 0 || depth < 0) return MHMR_ERR_BAD_ARG;
+    if (P == 0) return 0;
+    if (!mhmr_hph_stack_shape_ok(dim, heads, mlp, Kc)) return MHMR_ERR_BAD_SHAPE;
+    const HphStack t{dim, heads, mlp, Kc, N, B, dtype, P, ctx16, gstart, ngroups, nmax, chunks, nchunks};
+    const HphLayerBufs b{x, x, x, x, xn, t1, t2, t1, t2, kv, t1, nullptr};
+    for (int l = 0; l < depth; ++l) TRY(mhmr_launch_hph_layer(t, layers[l], b, (hipStream_t)stream));
+    return 0;
+}
+
+int mhmr_hph_forward(const mhmr_hph_desc* d, const float* feat32, const float* zK, void* ctx16, const int* det_b,
+                     const int* det_y, const int* det_x, int P, const int* gstart, int ngroups, int nmax, const int* chunks,
+                     int nchunks, const float* K, int B, float* offset, float* loc, float* rotmat, float* rotvec, float* betas,
+                     float* expr, float* dist_pp, float* dist, void* stream) {
+    if (!d || P < 0) return MHMR_ERR_BAD_ARG;
+    if (P == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int C = d->C, dim = d->dim;
+    if (!mhmr_hph_head_shape_ok(d)) return MHMR_ERR_BAD_SHAPE;
+
+    // queries, mlp_offset input, context rows of the detected cells  (model.py:255-265, 500-517, 541-552)
+    TRY(launch_hph_inputs(feat32, zK, det_b, det_y, det_x, d->cq_x, d->cq_y, d->cv_x, d->cv_y, d->init_tail,
+                          318 + d->nb + 3, d->zc, d->token, d->Ktok, ctx16, d->Kc, d->det_row, P, d->G, C, d->dtype, d->nvalid,
+                          d->cam_dim > 0 ? d->cam_dim : 99, s));
+    // mlp_offset (model.py:258) and loc (272-275)
+    TRY(mhmr_launch_linear_f32(d->zc, C, nullptr, d->off1_w, C, d->off1_b, nullptr, 0, d->t1, C, P, C, C, MHMR_ACT_RELU, s));
+    TRY(mhmr_launch_linear_f32(d->t1, C, nullptr, d->off2_w, C, d->off2_b, nullptr, 0, offset, 2, P, 2, C, MHMR_ACT_NONE, s));
+    TRY(launch_loc(offset, det_y, det_x, d->patch, loc, P, s));
+    // token embedding (+ pos_embedding folded into the bias)  (cross_attn_transformer.py:352-357)
+    TRY(mhmr_launch_linear_f32(d->token, d->Ktok, nullptr, d->tok_w, d->Ktok, d->tok_b, nullptr, 0, d->x, dim, P, dim, d->Ktok,
+                               MHMR_ACT_NONE, s));
+    TRY(mhmr_xattn_layers_forward(d->layers, d->depth, dim, d->heads, d->mlp, d->Kc, d->N, B, d->dtype, d->x, d->xn, d->t1, d->t2, d->kv,
+                                  ctx16, gstart, ngroups, nmax, chunks, nchunks, P, stream));
+    // read-outs + init (model.py:571-575), 6D -> rotmat -> rotvec, distance post-processing
+    TRY(mhmr_launch_linear_f32(d->x, dim, nullptr, d->dec_w, dim, d->dec_b, nullptr, 0, d->dec, d->Ndec, P, d->Ndec, dim, MHMR_ACT_NONE, s));
+    return launch_decode(d->dec, d->Ndec, d->nb, K, det_b, d->fn, d->nearness, rotmat, rotvec, betas, expr, dist_pp, dist, P, s);
+}
+
+}  // extern "C"

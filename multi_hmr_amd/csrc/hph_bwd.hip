@@ -18,19 +18,12 @@
 //                         partial products are added in slice order (fp64) by a finishing pass; columns c >= cvalid are exact zeros.
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
+#include "hph_shared.h"
 
 namespace {
 
-constexpr float ATT_SCALE = 0.17677669529663688110f;      // 32^-0.5, as the forward
-constexpr int CA_WAVES = 8;                               // hph.hip's cross-attention workgroup
 constexpr int LN_SLICE = 32;                              // rows per first-stage slice of the LayerNorm parameter sums
 constexpr int CTX_SLICES = 16;                            // upper bound of the row slices of the to_kv gradient
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ float dact(float z, int act) {
     if (act == MHMR_ACT_RELU) return z > 0.f ? 1.f : 0.f;
@@ -144,8 +137,8 @@ __global__ __launch_bounds__(64) void linear_bwd_bias_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// LayerNorm backward.  dx: one wave per row, the statistics recomputed as the forward computes them and left in stats[row] = (mean, rstd)
-// for the parameter sums.  dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ dR),  g = dy gamma.
+// LayerNorm backward.  dx: one wave per row, the statistics recomputed by the forward's own ln_row_stats and left in stats[row] =
+// (mean, rstd) for the parameter sums.  dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ dR),  g = dy gamma.
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_bwd_dx_kernel(const float* __restrict__ in, const float* __restrict__ gw,
                                                                const float* __restrict__ dy, const float* dR, float* dx,
@@ -153,20 +146,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_dx_kernel(const float* __re
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* ip = in + (size_t)row * C;
     const float* dp = dy + (size_t)row * C;
-    float v[32], gq[32];
+    float v[32], gq[32], mean, rstd;
     const int n = C / 64;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        if (i < n) { v[i] = ip[i * 64 + lane]; s += v[i]; }
-    const float mean = wave_sum(s) / C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        if (i < n) { v[i] -= mean; q += v[i] * v[i]; }
-    const float rstd = rsqrtf(wave_sum(q) / C + eps);
+    ln_row_stats(in + (size_t)row * C, lane, C, eps, v, mean, rstd);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i)
@@ -219,7 +202,7 @@ __global__ __launch_bounds__(64) void layernorm_bwd_param2_kernel(const double* 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Self-attention backward, query side: lane = one query (the forward's grid).  Pass 1 repeats the forward's online softmax (lse, O),
+// Self-attention backward, query side: lane = one query (the forward's grid).  Pass 1 is the forward's self_attn_row (lse, O),
 // D = dO . O; pass 2 streams the keys again: p = exp(s - lse), dq = scale sum_j p (dO . v_j - D) k_j.  lse_d[row][h] = (lse, D).
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void self_attn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ dO,
@@ -232,24 +215,10 @@ __global__ __launch_bounds__(64) void self_attn_bwd_q_kernel(const float* __rest
     const bool active = qi < n;
     const int ld = 3 * inner;
     const size_t row = (size_t)(s0 + (active ? qi : 0));
-    const float* qp = qkv + row * ld + h * 32;
-    float q[32], o[32], go[32];
+    float q[32], o[32], go[32], m, l;
 #pragma unroll
-    for (int d = 0; d < 32; ++d) { q[d] = qp[d] * scale; o[d] = 0.f; go[d] = dO[row * inner + h * 32 + d]; }
-    float m = -INFINITY, l = 0.f;
-    for (int j = 0; j < n; ++j) {
-        const float* kp = qkv + (size_t)(s0 + j) * ld + inner + h * 32;
-        const float* vp = kp + inner;
-        float s = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) s += q[d] * kp[d];
-        const float mn = fmaxf(m, s);
-        const float a = expf(m - mn), pj = expf(s - mn);
-        l = l * a + pj;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) o[d] = o[d] * a + pj * vp[d];
-        m = mn;
-    }
+    for (int d = 0; d < 32; ++d) go[d] = dO[row * inner + h * 32 + d];
+    self_attn_row(qkv, qkv + row * ld + h * 32, s0, n, inner, h, scale, q, o, m, l);
     const float inv = 1.0f / l, lse = m + logf(l);
     float D = 0.f;
 #pragma unroll
@@ -308,91 +277,22 @@ __global__ __launch_bounds__(64) void self_attn_bwd_kv_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Cross-attention backward (a): the forward's kernel up to its merge, ending in lse_d[q][h] = (log-sum-exp of the N scores, dO . O).
+// Cross-attention backward (a): the forward's cross_attn_row, ending in lse_d[q][h] = (log-sum-exp of the N scores, dO . O).
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * CA_WAVES) void cross_attn_bwd_stats_kernel(const float* __restrict__ q, const float* __restrict__ kv,
                                                                   const float* __restrict__ dO, const int* __restrict__ chunks, int ncap,
                                                                   float* __restrict__ lse_d, int inner, int N, float scale) {
-    const int nc = __syncthreads_count(threadIdx.x < ncap && chunks[3 * threadIdx.x + 2] > 0);      // (ncap <= 512: the launcher)
-    const int heads = inner >> 5;
-    if ((int)blockIdx.x >= nc * heads) return;
-    const int ch = blockIdx.x % nc, h = blockIdx.x / nc;
-    const int b = chunks[3 * ch], q0 = chunks[3 * ch + 1], nq = chunks[3 * ch + 2];
-    __shared__ float part[CA_WAVES][8][34];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, qi = lane & 7, sl = lane >> 3;
-    const bool active = qi < nq;
-    const float* qp = q + (size_t)(q0 + (active ? qi : 0)) * inner + h * 32;
-    float qv[32], o[32];
+    CrossAttnItem it;
+    float mt, lt, o[32];
+    if (!cross_attn_row(q, kv, chunks, ncap, inner, N, scale, it, mt, lt, o)) return;
+    const float inv = 1.0f / lt;
+    const float* gp = dO + it.qrow * inner + it.h * 32;
+    float D = 0.f;
 #pragma unroll
-    for (int d = 0; d < 32; ++d) { qv[d] = qp[d] * scale; o[d] = 0.f; }
-    float m = -INFINITY, l = 0.f;
-    const int ld = 2 * inner;
-    const float* kbase = kv + (size_t)b * N * ld + h * 32;
-    for (int j = sl + 8 * wv; j < N; j += 8 * CA_WAVES) {
-        const float* kp = kbase + (size_t)j * ld;
-        const float* vp = kp + inner;
-        float kk[32];
-#pragma unroll
-        for (int d = 0; d < 32; d += 4) *(f32x4*)(kk + d) = *(const f32x4*)(kp + d);
-        float s = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) s += qv[d] * kk[d];
-        if (s > m) {
-            const float a = expf(m - s);
-            l *= a;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) o[d] *= a;
-            m = s;
-        }
-        const float pj = expf(s - m);
-        l += pj;
-#pragma unroll
-        for (int d = 0; d < 32; d += 4) {
-            const f32x4 vv = *(const f32x4*)(vp + d);
-            o[d] += pj * vv[0]; o[d + 1] += pj * vv[1]; o[d + 2] += pj * vv[2]; o[d + 3] += pj * vv[3];
-        }
-    }
-#pragma unroll
-    for (int off = 8; off < 64; off <<= 1) {
-        const float m2 = __shfl_xor(m, off), l2 = __shfl_xor(l, off);
-        const float mn = fmaxf(m, m2);
-        const float a1 = (m == -INFINITY) ? 0.f : expf(m - mn), a2 = (m2 == -INFINITY) ? 0.f : expf(m2 - mn);
-        l = l * a1 + l2 * a2;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) o[d] = o[d] * a1 + __shfl_xor(o[d], off) * a2;
-        m = mn;
-    }
-    if (sl == 0) {
-        part[wv][qi][32] = m;
-        part[wv][qi][33] = l;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) part[wv][qi][d] = o[d];
-    }
-    __syncthreads();
-    if (wv == 0 && active && sl == 0) {
-        float mt = part[0][qi][32];
-#pragma unroll
-        for (int w2 = 1; w2 < CA_WAVES; ++w2) mt = fmaxf(mt, part[w2][qi][32]);
-        float lt = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) o[d] = 0.f;
-#pragma unroll
-        for (int w2 = 0; w2 < CA_WAVES; ++w2) {
-            const float mw = part[w2][qi][32];
-            const float a = (mw == -INFINITY) ? 0.f : expf(mw - mt);
-            lt += part[w2][qi][33] * a;
-#pragma unroll
-            for (int d = 0; d < 32; ++d) o[d] += part[w2][qi][d] * a;
-        }
-        const float inv = 1.0f / lt;
-        const float* gp = dO + (size_t)(q0 + qi) * inner + h * 32;
-        float D = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; ++d) D += gp[d] * (o[d] * inv);
-        float* sp = lse_d + ((size_t)(q0 + qi) * heads + h) * 2;
-        sp[0] = mt + logf(lt);
-        sp[1] = D;
-    }
+    for (int d = 0; d < 32; ++d) D += gp[d] * (o[d] * inv);
+    float* sp = lse_d + (it.qrow * (inner >> 5) + it.h) * 2;
+    sp[0] = mt + logf(lt);
+    sp[1] = D;
 }
 
 // (b) dq: the same split of the keys over lanes and waves; the 8 slices of a wave are added by xor shuffles, the waves through LDS in
@@ -401,15 +301,11 @@ __global__ __launch_bounds__(64 * CA_WAVES) void cross_attn_bwd_q_kernel(const f
                                                               const float* __restrict__ dO, const int* __restrict__ chunks, int ncap,
                                                               const float* __restrict__ lse_d, float* __restrict__ dq, int inner, int N,
                                                               float scale) {
-    const int nc = __syncthreads_count(threadIdx.x < ncap && chunks[3 * threadIdx.x + 2] > 0);
-    const int heads = inner >> 5;
-    if ((int)blockIdx.x >= nc * heads) return;
-    const int ch = blockIdx.x % nc, h = blockIdx.x / nc;
-    const int b = chunks[3 * ch], q0 = chunks[3 * ch + 1], nq = chunks[3 * ch + 2];
+    CrossAttnItem it;
+    if (!cross_attn_item(chunks, ncap, inner, it)) return;
     __shared__ float part[CA_WAVES][8][33];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, qi = lane & 7, sl = lane >> 3;
-    const bool active = qi < nq;
-    const size_t qrow = (size_t)(q0 + (active ? qi : 0));
+    const int heads = inner >> 5, h = it.h, wv = it.wv, qi = it.qi, sl = it.sl;
+    const size_t qrow = it.qrow;
     const float* qp = q + qrow * inner + h * 32;
     const float* gp = dO + qrow * inner + h * 32;
     float qv[32], go[32], acc[32];
@@ -417,7 +313,7 @@ __global__ __launch_bounds__(64 * CA_WAVES) void cross_attn_bwd_q_kernel(const f
     for (int d = 0; d < 32; ++d) { qv[d] = qp[d] * scale; go[d] = gp[d]; acc[d] = 0.f; }
     const float lse = lse_d[(qrow * heads + h) * 2], D = lse_d[(qrow * heads + h) * 2 + 1];
     const int ld = 2 * inner;
-    const float* kbase = kv + (size_t)b * N * ld + h * 32;
+    const float* kbase = cross_attn_kbase(kv, it, inner, N);
     for (int j = sl + 8 * wv; j < N; j += 8 * CA_WAVES) {
         const float* kp = kbase + (size_t)j * ld;
         const float* vp = kp + inner;
@@ -446,7 +342,7 @@ __global__ __launch_bounds__(64 * CA_WAVES) void cross_attn_bwd_q_kernel(const f
         for (int d = 0; d < 32; ++d) part[wv][qi][d] = acc[d];
     }
     __syncthreads();
-    if (wv == 0 && active && sl == 0) {
+    if (it.finishes()) {
         float* op = dq + qrow * inner + h * 32;
 #pragma unroll
         for (int d = 0; d < 32; ++d) {
@@ -634,26 +530,24 @@ int launch_layernorm_bwd(const float* x, const float* w, const float* dy, const 
 int launch_self_attn_bwd(const float* qkv, const float* dO, const int* gstart, float* dqkv, float* lse_d, int ngroups, int nmax, int heads,
                          hipStream_t s) {
     const dim3 grid(ngroups, heads, (nmax + 63) / 64);
-    hipLaunchKernelGGL(self_attn_bwd_q_kernel, grid, dim3(64), 0, s, qkv, dO, gstart, dqkv, lse_d, heads * 32, ATT_SCALE);
-    hipLaunchKernelGGL(self_attn_bwd_kv_kernel, grid, dim3(64), 0, s, qkv, dO, gstart, dqkv, lse_d, heads * 32, ATT_SCALE);
+    hipLaunchKernelGGL(self_attn_bwd_q_kernel, grid, dim3(64), 0, s, qkv, dO, gstart, dqkv, lse_d, heads * 32, HPH_ATT_SCALE);
+    hipLaunchKernelGGL(self_attn_bwd_kv_kernel, grid, dim3(64), 0, s, qkv, dO, gstart, dqkv, lse_d, heads * 32, HPH_ATT_SCALE);
     MHMR_CHECK_LAUNCH();
     return 0;
 }
 
 int launch_cross_attn_bwd(const float* q, const float* kv, const float* dO, const int* chunks, int nchunks, float* dq, float* dkv, float* lse_d,
                           int heads, int N, int B, hipStream_t s) {
-    // work lists longer than one workgroup can count take one launch per 512 entries, as the forward's launcher
-    for (int c0 = 0; c0 < nchunks; c0 += 64 * CA_WAVES) {
-        const int n = nchunks - c0 < 64 * CA_WAVES ? nchunks - c0 : 64 * CA_WAVES;
+    for_each_work_list_launch(nchunks, [&](int c0, int n) {
         hipLaunchKernelGGL(cross_attn_bwd_stats_kernel, dim3(n * heads), dim3(64 * CA_WAVES), 0, s, q, kv, dO, chunks + 3 * c0, n, lse_d,
-                           heads * 32, N, ATT_SCALE);
+                           heads * 32, N, HPH_ATT_SCALE);
         if (dq)
             hipLaunchKernelGGL(cross_attn_bwd_q_kernel, dim3(n * heads), dim3(64 * CA_WAVES), 0, s, q, kv, dO, chunks + 3 * c0, n, lse_d, dq,
-                               heads * 32, N, ATT_SCALE);
-    }
+                               heads * 32, N, HPH_ATT_SCALE);
+    });
     if (dkv)
         hipLaunchKernelGGL(cross_attn_bwd_kv_kernel, dim3((N + 255) / 256, B, heads), dim3(256), 0, s, q, kv, dO, chunks, nchunks, lse_d, dkv,
-                           heads * 32, N, ATT_SCALE);
+                           heads * 32, N, HPH_ATT_SCALE);
     MHMR_CHECK_LAUNCH();
     return 0;
 }
@@ -690,12 +584,6 @@ int launch_op16_to_f32(const void* in, float* out, size_t n, int dtype, hipStrea
     MHMR_CHECK_LAUNCH();
     return 0;
 }
-
-#define TRY(expr)                   \
-    do {                            \
-        int rc__ = (expr);          \
-        if (rc__ != 0) return rc__; \
-    } while (0)
 
 // ---------------------------------------------------------------- the stack's workspace: tape + scratch, every piece 256-byte aligned
 struct StackLayout {
@@ -738,10 +626,8 @@ bool stack_layout(int depth, int dim, int heads, int mlp, int Kc, int N, int B, 
 }
 
 int stack_shape_rc(int dim, int heads, int mlp, int Kc, int B) {
-    const int inner = heads * 32;
     if (heads <= 0 || heads > 65535 || B <= 0 || B > 65535) return MHMR_ERR_BAD_SHAPE;
-    if (Kc % 64 || dim % 64 || dim > 2048 || mlp % 16 || (2 * inner) % 128) return MHMR_ERR_BAD_SHAPE;      // the forward's rules
-    return 0;
+    return mhmr_hph_stack_shape_ok(dim, heads, mlp, Kc) ? 0 : MHMR_ERR_BAD_SHAPE;
 }
 
 }  // namespace
@@ -833,8 +719,8 @@ long long mhmr_xattn_layers_backward_workspace_bytes(int depth, int dim, int hea
     return L.total;
 }
 
-// The stack's backward.  The forward overwrites x in place, so the layers are first re-run with the forward's own launchers, out of place,
-// into the tape (the inputs of the three sub-blocks, qkv, q, both attention outputs, the feed-forward's pre-activation Z and gelu(Z));
+// The stack's backward.  The forward overwrites x in place, so the layers are first re-run by the forward's own layer function, out of
+// place, into the tape (the inputs of the three sub-blocks, qkv, q, both attention outputs, the feed-forward's pre-activation Z and gelu(Z));
 // kv is recomputed per layer from ctx16 on the way back.
 int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream) {
     if (!d || d->P < 0 || d->depth < 0) return MHMR_ERR_BAD_ARG;
@@ -862,7 +748,7 @@ int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream) 
     }
     hipStream_t s = (hipStream_t)stream;
     const int P = d->P, dim = d->dim, heads = d->heads, mlp = d->mlp, Kc = d->Kc, N = d->N, B = d->B, inner = heads * 32;
-    const int rows = B * N, Mctx = (rows + 127) / 128 * 128;
+    const int rows = B * N;
     char* ws = (char*)d->workspace;
     auto F = [&](long long off) { return (float*)(ws + off); };
     auto xs = [&](int i) { return F(L.xs + (long long)i * L.s_x); };
@@ -871,29 +757,13 @@ int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream) 
     void* ctxws = ws + L.ctx;
 
     // ---- the forward again, out of place
+    const HphStack t{dim, heads, mlp, Kc, N, B, d->dtype, P, d->ctx16, d->gstart, d->ngroups, d->nmax, d->chunks, d->nchunks};
     for (int l = 0; l < d->depth; ++l) {
-        const mhmr_hph_layer& W = d->layers[l];
-        const float* x_sa = l == 0 ? d->x0 : xs(3 * l - 1);
-        float *x_ca = xs(3 * l), *x_ff = xs(3 * l + 1), *x_out = xs(3 * l + 2);
-        float *qkv = F(L.qkv + l * L.s_qkv), *o_sa = F(L.o_sa + l * L.s_inner), *q = F(L.q + l * L.s_inner), *o_ca = F(L.o_ca + l * L.s_inner);
-        float *z1 = F(L.z1 + l * L.s_mlp), *h1 = F(L.h1 + l * L.s_mlp);
-        TRY(mhmr_launch_layernorm_f32(x_sa, W.ln_sa_w, W.ln_sa_b, xn, P, dim, 1e-5f, s));
-        TRY(mhmr_launch_linear_f32(xn, dim, nullptr, W.to_qkv, dim, nullptr, nullptr, 0, qkv, 3 * inner, P, 3 * inner, dim, MHMR_ACT_NONE, s));
-        TRY(mhmr_launch_hph_self_attn(qkv, d->gstart, o_sa, d->ngroups, d->nmax, heads, s));
-        TRY(mhmr_launch_linear_f32(o_sa, inner, nullptr, W.sa_out_w, inner, W.sa_out_b, x_sa, dim, x_ca, dim, P, dim, inner, MHMR_ACT_NONE, s));
-        {
-            GemmArgs g{d->ctx16, Kc, W.to_kv16, Kc, Mctx, 2 * inner, Kc, nullptr, nullptr, kv, 2 * inner, nullptr, 0, 128, 1, Mctx, EPI_F32};
-            TRY(mhmr_launch_gemm(g, d->dtype, s));
-        }
-        TRY(mhmr_launch_layernorm_f32(x_ca, W.ln_ca_w, W.ln_ca_b, xn, P, dim, 1e-5f, s));
-        TRY(mhmr_launch_linear_f32(xn, dim, nullptr, W.to_q, dim, nullptr, nullptr, 0, q, inner, P, inner, dim, MHMR_ACT_NONE, s));
-        TRY(mhmr_launch_hph_cross_attn(q, kv, d->chunks, d->nchunks, o_ca, heads, N, s));
-        TRY(mhmr_launch_linear_f32(o_ca, inner, nullptr, W.ca_out_w, inner, W.ca_out_b, x_ca, dim, x_ff, dim, P, dim, inner, MHMR_ACT_NONE, s));
-        TRY(mhmr_launch_layernorm_f32(x_ff, W.ln_ff_w, W.ln_ff_b, xn, P, dim, 1e-5f, s));
-        TRY(mhmr_launch_linear_f32(xn, dim, nullptr, W.ff1_w, dim, W.ff1_b, nullptr, 0, z1, mlp, P, mlp, dim, MHMR_ACT_NONE, s));
-        TRY(mhmr_launch_linear_f32(xn, dim, nullptr, W.ff1_w, dim, W.ff1_b, nullptr, 0, h1, mlp, P, mlp, dim, MHMR_ACT_GELU, s));
-        if (l + 1 < d->depth)      // the last layer's output is not needed
-            TRY(mhmr_launch_linear_f32(h1, mlp, nullptr, W.ff2_w, mlp, W.ff2_b, x_ff, dim, x_out, dim, P, dim, mlp, MHMR_ACT_NONE, s));
+        const HphLayerBufs b{l == 0 ? d->x0 : xs(3 * l - 1), xs(3 * l), xs(3 * l + 1),
+                             l + 1 < d->depth ? xs(3 * l + 2) : nullptr,      // the last layer's output is not needed
+                             xn, F(L.qkv + l * L.s_qkv), F(L.o_sa + l * L.s_inner), F(L.q + l * L.s_inner), F(L.o_ca + l * L.s_inner), kv,
+                             F(L.h1 + l * L.s_mlp), F(L.z1 + l * L.s_mlp)};
+        TRY(mhmr_launch_hph_layer(t, d->layers[l], b, s));
     }
 
     // ---- and back
@@ -909,20 +779,17 @@ int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream) 
         const float *qkv = F(L.qkv + l * L.s_qkv), *o_sa = F(L.o_sa + l * L.s_inner), *q = F(L.q + l * L.s_inner), *o_ca = F(L.o_ca + l * L.s_inner);
         const float *z1 = F(L.z1 + l * L.s_mlp), *h1 = F(L.h1 + l * L.s_mlp);
         // feed-forward
-        TRY(mhmr_launch_layernorm_f32(x_ff, W.ln_ff_w, W.ln_ff_b, xn, P, dim, 1e-5f, s));
+        TRY(mhmr_launch_layernorm_f32(x_ff, W.ln_ff_w, W.ln_ff_b, xn, P, dim, HPH_LN_EPS, s));
         TRY(launch_linear_bwd_weight(g, dim, nullptr, 0, h1, mlp, G.ff2_w, mlp, G.ff2_b, P, dim, mlp, MHMR_ACT_NONE, s));
         TRY(launch_linear_bwd_input(g, dim, nullptr, nullptr, 0, W.ff2_w, mlp, nullptr, 0, tbig, mlp, P, dim, mlp, MHMR_ACT_NONE, s));
         TRY(launch_linear_bwd_weight(tbig, mlp, z1, mlp, xn, dim, G.ff1_w, dim, G.ff1_b, P, mlp, dim, MHMR_ACT_GELU, s));
         TRY(launch_linear_bwd_input(tbig, mlp, nullptr, z1, mlp, W.ff1_w, dim, nullptr, 0, xn, dim, P, mlp, dim, MHMR_ACT_GELU, s));
         // (xn is read by the weight side before the input side overwrites it: stream order)
         float* g1 = gbuf[gi]; gi ^= 1;
-        TRY(launch_layernorm_bwd(x_ff, W.ln_ff_w, xn, g, g1, G.ln_ff_w, G.ln_ff_b, P, dim, 1e-5f, lnws, s));
+        TRY(launch_layernorm_bwd(x_ff, W.ln_ff_w, xn, g, g1, G.ln_ff_w, G.ln_ff_b, P, dim, HPH_LN_EPS, lnws, s));
         // cross-attention
-        {
-            GemmArgs ga{d->ctx16, Kc, W.to_kv16, Kc, Mctx, 2 * inner, Kc, nullptr, nullptr, kv, 2 * inner, nullptr, 0, 128, 1, Mctx, EPI_F32};
-            TRY(mhmr_launch_gemm(ga, d->dtype, s));
-        }
-        TRY(mhmr_launch_layernorm_f32(x_ca, W.ln_ca_w, W.ln_ca_b, xn, P, dim, 1e-5f, s));
+        TRY(mhmr_launch_to_kv(t, W, kv, s));
+        TRY(mhmr_launch_layernorm_f32(x_ca, W.ln_ca_w, W.ln_ca_b, xn, P, dim, HPH_LN_EPS, s));
         TRY(launch_linear_bwd_weight(g1, dim, nullptr, 0, o_ca, inner, G.ca_out_w, inner, G.ca_out_b, P, dim, inner, MHMR_ACT_NONE, s));
         TRY(launch_linear_bwd_input(g1, dim, nullptr, nullptr, 0, W.ca_out_w, inner, nullptr, 0, tin, inner, P, dim, inner, MHMR_ACT_NONE, s));
         TRY(launch_cross_attn_bwd(q, kv, tin, d->chunks, d->nchunks, tbig, dkv, lse, heads, N, B, s));
@@ -936,16 +803,16 @@ int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream) 
         TRY(launch_linear_bwd_weight(tbig, inner, nullptr, 0, xn, dim, G.to_q, dim, nullptr, P, inner, dim, MHMR_ACT_NONE, s));
         TRY(launch_linear_bwd_input(tbig, inner, nullptr, nullptr, 0, W.to_q, dim, nullptr, 0, xn, dim, P, inner, dim, MHMR_ACT_NONE, s));
         float* g2 = gbuf[gi]; gi ^= 1;
-        TRY(launch_layernorm_bwd(x_ca, W.ln_ca_w, xn, g1, g2, G.ln_ca_w, G.ln_ca_b, P, dim, 1e-5f, lnws, s));
+        TRY(launch_layernorm_bwd(x_ca, W.ln_ca_w, xn, g1, g2, G.ln_ca_w, G.ln_ca_b, P, dim, HPH_LN_EPS, lnws, s));
         // self-attention
-        TRY(mhmr_launch_layernorm_f32(x_sa, W.ln_sa_w, W.ln_sa_b, xn, P, dim, 1e-5f, s));
+        TRY(mhmr_launch_layernorm_f32(x_sa, W.ln_sa_w, W.ln_sa_b, xn, P, dim, HPH_LN_EPS, s));
         TRY(launch_linear_bwd_weight(g2, dim, nullptr, 0, o_sa, inner, G.sa_out_w, inner, G.sa_out_b, P, dim, inner, MHMR_ACT_NONE, s));
         TRY(launch_linear_bwd_input(g2, dim, nullptr, nullptr, 0, W.sa_out_w, inner, nullptr, 0, tin, inner, P, dim, inner, MHMR_ACT_NONE, s));
         TRY(launch_self_attn_bwd(qkv, tin, d->gstart, tbig, lse, d->ngroups, d->nmax, heads, s));
         TRY(launch_linear_bwd_weight(tbig, 3 * inner, nullptr, 0, xn, dim, G.to_qkv, dim, nullptr, P, 3 * inner, dim, MHMR_ACT_NONE, s));
         TRY(launch_linear_bwd_input(tbig, 3 * inner, nullptr, nullptr, 0, W.to_qkv, dim, nullptr, 0, xn, dim, P, 3 * inner, dim, MHMR_ACT_NONE, s));
         float* g3 = l == 0 ? d->g_x0 : gbuf[gi];
-        TRY(launch_layernorm_bwd(x_sa, W.ln_sa_w, xn, g2, g3, G.ln_sa_w, G.ln_sa_b, P, dim, 1e-5f, lnws, s));
+        TRY(launch_layernorm_bwd(x_sa, W.ln_sa_w, xn, g2, g3, G.ln_sa_w, G.ln_sa_b, P, dim, HPH_LN_EPS, lnws, s));
         g = g3;
         // gbuf[gi] now holds g; the next two writes go to the other buffer, then to this one's partner: g1 must not alias g
         gi ^= 1;
@@ -977,8 +844,7 @@ void head_layout(const mhmr_hph_desc* f, int P, HeadLayout* H, long long stack_b
 }
 
 int head_shape_rc(const mhmr_hph_desc* f, int B) {
-    if (f->Ktok % 16 || f->Kc % 64 || f->C % 16 || f->C <= 0 || f->G <= 0 || f->N <= 0) return MHMR_ERR_BAD_SHAPE;      // the forward's rules
-    if (f->nb < 0 || f->nb > 64 || f->Ndec != 318 + f->nb + 13) return MHMR_ERR_BAD_SHAPE;
+    if (!mhmr_hph_head_shape_ok(f) || f->C <= 0 || f->G <= 0 || f->N <= 0 || f->Ndec != 318 + f->nb + 13) return MHMR_ERR_BAD_SHAPE;
     const int E = f->cam_dim > 0 ? f->cam_dim : 99;
     if (E < 3 || f->C + E > f->Kc || f->C + E + 318 + f->nb + 3 > f->Ktok) return MHMR_ERR_BAD_SHAPE;
     return stack_shape_rc(f->dim, f->heads, f->mlp, f->Kc, B);

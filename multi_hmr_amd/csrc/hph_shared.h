@@ -1,0 +1,227 @@
+// What the person head's forward (hph.hip, anny.hip) and its backward (hph_bwd.hip) both compute, defined once: the backward
+// differentiates the evaluation the forward runs because both call the functions below.  Changing an expression, its association or a
+// branch here changes forward and backward together; nothing here may be copied into a kernel.
+#pragma once
+#include "mhmr_common.h"
+
+constexpr int CA_WAVES = 8;                                  // waves of a cross-attention workgroup; a work list is counted by one: <= 64 CA_WAVES entries
+constexpr float HPH_ATT_SCALE = 0.17677669529663688110f;     // dim_head^-0.5 = 32^-0.5
+constexpr float HPH_LN_EPS = 1e-5f;                          // every LayerNorm of the decoder stack
+
+// Work lists longer than one workgroup can count (512 entries = 4096 persons in one batch) take one launch per 512 entries:
+// launch(first entry, entries of this launch).
+template <typename F>
+inline void for_each_work_list_launch(int nchunks, F launch) {
+    for (int c0 = 0; c0 < nchunks; c0 += 64 * CA_WAVES) launch(c0, nchunks - c0 < 64 * CA_WAVES ? nchunks - c0 : 64 * CA_WAVES);
+}
+
+// LayerNorm row, one wave per row (C % 64 == 0, C <= 2048; lane holds columns i * 64 + lane): two passes in registers.
+// Leaves v[i] = x - mean for i < C / 64, mean and rstd.
+__device__ __forceinline__ void ln_row_stats(const float* __restrict__ ip, int lane, int C, float eps, float (&v)[32], float& mean,
+                                             float& rstd) {
+    const int n = C / 64;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+        if (i < n) { v[i] = ip[i * 64 + lane]; s += v[i]; }
+    mean = wave_sum(s) / C;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i)
+        if (i < n) { v[i] -= mean; q += v[i] * v[i]; }
+    rstd = rsqrtf(wave_sum(q) / C + eps);
+}
+
+// Self-attention, one query (lane) of head h over the n keys of its group, which starts at row s0 of qkv [P, 3 inner] (q | k | v): keys
+// streamed at wave-uniform addresses, online softmax.  Leaves q[] = the scaled query, the running maximum m, l = sum exp(s - m) and
+// o[] = sum exp(s - m) v, un-normalised.
+__device__ __forceinline__ void self_attn_row(const float* __restrict__ qkv, const float* __restrict__ qp, int s0, int n, int inner,
+                                              int h, float scale, float (&q)[32], float (&o)[32], float& m, float& l) {
+    const int ld = 3 * inner;
+#pragma unroll
+    for (int d = 0; d < 32; ++d) { q[d] = qp[d] * scale; o[d] = 0.f; }
+    m = -INFINITY; l = 0.f;
+    for (int j = 0; j < n; ++j) {
+        const float* kp = qkv + (size_t)(s0 + j) * ld + inner + h * 32;
+        const float* vp = kp + inner;
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) s += q[d] * kp[d];
+        const float mn = fmaxf(m, s);
+        const float a = expf(m - mn), pj = expf(s - mn);
+        l = l * a + pj;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) o[d] = o[d] * a + pj * vp[d];
+        m = mn;
+    }
+}
+
+// The cross-attention work item of a workgroup and a lane's place in it.  1-D grid of ncap x heads workgroups over a work list of ncap
+// entries (image b, first query, count <= 8) whose tail may be padding (count 0: person_groups_kernel pads up to the launch's upper
+// bound).  The real work is the FIRST nc x heads workgroups: the dispatcher hands out workgroups in index order, two per CU -- with the
+// padding interleaved (a 2-D grid, real chunks 0..31 of 64 in every row) half of the CUs received two real workgroups and the other half
+// two that return at once: 221 instead of 118 us per layer.
+// lane = slice * 8 + qi; wave wv's slice sl handles keys j = sl + 8 wv (mod 8 CA_WAVES).
+struct CrossAttnItem {
+    int b, h;                 // image, head
+    int wv, qi, sl;           // wave, query of the item, key slice of the wave
+    bool active;              // qi < the item's count (the other lanes compute on query 0 and write nothing)
+    size_t qrow;              // the lane's query row (query 0's if not active)
+    __device__ bool finishes() const { return wv == 0 && active && sl == 0; }      // the lane that holds the merged result of query qi
+};
+// -> false: this workgroup is beyond the real work.  Every thread of the workgroup must call it (it counts through a barrier).
+__device__ __forceinline__ bool cross_attn_item(const int* __restrict__ chunks, int ncap, int inner, CrossAttnItem& it) {
+    const int nc = __syncthreads_count(threadIdx.x < ncap && chunks[3 * threadIdx.x + 2] > 0);      // (ncap <= 512: the launcher)
+    const int heads = inner >> 5;
+    if ((int)blockIdx.x >= nc * heads) return false;
+    const int ch = blockIdx.x % nc;
+    it.h = blockIdx.x / nc;
+    it.b = chunks[3 * ch];
+    const int q0 = chunks[3 * ch + 1], nq = chunks[3 * ch + 2];
+    const int lane = threadIdx.x & 63;
+    it.wv = threadIdx.x >> 6; it.qi = lane & 7; it.sl = lane >> 3;
+    it.active = it.qi < nq;
+    it.qrow = (size_t)(q0 + (it.active ? it.qi : 0));
+    return true;
+}
+// first K | V row pair of a lane and the keys it walks: for (j = sl + 8 wv; j < N; j += 8 CA_WAVES) row kbase + j * 2 inner
+__device__ __forceinline__ const float* cross_attn_kbase(const float* __restrict__ kv, const CrossAttnItem& it, int inner, int N) {
+    return kv + (size_t)it.b * N * (2 * inner) + it.h * 32;
+}
+
+// Cross-attention of a work item's queries over the N context tokens of their image.  q: [P, inner]; kv: [B N, 2 inner] (k | v) fp32.
+// The 8 partial (m, l, o) per query of a wave are merged with 3 xor-shuffle rounds, the CA_WAVES wave results through LDS in wave order
+// (deterministic).  The loop is latency-bound (one 256-byte K|V row pair per lane-slice per trip): a single wave per (chunk, head)
+// walked 512 trips at N = 4096 (0.56 ms per layer); 8 waves walk 64 each.
+// -> true on the lanes that finish a query (it.finishes()): there mt = the maximum of the N scores, lt = sum exp(s - mt),
+// o[] = sum exp(s - mt) v, un-normalised.  Every thread of the workgroup must call it.
+__device__ __forceinline__ bool cross_attn_row(const float* __restrict__ q, const float* __restrict__ kv, const int* __restrict__ chunks,
+                                               int ncap, int inner, int N, float scale, CrossAttnItem& it, float& mt, float& lt,
+                                               float (&o)[32]) {
+    if (!cross_attn_item(chunks, ncap, inner, it)) return false;
+    __shared__ float part[CA_WAVES][8][34];
+    const int wv = it.wv, qi = it.qi, sl = it.sl;
+    const float* qp = q + it.qrow * inner + it.h * 32;
+    float qv[32];
+#pragma unroll
+    for (int d = 0; d < 32; ++d) { qv[d] = qp[d] * scale; o[d] = 0.f; }
+    float m = -INFINITY, l = 0.f;
+    const int ld = 2 * inner;
+    const float* kbase = cross_attn_kbase(kv, it, inner, N);
+    for (int j = sl + 8 * wv; j < N; j += 8 * CA_WAVES) {
+        const float* kp = kbase + (size_t)j * ld;
+        const float* vp = kp + inner;
+        float kk[32];
+#pragma unroll
+        for (int d = 0; d < 32; d += 4) *(f32x4*)(kk + d) = *(const f32x4*)(kp + d);
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) s += qv[d] * kk[d];
+        if (s > m) {  // rare after the first few keys
+            const float a = expf(m - s);
+            l *= a;
+#pragma unroll
+            for (int d = 0; d < 32; ++d) o[d] *= a;
+            m = s;
+        }
+        const float pj = expf(s - m);
+        l += pj;
+#pragma unroll
+        for (int d = 0; d < 32; d += 4) {
+            const f32x4 vv = *(const f32x4*)(vp + d);
+            o[d] += pj * vv[0]; o[d + 1] += pj * vv[1]; o[d + 2] += pj * vv[2]; o[d + 3] += pj * vv[3];
+        }
+    }
+    // merge the 8 key slices (lanes differing in bits 3..5)
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+        const float m2 = __shfl_xor(m, off), l2 = __shfl_xor(l, off);
+        const float mn = fmaxf(m, m2);
+        const float a1 = (m == -INFINITY) ? 0.f : expf(m - mn), a2 = (m2 == -INFINITY) ? 0.f : expf(m2 - mn);
+        l = l * a1 + l2 * a2;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) o[d] = o[d] * a1 + __shfl_xor(o[d], off) * a2;
+        m = mn;
+    }
+    // merge the waves: lanes 0..7 of every wave hold (m, l, o) of query qi over that wave's keys
+    if (sl == 0) {
+        part[wv][qi][32] = m;
+        part[wv][qi][33] = l;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) part[wv][qi][d] = o[d];
+    }
+    __syncthreads();
+    if (!it.finishes()) return false;
+    mt = part[0][qi][32];
+#pragma unroll
+    for (int w2 = 1; w2 < CA_WAVES; ++w2) mt = fmaxf(mt, part[w2][qi][32]);
+    lt = 0.f;
+#pragma unroll
+    for (int d = 0; d < 32; ++d) o[d] = 0.f;
+#pragma unroll
+    for (int w2 = 0; w2 < CA_WAVES; ++w2) {
+        const float mw = part[w2][qi][32];
+        const float a = (mw == -INFINITY) ? 0.f : expf(mw - mt);
+        lt += part[w2][qi][33] * a;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) o[d] += part[w2][qi][d] * a;
+    }
+    return true;
+}
+
+// ---- read-out decode (roma special_gramschmidt / rotmat_to_rotvec), shared by hph_decode_kernel and anny_decode_kernel
+// 6D -> rotation: x, y = the two given columns; R = [x' y' x'^y'] row-major (columns x', y', z)
+__device__ __forceinline__ void rot6d_to_rotmat(float x0, float x1, float x2, float y0, float y1, float y2, float (&R)[9]) {
+    const float nx = sqrtf(x0 * x0 + x1 * x1 + x2 * x2);
+    x0 /= nx; x1 /= nx; x2 /= nx;
+    const float dxy = x0 * y0 + x1 * y1 + x2 * y2;
+    y0 -= dxy * x0; y1 -= dxy * x1; y2 -= dxy * x2;
+    const float ny = sqrtf(y0 * y0 + y1 * y1 + y2 * y2);
+    y0 /= ny; y1 /= ny; y2 /= ny;
+    const float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
+    R[0] = x0; R[1] = y0; R[2] = z0; R[3] = x1; R[4] = y1; R[5] = z1; R[6] = x2; R[7] = y2; R[8] = z2;
+}
+
+// rotmat -> unit quaternion (XYZW), branch on the largest of (R00, R11, R22, trace) -> rotation vector v[3]
+__device__ __forceinline__ void rotmat_to_rotvec(const float (&R)[9], float* __restrict__ v) {
+    const float tr = R[0] + R[4] + R[8];
+    float qx, qy, qz, qw;
+    int choice = 0;  // argmax over (R00, R11, R22, trace), first maximal index wins
+    float best = R[0];
+    if (R[4] > best) { best = R[4]; choice = 1; }
+    if (R[8] > best) { best = R[8]; choice = 2; }
+    if (tr > best) { best = tr; choice = 3; }
+    if (choice == 3) {
+        qx = R[7] - R[5]; qy = R[2] - R[6]; qz = R[3] - R[1]; qw = 1.f + tr;
+    } else {
+        const int i = choice, jj = (i + 1) % 3, kk = (jj + 1) % 3;
+        float qq[3];
+        qq[i] = 1.f - tr + 2.f * R[i * 3 + i];
+        qq[jj] = R[jj * 3 + i] + R[i * 3 + jj];
+        qq[kk] = R[kk * 3 + i] + R[i * 3 + kk];
+        qw = R[kk * 3 + jj] - R[jj * 3 + kk];
+        qx = qq[0]; qy = qq[1]; qz = qq[2];
+    }
+    const float qn = sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
+    qx /= qn; qy /= qn; qz /= qn; qw /= qn;
+    if (qw < 0.f) { qx = -qx; qy = -qy; qz = -qz; qw = -qw; }
+    const float angle = 2.f * atan2f(sqrtf(qx * qx + qy * qy + qz * qz), qw);
+    float sc;
+    if (fabsf(angle) <= 1e-3f) sc = 2.f + angle * angle / 12.f + 7.f * angle * angle * angle * angle / 2880.f;
+    else sc = angle / sinf(angle / 2.f);
+    v[0] = sc * qx; v[1] = sc * qy; v[2] = sc * qz;
+}
+
+// ---- detection: hidden16[row] . w2 over a wave (C % 128 == 0), the sum in every lane
+template <int DT>
+__device__ __forceinline__ float score_dot(const void* __restrict__ hid_, int ld, const float* __restrict__ w2, int row, int lane, int C) {
+    typedef typename Op<DT>::T T;
+    typedef typename Op<DT>::V2 V2;
+    const T* hp = (const T*)hid_ + (size_t)row * ld;
+    float s = 0.f;
+    for (int c = lane * 2; c < C; c += 128) {
+        const V2 h = *(const V2*)(hp + c);
+        s += (float)h[0] * w2[c] + (float)h[1] * w2[c + 1];
+    }
+    return wave_sum(s);
+}

@@ -52,15 +52,6 @@ __device__ __forceinline__ void mat3_vec(const float* a, const float* v, float* 
     for (int i = 0; i < 3; ++i) o[i] = a[i * 3] * v[0] + a[i * 3 + 1] * v[1] + a[i * 3 + 2] * v[2];
 }
 
-__device__ __forceinline__ void inv3x3(const float* k, float* o) {
-    const float a = k[0], b = k[1], c = k[2], d = k[3], e = k[4], f = k[5], g = k[6], h = k[7], i = k[8];
-    const float A = e * i - f * h, B = -(d * i - f * g), Cc = d * h - e * g;
-    const float id = 1.0f / (a * A + b * B + c * Cc);
-    o[0] = A * id; o[1] = -(b * i - c * h) * id; o[2] = (b * f - c * e) * id;
-    o[3] = B * id; o[4] = (a * i - c * g) * id;  o[5] = -(a * f - c * d) * id;
-    o[6] = Cc * id; o[7] = -(a * h - b * g) * id; o[8] = (a * e - b * d) * id;
-}
-
 // perspective_projection (utils/camera.py:14-27): y = x / x.z ; (K y)[:2]
 __device__ __forceinline__ void project(const float* K, const float* x, float* o2) {
     const float yx = x[0] / x[2], yy = x[1] / x[2], yz = x[2] / x[2];

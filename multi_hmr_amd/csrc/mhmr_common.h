@@ -109,6 +109,23 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
+// sum over the 64 lanes of a wave, left in every lane (xor butterfly: the same bits in every lane)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// inverse of a row-major 3x3 by the adjugate, every cofactor TIMES 1 / det
+__device__ __forceinline__ void inv3x3(const float* k, float* o) {
+    const float a = k[0], b = k[1], c = k[2], d = k[3], e = k[4], f = k[5], g = k[6], h = k[7], i = k[8];
+    const float A = e * i - f * h, B = -(d * i - f * g), Cc = d * h - e * g;
+    const float id = 1.0f / (a * A + b * B + c * Cc);
+    o[0] = A * id; o[1] = -(b * i - c * h) * id; o[2] = (b * f - c * e) * id;
+    o[3] = B * id; o[4] = (a * i - c * g) * id;  o[5] = -(a * f - c * d) * id;
+    o[6] = Cc * id; o[7] = -(a * h - b * g) * id; o[8] = (a * e - b * d) * id;
+}
+
 // GELU for 16-bit outputs.  x Phi(x) = max(x, 0) - |x| Q(|x|), Q(a) = erfc(a / sqrt 2) / 2 the upper tail of the normal law (erf is
 // odd: no sign select).  Round 6: Q(a) = exp2(P(a)) with P a degree-5 polynomial fitted to log2 Q -- a smooth, concave function: -1 at
 // 0, ~ -a^2 / (2 ln 2) far out -- by weighted minimax on the ABSOLUTE error of a exp2(P(a)) over [0, 12] (tools/gelu_fit.py makes the

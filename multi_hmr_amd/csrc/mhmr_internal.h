@@ -140,6 +140,12 @@ enum { CLS_QKV = 0, CLS_RESID = 1, CLS_GELU = 2 };
 // ---- per-kernel-family hipEvent profiling (bench.py roofline leg) ----
 enum ProfKind { PROF_GEMM = 0, PROF_ATTN = 1, PROF_LBS = 2, PROF_KINDS = 3 };
 
+#define TRY(expr)                   \
+    do {                            \
+        int rc__ = (expr);          \
+        if (rc__ != 0) return rc__; \
+    } while (0)
+
 // ================================================================================================================================
 // Every function one translation unit defines and another calls, by defining file.  Default arguments live here, once.
 // ================================================================================================================================
@@ -186,24 +192,25 @@ int mhmr_launch_final_norm(const float* resid, const float* w, const float* b, v
 // ---- vit_cls.hip
 int mhmr_launch_cls_linear(const ClsArgs& a, int epi, int dtype, hipStream_t s);
 
-// ---- hph.hip
+// ---- hph.hip (the person head; its extern "C" entry points are defined there too)
 int mhmr_launch_linear_f32(const float* X, int ldx, const int* row_idx, const float* W, int ldw, const float* bias, const float* R, int ldr,
                            float* Y, int ldy, int M, int N, int K, int act, hipStream_t s);
 int mhmr_launch_layernorm_f32(const float* in, const float* w, const float* b, float* out, int rows, int C, float eps, hipStream_t s);
-int mhmr_launch_scores(const void* hid, int ld, const float* w2, const float* b2, float* scores, int rows, int C, int dtype, hipStream_t s);
-int mhmr_launch_detect_count(const float* scores, int B, int G, int nms_kernel, float thr, int* counts, hipStream_t s);
-int mhmr_launch_detect_write(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b, int* det_y, int* det_x,
-                             float* det_score, int cap, hipStream_t s);
-int mhmr_launch_person_groups(const int* counts, const int* det_b, int P, int B, int cap, int* base, int* gstart, int ngcap, int* chunks,
-                              int nccap, int* info, hipStream_t s);
-int mhmr_launch_camera_embed(const float* Kmat, const float* freq, int B, int G, int patch, float* zK, void* ctx16, int Kc, int C, int dtype,
-                             int nbands, hipStream_t s);
-int mhmr_launch_hph_inputs(const float* feat32, const float* zK, const int* det_b, const int* det_y, const int* det_x, const float* cq_x,
-                           const float* cq_y, const float* cv_x, const float* cv_y, const float* init_tail, int ntail, float* zc, float* token,
-                           int Ktok, void* ctx16, int Kc, int* det_row, int P, int G, int C, int dtype, const int* nvalid, int cam_dim,
-                           hipStream_t s);
-int mhmr_launch_hph_self_attn(const float* qkv, const int* gstart, float* out, int ngroups, int nmax, int heads, hipStream_t s);
-int mhmr_launch_hph_cross_attn(const float* q, const float* kv, const int* chunks, int nchunks, float* out, int heads, int N, hipStream_t s);
-int mhmr_launch_hph_decode(const float* dec, int ldd, int nb, const float* Kmat, const int* det_b, float fn, int nearness, float* rotmat,
-                           float* rotvec, float* betas, float* expr, float* dist_pp, float* dist, int P, hipStream_t s);
-int mhmr_launch_loc(const float* offset, const int* det_y, const int* det_x, int patch, float* loc, int P, hipStream_t s);
+// The shape rules of the decoder stack and of the whole head that forward and backward share (each entry point adds its own).
+bool mhmr_hph_stack_shape_ok(int dim, int heads, int mlp, int Kc);
+bool mhmr_hph_head_shape_ok(const mhmr_hph_desc* d);
+// One decoder layer, for the forward (in place: the x_* all alias, the temporaries are reused) and for the backward's tape (distinct
+// buffers).  z1 != null: also the feed-forward's pre-activation (a second ff1 launch without GELU); x_out == null: no ff2.
+struct HphStack {
+    int dim, heads, mlp, Kc, N, B, dtype, P;
+    const void* ctx16;
+    const int* gstart; int ngroups, nmax;
+    const int* chunks; int nchunks;
+};
+struct HphLayerBufs {
+    const float* x_sa;                  // inputs of the three sub-blocks
+    float *x_ca, *x_ff, *x_out;
+    float *xn, *qkv, *o_sa, *q, *o_ca, *kv, *h1, *z1;
+};
+int mhmr_launch_hph_layer(const HphStack& t, const mhmr_hph_layer& W, const HphLayerBufs& b, hipStream_t s);
+int mhmr_launch_to_kv(const HphStack& t, const mhmr_hph_layer& W, float* kv, hipStream_t s);      // kv [roundup(B N, 128), 2 inner] = ctx16 . to_kv16^T

@@ -54,12 +54,6 @@ __global__ void init_rows_kernel(float* __restrict__ resid, const float* __restr
     for (int c = threadIdx.x; c < C; c += blockDim.x) dst[c] = i == 0 ? cls_pos0[c] : 0.f;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // One wave per row; a lane holds NP vectors of VEC floats (C = NP * 64 * VEC; VEC = 4 -> 16-byte loads / 8-byte stores whenever
 // C % 256 == 0, VEC = 2 for C = 384).  Two-pass (mean, then centred variance) in registers.
 // PAIR: out16 rows of ld16 >= 2 C values, [hi = op16(y) | lo = op16(y - hi)] (the f16x3 precision mode)

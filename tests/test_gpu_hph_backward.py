@@ -204,6 +204,59 @@ def test_cross_attention_backward_more_than_512_work_items(L):
     assert _cross_attention_case(L, 64, 2, (1,) * 519 + (0, 9)) == 523
 
 
+def _one_hot_rows(P, heads, r):
+    """dOut[q, h, :] one-hot at d = (q + h + r) % 32 -> (dOut [P, heads * 32], the flat column of the hot element per (q, h))."""
+    q, h = torch.meshgrid(torch.arange(P), torch.arange(heads), indexing="ij")
+    col = h * 32 + (q + h + r) % 32
+    dO = torch.zeros(P, heads * 32)
+    dO[q.reshape(-1), col.reshape(-1)] = 1.0
+    return dO.to(dev()), col.to(dev())
+
+
+def test_self_attention_backward_recomputes_the_forward_bits(L):
+    """With a one-hot dOut row, D = dOut . O as the backward accumulates it IS the backward's own O[d] (zeros add exactly, 1 * x is exact
+    under an FMA): lse_d[q, h, 1] must equal the forward's output element bit for bit, for every d.  Groups of 1, 3, 64 and 65 queries
+    (65 crosses the 64-query block), 2 heads."""
+    heads, counts = 2, (1, 3, 64, 65)
+    inner, P = 32 * heads, sum(counts)
+    g = torch.Generator().manual_seed(310)
+    qkv_d = rn(g, P, 3 * inner, std=1.5).to(dev())
+    gstart = [0]
+    for c in counts:
+        gstart.append(gstart[-1] + c)
+    gs_d, out = i32(gstart), nan(P, inner)
+    _lib.check(L.mhmr_hph_self_attn(qkv_d.data_ptr(), gs_d.data_ptr(), out.data_ptr(), len(counts), max(counts), heads, stream()),
+               "mhmr_hph_self_attn")
+    assert bool(torch.isfinite(out).all())
+    for r in range(32):
+        dO_d, col = _one_hot_rows(P, heads, r)
+        dqkv, lse = nan(P, 3 * inner), nan(P, heads, 2)
+        _lib.check(L.mhmr_hph_self_attn_backward(qkv_d.data_ptr(), dO_d.data_ptr(), gs_d.data_ptr(), dqkv.data_ptr(), lse.data_ptr(),
+                                                 len(counts), max(counts), heads, stream()), "mhmr_hph_self_attn_backward")
+        assert torch.equal(lse[:, :, 1], out.gather(1, col)), f"r {r}"
+
+
+@pytest.mark.parametrize("N", [1, 7, 64, 65, 130])
+def test_cross_attention_backward_recomputes_the_forward_bits(L, N):
+    """The same identity for the cross-attention statistics kernel.  Two images, work items of 8, 1 and 5 queries, 2 heads; N = 1 and 7
+    leave whole key slices and whole waves at m = -inf (the guarded branches of the two merges), 65 and 130 give uneven trips."""
+    heads, counts = 2, (9, 5)
+    inner, B, P = 32 * heads, len(counts), sum(counts)
+    g = torch.Generator().manual_seed(410 + N)
+    q_d, kv_d = rn(g, P, inner, std=1.5).to(dev()), rn(g, B * N, 2 * inner, std=1.5).to(dev())
+    chunks = [0, 0, 8, 0, 8, 1, 1, 9, 5]
+    ch_d, out = i32(chunks), nan(P, inner)
+    _lib.check(L.mhmr_hph_cross_attn(q_d.data_ptr(), kv_d.data_ptr(), ch_d.data_ptr(), 3, out.data_ptr(), heads, N, stream()),
+               "mhmr_hph_cross_attn")
+    assert bool(torch.isfinite(out).all())
+    for r in range(32):
+        dO_d, col = _one_hot_rows(P, heads, r)
+        dq, lse = nan(P, inner), nan(P, heads, 2)
+        _lib.check(L.mhmr_hph_cross_attn_backward(q_d.data_ptr(), kv_d.data_ptr(), dO_d.data_ptr(), ch_d.data_ptr(), 3, dq.data_ptr(), None,
+                                                  lse.data_ptr(), heads, N, B, stream()), "mhmr_hph_cross_attn_backward")
+        assert torch.equal(lse[:, :, 1], out.gather(1, col)), f"r {r}"
+
+
 @pytest.mark.parametrize("precision", ["f16", "bf16"])
 @pytest.mark.parametrize("Kc", [512, 1152])
 def test_context_gemm(L, Kc, precision):
