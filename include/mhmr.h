@@ -523,6 +523,27 @@ long long mhmr_hph_backward_workspace_bytes(const mhmr_hph_desc* fwd, int B, int
 int mhmr_hph_backward(const mhmr_hph_backward_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Backward of the detection head mlp_classif (csrc/detect_bwd.hip): the derivative of
+ * mhmr_gemm16(EPI_OP16_RELU) -> mhmr_detect_scores (clamped = 1) or mhmr_anny_scores (clamped = 0) as those kernels
+ * evaluate them.  hid16 [rows, ldh] (the stored ReLU output), ctx16 [rows, ldx] (columns < C are read) and the rounded
+ * first-layer weight are exact numbers (straight-through); the ReLU mask is hid16 > 0.  With p = sigmoid(hid16[m] . w2 + b2)
+ * (the forward's dot product) and dl_m = g_scores[m] p (1 - p), or 0 where clamped and p lies outside [1e-4, 1 - 1e-4]:
+ *   g_b2 [1] = sum dl_m    g_w2 [C] = sum dl_m hid16[m][n]    g_b1 [C] = w2[n] sum dl_m [hid16[m][n] > 0]
+ *   g_w1 [C, C]: g_w1[n][c] = w2[n] sum dl_m [hid16[m][n] > 0] ctx16[m][c]
+ * over the `rows` real rows only.  The column sums are fp64 in two fixed stages (slices of 512 rows) over the unrounded fp64 dl; g_w1 is an fp32 MFMA
+ * chain over the rows in index order, the row range cut into min(16, ceil(rows / 512)) slices whose partial products are
+ * added in slice order in fp64.  The hidden layer's [rows, C] cotangent is never stored: the workspace is at most
+ * 16 C C 4 + 4 rows + 16 C ceil(rows / 512) bytes (+ alignment).  No atomics; two calls give the same bits; every element
+ * of the four outputs is written (rows == 0: zeros).
+ * MHMR_ERR_BAD_ARG: rows < 0, a NULL pointer that would be read or written, a short workspace; MHMR_ERR_BAD_SHAPE:
+ * C <= 0, C % 128, C > 16384, ldh < C, ldh odd, ldx < C, an unknown dtype, rows > 512 * 65535 (a launch limit).
+ * ---------------------------------------------------------------------------------------------------------- */
+long long mhmr_detect_backward_workspace_bytes(int rows, int C);
+int mhmr_detect_backward(const void* hid16, int ldh, const void* ctx16, int ldx, const float* w2, const float* b2,
+                         const float* g_scores, int rows, int C, int clamped, int dtype, float* g_w1, float* g_b1,
+                         float* g_w2, float* g_b2, void* workspace, long long workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * SMPL-X layer.  Replaces SMPL_Layer.forward (blocks/smpl_layer.py:47-155) -> smplx.SMPLX.forward / lbs,
  * roma.rotvec_to_rotmat (:107), inverse_perspective_projection (:117-123), perspective_projection (:143-144).
  * ---------------------------------------------------------------------------------------------------------- */

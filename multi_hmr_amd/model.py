@@ -306,8 +306,6 @@ class Model(nn.Module):
         P = vit.pack_encoder(self.backbone.encoder, self.img_size, self.precision, device, self.wlo, self.lnfold)
         dt_id, tdt = P["dt_id"], P["tdt"]
         C, G, N = P["C"], P["G"], P["N"]
-        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
-        op = lambda t: t.detach().to(device=device, dtype=torch.float32).to(tdt).contiguous()
         keep = P["keep"]      # tensors referenced by raw pointers in the descriptors
 
         def k(t):
@@ -320,8 +318,7 @@ class Model(nn.Module):
         Kc = roundup(Cc, 64)
         P["E"], P["nbands"] = E, nbands
         P["Cc"], P["Kc"] = Cc, Kc
-        P["cls0_w"], P["cls0_b"] = op(self.mlp_classif[0].weight), f32(self.mlp_classif[0].bias)
-        P["cls2_w"], P["cls2_b"] = f32(self.mlp_classif[2].weight.reshape(-1)), f32(self.mlp_classif[2].bias)
+        P.update(self._detect_tensors(device, tdt))
         # blocks/camera_embed.py:46: linspace(1, max_resolution / 2, num_bands) per ray component
         P["freq"] = torch.stack([torch.linspace(1.0, self._camera_max_resolution / 2, nbands) for _ in range(3)]).to(device).contiguous()
 
@@ -382,10 +379,17 @@ class Model(nn.Module):
                     cq_y=f32(hp.cross_queries_y), cv_x=f32(hp.cross_values_x), cv_y=f32(hp.cross_values_y), init_tail=init_tail,
                     tok_w=tok_w.contiguous(), tok_b=tok_b.contiguous(), dec_w=dec_w, dec_b=dec_b.contiguous())
 
+    def _detect_tensors(self, device, tdt):
+        """The packed copies of the ``mlp_classif`` parameters: the 16-bit first-layer weight, fp32 biases and second-layer row."""
+        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        return dict(cls0_w=f32(self.mlp_classif[0].weight).to(tdt).contiguous(), cls0_b=f32(self.mlp_classif[0].bias),
+                    cls2_w=f32(self.mlp_classif[2].weight.reshape(-1)), cls2_b=f32(self.mlp_classif[2].bias))
+
     def repack_heads(self):
-        """Re-pack ONLY the head weights (``mlp_offset``, ``x_attention_head``) into the buffers the descriptors already point to --
-        after an optimiser step on ``heads_parameters()``.  The ViT pack and the workspaces stay (``repack()`` drops both).  Outputs of
-        the next forward are bit-equal to ``repack()`` + forward.  A pending ``backward`` of a ``train_heads`` forward must run first."""
+        """Re-pack ONLY the head weights (``mlp_offset``, ``x_attention_head``, ``mlp_classif``) into the buffers the descriptors and
+        the forward already point to -- after an optimiser step on ``heads_parameters()`` and / or ``detection_parameters()``.  The ViT
+        pack and the workspaces stay (``repack()`` drops both).  Outputs of the next forward are bit-equal to ``repack()`` + forward.  A
+        pending ``backward`` of a ``train_heads`` / ``train_detection`` forward must run first."""
         with self._lock:
             P = self._packed
             if P is None:
@@ -397,6 +401,8 @@ class Model(nn.Module):
                 for lo, ln in zip(old["layers"], new["layers"]):
                     for n, t in ln.items():
                         lo[n].copy_(t)
+                for n, t in self._detect_tensors(P["device"], P["tdt"]).items():
+                    P[n].copy_(t)
             P["heads_generation"] += 1
 
     def heads_parameters(self):
@@ -409,6 +415,19 @@ class Model(nn.Module):
     def train_heads_(self, flag=True):
         """Set ``requires_grad`` of ``heads_parameters()``; returns self."""
         for p in self.heads_parameters():
+            p.requires_grad_(bool(flag))
+        return self
+
+    def detection_parameters(self):
+        """The four parameters of ``mlp_classif``: what ``train_detection=True`` differentiates.  They stay ``requires_grad=False`` until
+        ``train_detection_(True)``; ``heads_parameters()`` does not contain them."""
+        from .detect_train import DETECTION_PARAMETERS
+        params = dict(self.named_parameters())
+        return [params[n] for n in DETECTION_PARAMETERS]
+
+    def train_detection_(self, flag=True):
+        """Set ``requires_grad`` of ``detection_parameters()``; returns self."""
+        for p in self.detection_parameters():
             p.requires_grad_(bool(flag))
         return self
 
@@ -519,13 +538,20 @@ class Model(nn.Module):
         ``out["readout"]`` and ``out["offset"]`` attached to autograd with respect to ``heads_parameters()`` (those that require grad:
         ``train_heads_(True)``) -- ``decode_readout`` and ``Loss`` on top, ``backward()``, an optimiser step, ``repack_heads()``.  The
         backward reads this call's workspace: run it before the next forward of the same batch size (it raises otherwise).  With no
-        person the gradients are zeros."""
+        person the gradients are zeros.
+        ``train_detection=True`` (needs ``is_training=True``; independent of ``return_readout`` and ``train_heads``): the same dict, key for
+        key and bit for bit, with ``out["scores"]`` attached to autograd with respect to ``detection_parameters()`` (those that require
+        grad: ``train_detection_(True)``).  The same rule for the backward; with no person the detection gradients are NOT zeros (every
+        cell is a negative of the focal term)."""
+        if kwargs.get("train_detection", False) and not is_training:
+            raise ValueError("train_detection=True needs is_training=True")
         if kwargs.get("train_heads", False) and not (is_training and kwargs.get("return_readout", False)):
             raise ValueError("train_heads=True needs is_training=True and return_readout=True")
         with self._lock, torch.autocast("cuda", enabled=False):     # demo.forward_model wraps us in fp16 autocast (demo.py:117)
             return self._forward(x.float().contiguous(), idx, det_thresh, nms_kernel_size, K, is_training,
                                  bool(kwargs.get("return_image_index", False)), bool(kwargs.get("return_batched", False)),
-                                 bool(kwargs.get("return_readout", False)), bool(kwargs.get("train_heads", False)))
+                                 bool(kwargs.get("return_readout", False)), bool(kwargs.get("train_heads", False)),
+                                 bool(kwargs.get("train_detection", False)))
 
     supports_image_index = True
     supports_batched = True
@@ -554,7 +580,7 @@ class Model(nn.Module):
         return self._bm32
 
     def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, with_ids=False, batched=False, with_readout=False,
-                 train_heads=False):
+                 train_heads=False, train_detection=False):
         L = _lib.lib()
         P, ws, stream = self._prepare(x)
         dev, B, G = x.device, x.shape[0], P["G"]
@@ -570,6 +596,10 @@ class Model(nn.Module):
             idx = tuple(i.to(dev) for i in idx)
             Pn = int(idx[0].shape[0])
             out = {"scores": scores.clone()}
+            if train_detection:
+                from . import detect_train
+                out["scores"] = detect_train.attach(self, dict(P=P, ws=ws, dev=dev, rows=B * P["N"], generation=ws["generation"],
+                                                               heads_generation=P["heads_generation"], scores=out["scores"]))
             if Pn == 0:
                 if with_readout:
                     out["readout"] = torch.empty(0, 318 + P["hph"]["nb"] + 13, dtype=torch.float32, device=dev)
