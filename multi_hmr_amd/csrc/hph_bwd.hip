@@ -16,14 +16,16 @@
 //                         so the to_kv reduction may run over all B N rows.
 //   to_kv gradient        dWkv[n][c] = sum_rows dkv[row][n] ctx16[row][c]: fp32 MFMA, the row range split into <= 16 slices whose
 //                         partial products are added in slice order (fp64) by a finishing pass; columns c >= cvalid are exact zeros.
+// The sliced outer product of the to_kv gradient, the two stages of the LayerNorm parameter sums and the workspace cursor are those of
+// row_sums.h, which detect_bwd.hip shares; this file holds the LayerNorm term, the launchers and the layouts.
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
 #include "hph_shared.h"
+#include "row_sums.h"
 
 namespace {
 
 constexpr int LN_SLICE = 32;                              // rows per first-stage slice of the LayerNorm parameter sums
-constexpr int CTX_SLICES = 16;                            // upper bound of the row slices of the to_kv gradient
 
 __device__ __forceinline__ float dact(float z, int act) {
     if (act == MHMR_ACT_RELU) return z > 0.f ? 1.f : 0.f;
@@ -171,35 +173,18 @@ __global__ __launch_bounds__(256) void layernorm_bwd_dx_kernel(const float* __re
     if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
 }
 
-// stage 1: part[slice][c] = (sum dy xhat, sum dy) over the slice's LN_SLICE rows in index order (fp64); one thread per column
-__global__ __launch_bounds__(64) void layernorm_bwd_param1_kernel(const float* __restrict__ in, const float* __restrict__ dy,
-                                                                  const float* __restrict__ stats, double* __restrict__ part, int rows,
-                                                                  int C) {
-    const int c = blockIdx.x * 64 + threadIdx.x, sl = blockIdx.y;
-    const int r0 = sl * LN_SLICE, r1 = min(r0 + LN_SLICE, rows);
-    double a = 0.0, b = 0.0;
-    for (int r = r0; r < r1; ++r) {
+// the two addends of (row, column) of the parameter sums (row_sums.h: stage 1 over slices of LN_SLICE rows, one column per thread; stage
+// 2 the slices in index order): (dy xhat, dy)
+struct LnParamTerm {
+    const float *in, *dy, *stats; int C;
+    __device__ __forceinline__ double operator()(int r, int, int c, double (&ta)[1], double (&tb)[1]) const {
         const float xh = (in[(size_t)r * C + c] - stats[2 * r]) * stats[2 * r + 1];
         const float d = dy[(size_t)r * C + c];
-        a += (double)d * (double)xh;
-        b += (double)d;
+        ta[0] = (double)d * (double)xh;
+        tb[0] = (double)d;
+        return 0.0;
     }
-    part[((size_t)sl * C + c) * 2] = a;
-    part[((size_t)sl * C + c) * 2 + 1] = b;
-}
-
-// stage 2: the slices in index order
-__global__ __launch_bounds__(64) void layernorm_bwd_param2_kernel(const double* __restrict__ part, float* __restrict__ dw,
-                                                                  float* __restrict__ db, int nsl, int C) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
-    double a = 0.0, b = 0.0;
-    for (int sl = 0; sl < nsl; ++sl) {
-        a += part[((size_t)sl * C + c) * 2];
-        b += part[((size_t)sl * C + c) * 2 + 1];
-    }
-    dw[c] = (float)a;
-    db[c] = (float)b;
-}
+};
 
 // ------------------------------------------------------------------------------------------------------------
 // Self-attention backward, query side: lane = one query (the forward's grid).  Pass 1 is the forward's self_attn_row (lse, O),
@@ -400,69 +385,6 @@ __global__ __launch_bounds__(256) void cross_attn_bwd_kv_kernel(const float* __r
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// to_kv gradient: part[slice][n][c] = sum over the slice's rows of G[row][n] * op16[row][c].  Workgroup = 64 (n) x 128 (c), four waves
-// of 32 x 64 (2 x 4 MFMA tiles); four rows per MFMA, rows in index order; rows past the slice contribute an exact zero.
-// ------------------------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(256) void grad_ctx_gemm_kernel(const float* __restrict__ G, int ldg, const void* __restrict__ ctx_, int ldc,
-                                                            float* __restrict__ part, int rows, int Nn, int Kc, int slice_rows) {
-    typedef typename Op<DT>::T T;
-    const T* ctx = (const T*)ctx_;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int g = lane >> 4, l15 = lane & 15;
-    const int n0 = blockIdx.y * 64 + (w & 1) * 32, c0 = blockIdx.x * 128 + (w >> 1) * 64;
-    const int r0 = blockIdx.z * slice_rows, r1 = min(r0 + slice_rows, rows);
-    int na[2], ca[4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) na[t] = min(n0 + 16 * t + l15, Nn - 1);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) ca[u] = min(c0 + 16 * u + l15, Kc - 1);
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-    for (int r = r0; r < r1; r += 4) {
-        const int rr = r + g, rc = min(rr, r1 - 1);
-        const float* gp = G + (size_t)rc * ldg;
-        const T* cp = ctx + (size_t)rc * ldc;
-        float a[2], bb[4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) a[t] = rr < r1 ? gp[na[t]] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) bb[u] = (float)cp[ca[u]];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], bb[u], acc[t][u], 0, 0, 0);
-    }
-    float* pp = part + (size_t)blockIdx.z * Nn * Kc;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = c0 + 16 * u + l15;
-            if (c >= Kc) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int n = n0 + 16 * t + 4 * g + r;
-                if (n < Nn) pp[(size_t)n * Kc + c] = acc[t][u][r];
-            }
-        }
-}
-
-// finishing pass: the slices in index order (fp64); padding columns are exact zeros
-__global__ __launch_bounds__(256) void grad_ctx_finish_kernel(const float* __restrict__ part, float* __restrict__ dW, int nsl, int Nn, int Kc,
-                                                              int cvalid) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)Nn * Kc;
-    if (i >= total) return;
-    double s = 0.0;
-    for (int sl = 0; sl < nsl; ++sl) s += (double)part[(size_t)sl * total + i];
-    dW[i] = (int)(i % Kc) < cvalid ? (float)s : 0.f;
-}
-
 // op16 [n] -> fp32 (to_kv16 as the exact numbers it holds: the context cotangent goes through the fp32 input-side linear)
 template <int DT>
 __global__ __launch_bounds__(256) void op16_to_f32_kernel(const void* __restrict__ in_, float* __restrict__ out, size_t n) {
@@ -509,20 +431,25 @@ int launch_linear_bwd_weight(const float* dY, int lddy, const float* Z, int ldz,
     return 0;
 }
 
-inline long long align256(long long v) { return (v + 255) / 256 * 256; }
-inline long long ln_bwd_bytes(int rows, int C) {
-    const long long nsl = (rows + LN_SLICE - 1) / LN_SLICE;
-    return align256((long long)rows * 2 * sizeof(float)) + nsl * C * 2 * (long long)sizeof(double);
+struct LnLayout { int nsl; long long stats, part, total; };      // slices of stage 1; (mean, rstd) per row | stage 1's partials
+inline LnLayout ln_layout(int rows, int C) {
+    WsCursor ws;
+    const int nsl = (rows + LN_SLICE - 1) / LN_SLICE;
+    const long long stats = ws.take((long long)rows * 2 * sizeof(float)), part = ws.take((long long)nsl * C * 2 * sizeof(double));
+    return {nsl, stats, part, ws.at};
 }
+inline long long ln_bwd_bytes(int rows, int C) { return ln_layout(rows, C).total; }
 
 int launch_layernorm_bwd(const float* x, const float* w, const float* dy, const float* dR, float* dx, float* dw, float* db, int rows, int C,
                          float eps, void* ws, hipStream_t s) {
-    float* stats = (float*)ws;
-    double* part = (double*)((char*)ws + align256((long long)rows * 2 * sizeof(float)));
-    const int nsl = (rows + LN_SLICE - 1) / LN_SLICE;
+    const LnLayout L = ln_layout(rows, C);
+    float* stats = (float*)((char*)ws + L.stats);
+    double* part = (double*)((char*)ws + L.part);
     hipLaunchKernelGGL(layernorm_bwd_dx_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, dy, dR, dx, stats, rows, C, eps);
-    hipLaunchKernelGGL(layernorm_bwd_param1_kernel, dim3(C / 64, nsl), dim3(64), 0, s, x, dy, stats, part, rows, C);
-    hipLaunchKernelGGL(layernorm_bwd_param2_kernel, dim3(C / 64), dim3(64), 0, s, part, dw, db, nsl, C);
+    hipLaunchKernelGGL((col_sums1_kernel<LN_SLICE, 1, LnParamTerm>), dim3(C / 64, L.nsl), dim3(64), 0, s, LnParamTerm{x, dy, stats, C}, part,
+                       (double*)nullptr, 0, 0, rows, C);
+    hipLaunchKernelGGL(col_sums2_kernel, dim3(C / 64), dim3(64), 0, s, part, (const double*)nullptr, (const float*)nullptr, dw, db,
+                       (float*)nullptr, L.nsl, C);
     MHMR_CHECK_LAUNCH();
     return 0;
 }
@@ -552,19 +479,19 @@ int launch_cross_attn_bwd(const float* q, const float* kv, const float* dO, cons
     return 0;
 }
 
-inline int ctx_slices(int rows) { return rows <= 0 ? 1 : (int)((rows + 511) / 512 < CTX_SLICES ? (rows + 511) / 512 : CTX_SLICES); }
-
 int launch_grad_ctx_gemm(const float* G, int ldg, const void* op16, int ld16, float* dW, int rows, int Nn, int Kc, int cvalid, int dtype,
                          void* ws, hipStream_t s) {
-    const int nsl = ctx_slices(rows);
-    const int slice_rows = ((rows + nsl - 1) / nsl + 3) / 4 * 4;
+    const int nsl = row_slices_or_one(rows);      // rows == 0: one empty slice, the product still runs
+    const int srows = slice_rows(rows, nsl);
     const dim3 grid((Kc + 127) / 128, (Nn + 63) / 64, nsl);
+    const LeftF32 left{G, ldg};
     if (dtype == MHMR_DT_F16)
-        hipLaunchKernelGGL((grad_ctx_gemm_kernel<MHMR_DT_F16>), grid, dim3(256), 0, s, G, ldg, op16, ld16, (float*)ws, rows, Nn, Kc, slice_rows);
+        hipLaunchKernelGGL((row_outer_kernel<MHMR_DT_F16, LeftF32, true>), grid, dim3(256), 0, s, left, op16, ld16, (float*)ws, rows, Nn, Kc, srows);
     else
-        hipLaunchKernelGGL((grad_ctx_gemm_kernel<MHMR_DT_BF16>), grid, dim3(256), 0, s, G, ldg, op16, ld16, (float*)ws, rows, Nn, Kc, slice_rows);
+        hipLaunchKernelGGL((row_outer_kernel<MHMR_DT_BF16, LeftF32, true>), grid, dim3(256), 0, s, left, op16, ld16, (float*)ws, rows, Nn, Kc, srows);
     const long long total = (long long)Nn * Kc;
-    hipLaunchKernelGGL(grad_ctx_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)ws, dW, nsl, Nn, Kc, cvalid);
+    hipLaunchKernelGGL(row_outer_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)ws, (const float*)nullptr,
+                       dW, nsl, Nn, Kc, cvalid);
     MHMR_CHECK_LAUNCH();
     return 0;
 }
@@ -600,28 +527,27 @@ bool stack_layout(int depth, int dim, int heads, int mlp, int Kc, int N, int B, 
     L->s_qkv = align256((long long)P * 3 * inner * 4);
     L->s_inner = align256((long long)P * inner * 4);
     L->s_mlp = align256((long long)P * mlp * 4);
-    long long o = 0;
-    auto take = [&](long long bytes) { const long long at = o; o += align256(bytes); return at; };
-    L->xs = take(3LL * depth * L->s_x);
-    L->qkv = take(depth * L->s_qkv);
-    L->o_sa = take(depth * L->s_inner);
-    L->q = take(depth * L->s_inner);
-    L->o_ca = take(depth * L->s_inner);
-    L->z1 = take(depth * L->s_mlp);
-    L->h1 = take(depth * L->s_mlp);
-    L->xn = take(L->s_x);
-    L->ga = take(L->s_x);
-    L->gb = take(L->s_x);
+    WsCursor ws;
+    L->xs = ws.take(3LL * depth * L->s_x);
+    L->qkv = ws.take(depth * L->s_qkv);
+    L->o_sa = ws.take(depth * L->s_inner);
+    L->q = ws.take(depth * L->s_inner);
+    L->o_ca = ws.take(depth * L->s_inner);
+    L->z1 = ws.take(depth * L->s_mlp);
+    L->h1 = ws.take(depth * L->s_mlp);
+    L->xn = ws.take(L->s_x);
+    L->ga = ws.take(L->s_x);
+    L->gb = ws.take(L->s_x);
     const long long big = 3 * inner > mlp ? 3 * inner : mlp;
-    L->t_big = take((long long)P * big * 4);
-    L->t_inner = take(L->s_inner);
-    L->kv = take(Mctx * 2 * inner * 4);
-    L->dkv = take(rows * 2 * inner * 4);
-    L->lse = take((long long)P * heads * 2 * 4);
-    L->ln = take(ln_bwd_bytes(P, dim));
-    L->ctx = take((long long)ctx_slices((int)rows) * 2 * inner * Kc * 4);
-    L->w32 = take(2 * inner * Kc * 4);
-    L->total = o;
+    L->t_big = ws.take((long long)P * big * 4);
+    L->t_inner = ws.take(L->s_inner);
+    L->kv = ws.take(Mctx * 2 * inner * 4);
+    L->dkv = ws.take(rows * 2 * inner * 4);
+    L->lse = ws.take((long long)P * heads * 2 * 4);
+    L->ln = ws.take(ln_bwd_bytes(P, dim));
+    L->ctx = ws.take((long long)row_slices_or_one((int)rows) * 2 * inner * Kc * 4);
+    L->w32 = ws.take(2 * inner * Kc * 4);
+    L->total = ws.at;
     return true;
 }
 
@@ -694,7 +620,7 @@ int mhmr_hph_cross_attn_backward(const float* q, const float* kv, const float* d
 long long mhmr_grad_ctx_gemm_workspace_bytes(int rows, int Nn, int Kc) {
     if (rows < 0) return MHMR_ERR_BAD_ARG;
     if (Nn <= 0 || Kc <= 0) return MHMR_ERR_BAD_SHAPE;
-    return (long long)ctx_slices(rows) * Nn * Kc * (long long)sizeof(float);
+    return (long long)row_slices_or_one(rows) * Nn * Kc * (long long)sizeof(float);
 }
 
 int mhmr_grad_ctx_gemm(const float* G, int ldg, const void* op16, int ld16, float* dW, int rows, int Nn, int Kc, int cvalid, int dtype,
@@ -830,17 +756,16 @@ struct HeadLayout {
 };
 
 void head_layout(const mhmr_hph_desc* f, int P, HeadLayout* H, long long stack_bytes) {
-    long long o = 0;
-    auto take = [&](long long bytes) { const long long at = o; o += align256(bytes); return at; };
-    H->x0 = take((long long)P * f->dim * 4);
-    H->gx = take((long long)P * f->dim * 4);
-    H->gx0 = take((long long)P * f->dim * 4);
-    H->z1 = take((long long)P * f->C * 4);
-    H->h1 = take((long long)P * f->C * 4);
-    H->dh = take((long long)P * f->C * 4);
-    H->gctx = take((long long)P * f->Kc * 4);
-    H->stack = take(stack_bytes);
-    H->total = o;
+    WsCursor ws;
+    H->x0 = ws.take((long long)P * f->dim * 4);
+    H->gx = ws.take((long long)P * f->dim * 4);
+    H->gx0 = ws.take((long long)P * f->dim * 4);
+    H->z1 = ws.take((long long)P * f->C * 4);
+    H->h1 = ws.take((long long)P * f->C * 4);
+    H->dh = ws.take((long long)P * f->C * 4);
+    H->gctx = ws.take((long long)P * f->Kc * 4);
+    H->stack = ws.take(stack_bytes);
+    H->total = ws.at;
 }
 
 int head_shape_rc(const mhmr_hph_desc* f, int B) {

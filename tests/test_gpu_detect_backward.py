@@ -184,6 +184,45 @@ def test_clamp_and_zero_cotangent_rows_are_exact(L):
     assert all(bool((t == 0).all()) for t in empty)
 
 
+@pytest.mark.parametrize("ldx", [128, 128 + 72])
+@pytest.mark.parametrize("precision", ["f16", "bf16"])
+@pytest.mark.parametrize("rows", [5, 515, 8300])
+def test_dw1_is_the_context_gemm_on_the_materialised_left_operand(L, rows, precision, ldx):
+    """The dW1 product and mhmr_grad_ctx_gemm are ONE sliced outer product (csrc/row_sums.h): on the left operand written out as fp32,
+    G[m][n] = hid16[m][n] > 0 ? dl_m : 0, the context GEMM gives the bits of dW1 (up to the exact factor w2[n] = +-1).  The inputs let the
+    host know dl exactly: b2 = 0, w2 = (+1, -1, +1, ...) and hid16[m][2j] = hid16[m][2j + 1] = h, a small integer, so score_dot is exactly 0
+    in any order, p = 0.5 lies inside the clamp and dl_m = 0.25 gs_m exactly, in fp64 and after the fp32 rounding.  rows 5: a partial MFMA
+    step; 515: two slices with a three-row tail; 8300: the 16-slice cap with uneven slices."""
+    C_ = 128
+    g = torch.Generator().manual_seed(4000 + rows + (7 if precision == "bf16" else 0))
+    h = torch.randint(1, 4, (rows, C_ // 2), generator=g) * (torch.rand(rows, C_ // 2, generator=g) < 0.5)
+    hid = h.repeat_interleave(2, dim=1).float()
+    assert 0.4 < float((hid == 0).float().mean()) < 0.6 or rows < 16
+    w2 = torch.ones(C_)
+    w2[1::2] = -1
+    gs = rn(g, rows)
+    gs[3::7] = 0
+    tdt = do.TDT[precision]
+    c = dict(hid16=hid.to(tdt), ctx16=rn(g, rows, C_).to(tdt), w2=w2, b2=torch.zeros(1), gs=gs, rows=rows, C=C_, precision=precision)
+    hid_d, ctx_d = _device_operands(c, C_, ldx, 60000.0)
+    G = torch.where(hid > 0, (0.25 * gs)[:, None].expand(rows, C_), torch.zeros(())).contiguous().to(dev())
+    nbytes = L.mhmr_grad_ctx_gemm_workspace_bytes(rows, C_, C_)
+    assert nbytes > 0
+    ws = torch.full((nbytes,), 255, dtype=torch.uint8, device=dev())
+    dW = torch.full((C_, C_), float("nan"), dtype=torch.float32, device=dev())
+    _lib.check(L.mhmr_grad_ctx_gemm(G.data_ptr(), C_, ctx_d.data_ptr(), ldx, dW.data_ptr(), rows, C_, C_, C_, DT[precision], ws.data_ptr(),
+                                    nbytes, stream()), "mhmr_grad_ctx_gemm")
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(dW).all()) and bool((dW != 0).any())
+    want = w2.to(dev())[:, None] * dW
+    for clamped in (1, 0):
+        g_w1 = _run(L, c, hid_d, ctx_d, clamped)[0]
+        differ = (g_w1 != want).nonzero()
+        print(f"[dW1 == ctx gemm rows {rows} {precision} ldx {ldx} clamped {clamped}] elements that differ: {len(differ)}"
+              + (f", first at {differ[0].tolist()}" if len(differ) else ""))
+        assert torch.equal(g_w1, want)
+
+
 # ------------------------------------------------------------------------------------------------------ (2) through Model
 S, GRID, NB, NAME = 224, 16, 10, "dinov2_vits14"
 
