@@ -667,7 +667,8 @@ int mhmr_eval_mesh_errors(const float* pred, const float* gt, const float* pred_
  *   landmarks (sum_f bary[l][f] * vertex lmk_idx[l][f]);  v2d [G][V][2], j2d [G][J + E + L][2] when K is given.
  * Workspaces: ws_F [ceil(G / 8)][K][8] floats, ws_A [G][J][12] floats.  Three launches on `stream`, no allocation,
  * no synchronisation.  J > 64, K != nc + 9 (J - 1), K > 1536 or Vp not a multiple of 64 -> MHMR_ERR_BAD_SHAPE;
- * G == 0 launches nothing.  parents[i] < i for i > 0 is the caller's duty (multi_hmr_amd/bodymodel.py checks it).
+ * G == 0 launches nothing.  parents[i] < i for i > 0 is the caller's duty (multi_hmr_amd/bodymodel.py checks it); a table
+ * that breaks it is not refused here: see `parents` below.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
     int V, Vp;                /* vertices; V rounded up to a multiple of 64 (columns of the operands, zero-padded)   */
@@ -677,7 +678,9 @@ typedef struct {
     const float* basis;       /* [K][3][Vp]    [shapedirs(nb) | exprdirs(ne) | posedirs(9 (J - 1))]                  */
     const float* J0;          /* [J*3]         J_regressor . v_template                                               */
     const float* JS;          /* [J*3][nc]     J_regressor . dirs                                                     */
-    const int* parents;       /* [J]           parents[0] is ignored                                                  */
+    const int* parents;       /* [J]           parents[0] is ignored; for i > 0 mhmr_body_forward and mhmr_body_backward both
+                                               read parents[i] clamped into [0, i - 1], so a malformed table is walked as
+                                               the same tree in both directions (a well-formed one is read as it stands)     */
     const float* weights;     /* [J][Vp]       dense skinning weights, joint-major                                    */
     const int* extra_idx;     /* [E]                                                                                  */
     const int* lmk_idx;       /* [L][3]        faces[lmk_faces_idx]                                                   */

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
 SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
-HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
+HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
 DT_BF16, DT_F16 = 0, 1

@@ -17,8 +17,8 @@ import torch
 from . import _lib
 from .constants import SMPL_EXTRA_JOINT_VERTS, SMPL_NUM_JOINTS, SMPLX_EXTRA_JOINT_VERTS, SMPLX_NUM_JOINTS
 
-VERTEX_TILE = 64          # csrc/bodymodel.hip VT
-PERSON_GROUP = 8          # csrc/bodymodel.hip PG
+VERTEX_TILE = 64          # csrc/body_shared.h VT
+PERSON_GROUP = 8          # csrc/body_shared.h PG
 
 
 def _dense(a):

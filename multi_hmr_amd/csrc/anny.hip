@@ -63,8 +63,8 @@ __global__ void anny_decode_kernel(const float* __restrict__ rot6d, const float*
     }
     if (j < nb) shape[(size_t)p * nb + j] = 1.0f / (1.0f + expf(-shape_logit[(size_t)p * nb + j]));
     if (j == 0) {
-        const float lx = ((float)det_x[p] + 0.5f + offset[2 * p]) * patch;
-        const float ly = ((float)det_y[p] + 0.5f + offset[2 * p + 1]) * patch;
+        const float lx = decode_loc(det_x[p], offset[2 * p], patch);
+        const float ly = decode_loc(det_y[p], offset[2 * p + 1], patch);
         loc[2 * p] = lx;
         loc[2 * p + 1] = ly;
         const float* k = Kmat + 9 * det_b[p];

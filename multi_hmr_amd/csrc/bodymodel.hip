@@ -10,7 +10,7 @@
 //   mhmr_project_points    utils/camera.py:14-27 for points that do not come from the body kernel (EHF's given vertices).
 //
 // Body forward = three launches on one stream.
-//   pose kernel    one 64-lane workgroup per person: Rodrigues (upstream's angle = |v + 1e-8|), the feature row F = [coef | R_1..J-1 - I],
+//   pose kernel    one 64-lane workgroup per person: upstream's Rodrigues (body_shared.h), the feature row F = [coef | R_1..J-1 - I],
 //                  shaped joints from the load-time products J_regressor.v_template and J_regressor.dirs, then the kinematic chain
 //                  joint by joint (parents precede children: 12 lanes, one per element of the 3x4 transform).
 //   vertex kernel  one workgroup per (64-vertex tile, group of 8 persons).  The basis is [k][axis][Vp] fp32, so lane = vertex reads
@@ -18,23 +18,10 @@
 //                  features broadcast from LDS; partial tiles are summed through LDS in wave order (deterministic), then wave w skins
 //                  person w of the group.  The basis is read once per 8 persons: HBM-bound, ~4 flop per byte.
 //   joint kernel   picked vertices, landmarks and the projection of every joint.
-#include "mhmr_common.h"
+#include "body_shared.h"
 #include "mhmr_internal.h"
 
 namespace {
-
-constexpr int PG = 8;          // persons per pass over the basis
-constexpr int VT = 64;         // vertices per tile (= lanes)
-constexpr int NW = 8;          // waves per vertex workgroup
-constexpr int KMAX = 1536;     // feature rows that fit the 48 KB LDS block
-constexpr int JMAX = 64;
-
-__device__ __forceinline__ void project(const float* __restrict__ K, float x, float y, float z, float* __restrict__ out) {
-    // utils/camera.py:14-27: y = x / x_z, then K y (all three terms, as the einsum)
-    const float a = x / z, b = y / z, c = z / z;
-    out[0] = K[0] * a + K[1] * b + K[2] * c;
-    out[1] = K[3] * a + K[4] * b + K[5] * c;
-}
 
 __global__ __launch_bounds__(64) void body_pose_kernel(mhmr_body_consts c, const float* __restrict__ pose, const float* __restrict__ coef,
                                                        const float* __restrict__ transl, float* __restrict__ ws_F,
@@ -43,43 +30,19 @@ __global__ __launch_bounds__(64) void body_pose_kernel(mhmr_body_consts c, const
     const int g = blockIdx.x, tid = threadIdx.x, J = c.J, nc = c.nc;
     float* F = ws_F + (size_t)(g / PG) * c.K * PG + (g % PG);
     if (tid < J) {
-        const float* v = pose + ((size_t)g * J + tid) * 3;
-        const float x = v[0], y = v[1], z = v[2];
-        const float ex = x + 1e-8f, ey = y + 1e-8f, ez = z + 1e-8f;
-        const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-        const float rx = x / angle, ry = y / angle, rz = z / angle;
-        float s, co;
-        sincosf(angle, &s, &co);
-        const float omc = 1.f - co;
-        // K = [[0,-rz,ry],[rz,0,-rx],[-ry,rx,0]];  R = I + sin K + (1 - cos) K K
-        const float kk[9] = {-(rz * rz) - ry * ry, rx * ry, rx * rz, rx * ry, -(rz * rz) - rx * rx, ry * rz, rx * rz, ry * rz, -(ry * ry) - rx * rx};
-        const float k1[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
+        const Rodrigues<float> q = rodrigues<float>(pose + ((size_t)g * J + tid) * 3);
 #pragma unroll
         for (int e = 0; e < 9; ++e) {
-            const float d = s * k1[e] + omc * kk[e];                  // R - I: the pose feature, without the cancellation of (I + d) - I
-            sR[tid][e] = ((e & 3) == 0 ? 1.f : 0.f) + d;
-            if (tid > 0) F[(size_t)(nc + 9 * (tid - 1) + e) * PG] = d;
+            sR[tid][e] = q.rotation(e);
+            if (tid > 0) F[(size_t)(nc + 9 * (tid - 1) + e) * PG] = q.minus_identity(e);      // the pose feature
         }
     }
     for (int t = tid; t < nc; t += 64) F[(size_t)t * PG] = coef[(size_t)g * nc + t];
-    for (int t = tid; t < 3 * J; t += 64) {
-        float a = c.J0[t];
-        for (int k = 0; k < nc; ++k) a = __builtin_fmaf(c.JS[(size_t)t * nc + k], coef[(size_t)g * nc + k], a);
-        sJ[t] = a;
-    }
+    for (int t = tid; t < 3 * J; t += 64) sJ[t] = shaped_joint<float>(c, coef + (size_t)g * nc, t);
     __syncthreads();
     for (int i = 0; i < J; ++i) {
-        const int p = i == 0 ? -1 : c.parents[i];
-        if (tid < 12) {
-            const int r = tid >> 2, cc = tid & 3;
-            float l[3];                                               // column cc of the local transform [R_i | J_i - J_parent]
-#pragma unroll
-            for (int m = 0; m < 3; ++m) l[m] = cc < 3 ? sR[i][3 * m + cc] : (p < 0 ? sJ[3 * i + m] : sJ[3 * i + m] - sJ[3 * p + m]);
-            float o;
-            if (p < 0) o = l[r];
-            else o = sG[p][4 * r] * l[0] + sG[p][4 * r + 1] * l[1] + sG[p][4 * r + 2] * l[2] + (cc == 3 ? sG[p][4 * r + 3] : 0.f);
-            sG[i][tid] = o;
-        }
+        const int p = body_parent(c, i);
+        if (tid < 12) sG[i][tid] = chain_element<float>(sR, sJ, sG, i, p, tid);
         __syncthreads();
     }
     if (tid < J) {
@@ -101,52 +64,18 @@ __global__ __launch_bounds__(VT * NW) void body_vertex_kernel(mhmr_body_consts c
                                                               float* __restrict__ vertices, float* __restrict__ v2d) {
     __shared__ float smem[KMAX * PG];                                 // features [k][8]; afterwards partial tiles [wave][24][64]
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, grp = blockIdx.y, v = blockIdx.x * VT + lane;
-    const int K = c.K, Vp = c.Vp;
+    const int K = c.K;
     const float* F = ws_F + (size_t)grp * K * PG;
     for (int i = threadIdx.x; i < K * PG; i += VT * NW) smem[i] = F[i];
     __syncthreads();
     float acc[PG][3];
-#pragma unroll
-    for (int p = 0; p < PG; ++p) acc[p][0] = acc[p][1] = acc[p][2] = 0.f;
-    const int kc = (K + NW - 1) / NW, k0 = w * kc, k1 = min(K, k0 + kc);
-    const float* b = c.basis + (size_t)k0 * 3 * Vp + v;
-#pragma unroll 4
-    for (int k = k0; k < k1; ++k, b += 3 * (size_t)Vp) {
-        const float b0 = b[0], b1 = b[Vp], b2 = b[2 * (size_t)Vp];
-        const f32x4 fa = *reinterpret_cast<const f32x4*>(smem + k * PG), fb = *reinterpret_cast<const f32x4*>(smem + k * PG + 4);
-        const float f[PG] = {fa[0], fa[1], fa[2], fa[3], fb[0], fb[1], fb[2], fb[3]};
-#pragma unroll
-        for (int p = 0; p < PG; ++p) {
-            acc[p][0] = __builtin_fmaf(f[p], b0, acc[p][0]);
-            acc[p][1] = __builtin_fmaf(f[p], b1, acc[p][1]);
-            acc[p][2] = __builtin_fmaf(f[p], b2, acc[p][2]);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < PG; ++p)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) smem[(w * 24 + p * 3 + a) * VT + lane] = acc[p][a];
-    __syncthreads();
+    basis_pass<4>(c, smem, v, w, acc, [](int, float, float, float) {});
+    deposit_partial_tiles(smem, w, lane, acc);
     const int g = grp * PG + w;                                       // wave w finishes person w of the group
     if (g >= G) return;
-    float vp[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float s = c.vtemp[(size_t)a * Vp + v];
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) s += smem[(ww * 24 + w * 3 + a) * VT + lane];
-        vp[a] = s;
-    }
-    float T[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) T[e] = 0.f;
-    const float* A = ws_A + (size_t)g * c.J * 12;
-    for (int j = 0; j < c.J; ++j) {
-        const float wj = c.weights[(size_t)j * Vp + v];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) T[e] = __builtin_fmaf(wj, A[12 * j + e], T[e]);
-    }
+    float vp[3], T[12];
+    v_posed(c, smem, w, lane, v, vp);
+    skin_blend(c, ws_A + (size_t)g * c.J * 12, v, T);
     if (v >= c.V) return;
     float x[3];
 #pragma unroll
@@ -278,12 +207,10 @@ __global__ __launch_bounds__(256) void rotvec_to_rotmat_kernel(const float* __re
 extern "C" int mhmr_body_forward(const mhmr_body_consts* c, const float* pose, const float* coef, const float* transl, const float* K, int G,
                                  float* ws_F, float* ws_A, float* vertices, float* joints, float* v2d, float* j2d, void* stream) {
     if (!c) return MHMR_ERR_BAD_ARG;
-    if (G < 0 || c->V <= 0 || c->Vp < c->V || c->Vp % VT != 0 || c->J <= 0 || c->J > JMAX || c->nc < 0 || c->E < 0 || c->L < 0 ||
-        c->K != c->nc + 9 * (c->J - 1) || c->K <= 0 || c->K > KMAX)
-        return MHMR_ERR_BAD_SHAPE;
+    if (G < 0 || body_bad_shape(c)) return MHMR_ERR_BAD_SHAPE;
     if (G == 0) return 0;
-    if (!pose || (c->nc > 0 && !coef) || !ws_F || !ws_A || !vertices || !joints || !c->vtemp || !c->basis || !c->J0 || (c->nc > 0 && !c->JS) ||
-        !c->parents || !c->weights || (c->E > 0 && !c->extra_idx) || (c->L > 0 && (!c->lmk_idx || !c->lmk_bary)) || (K && (!v2d || !j2d)))
+    if (body_missing_pointer(c, pose, coef, ws_F, ws_A, vertices, joints) || (c->E > 0 && !c->extra_idx) ||
+        (c->L > 0 && (!c->lmk_idx || !c->lmk_bary)) || (K && (!v2d || !j2d)))
         return MHMR_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int NJ = c->J + c->E + c->L, groups = (G + PG - 1) / PG;

@@ -12,22 +12,18 @@
 //                  above them (across the tiles of the range) is added in fp64 into the workgroup's own slice of the workspace, by the
 //                  same lanes in tile order.
 //   pose kernel    one workgroup per person, fp64 throughout (a few thousand operations): sums the range slices in index order,
-//                  recomputes Rodrigues / shaped joints / the kinematic chain from pose and coef, walks the tree in descending joint
-//                  order, differentiates Rodrigues along its own evaluation (angle = |v + 1e-8|, r = v / angle, sin K + (1 - cos) K K:
+//                  recomputes Rodrigues / shaped joints / the kinematic chain from pose and coef by the forward's own functions
+//                  (body_shared.h, at double), walks the tree in descending joint order, differentiates Rodrigues along the factors
+//                  that evaluation left (angle = |v + offset|, r = v / angle, sin K + (1 - cos) K K:
 //                  at v = 0 this is sin(angle) / angle * the antisymmetric part, nothing is divided by angle^3), and rounds each output
 //                  once.
 // The order of every sum depends on (V, G) only; a person's numbers do not depend on who shares its group.
 #include <algorithm>
-#include "mhmr_common.h"
+#include "body_shared.h"
 #include "mhmr_internal.h"
 
 namespace {
 
-constexpr int PG = 8;          // persons per pass over the basis      (as csrc/bodymodel.hip)
-constexpr int VT = 64;         // vertices per tile (= lanes)
-constexpr int NW = 8;          // waves per vertex workgroup
-constexpr int KMAX = 1536;
-constexpr int JMAX = 64;
 constexpr int TARGET_WG = 512; // vertex workgroups wanted when there are few person groups (two per CU of an MI355X)
 
 struct BwdArgs {
@@ -40,21 +36,12 @@ struct BwdArgs {
     int G, R, S, NJ;
 };
 
-// (u, v) = (K0 x/z + K1 y/z + K2, K3 x/z + K4 y/z + K5)  ->  g += J^T (gu, gv)
-__device__ __forceinline__ void project_bwd(const float* __restrict__ K, const float* __restrict__ x, float gu, float gv, float* g) {
-    const float iz = 1.f / x[2];
-    const float a = gu * K[0] + gv * K[3], b = gu * K[1] + gv * K[4];
-    g[0] += a * iz;
-    g[1] += b * iz;
-    g[2] -= (a * x[0] + b * x[1]) * iz * iz;
-}
-
 // 3D cotangent of output joint j of person g: g_joints + the projection Jacobian of g_j2d at the saved joint
 __device__ __forceinline__ void joint_cotangent(const BwdArgs& a, int g, int j, float* o) {
     const size_t t = (size_t)g * a.NJ + j;
     o[0] = o[1] = o[2] = 0.f;
     if (a.g_joints) { o[0] = a.g_joints[3 * t]; o[1] = a.g_joints[3 * t + 1]; o[2] = a.g_joints[3 * t + 2]; }
-    if (a.g_j2d) project_bwd(a.K + 9 * (size_t)g, a.joints + 3 * t, a.g_j2d[2 * t], a.g_j2d[2 * t + 1], o);
+    if (a.g_j2d) project_jacobian_t(a.K + 9 * (size_t)g, a.joints + 3 * t, a.g_j2d[2 * t], a.g_j2d[2 * t + 1], o);
 }
 
 // Sum over the 64 lanes of 8 (16) values per lane in 10 (19) exchanges: every step halves the values a lane carries.  All lanes end with a
@@ -106,7 +93,6 @@ __global__ __launch_bounds__(VT * NW) void body_vertex_bwd_kernel(BwdArgs a) {
     double* slice = a.ws + ((size_t)rg * G + (live ? g : 0)) * a.S;   // written only if live
     const float* F = a.ws_F + (size_t)grp * K * PG;
     const float* A = a.ws_A + (size_t)(live ? g : 0) * J * 12;
-    const int kc = (K + NW - 1) / NW, k0 = w * kc, k1 = min(K, k0 + kc);
     const int pl = bfly8_index(lane), gl = grp * PG + pl;             // the person whose g_F total lands in this lane
     double* fslice = a.ws + ((size_t)rg * G + (gl < G ? gl : 0)) * a.S;
     const bool fwrite = lane < 8 && gl < G;
@@ -122,7 +108,7 @@ __global__ __launch_bounds__(VT * NW) void body_vertex_bwd_kernel(BwdArgs a) {
         if (live && v < V) {
             const size_t t = (size_t)g * V + v;
             if (a.g_vertices) { gx[0] = a.g_vertices[3 * t]; gx[1] = a.g_vertices[3 * t + 1]; gx[2] = a.g_vertices[3 * t + 2]; }
-            if (a.g_v2d) project_bwd(a.K + 9 * (size_t)g, a.vertices + 3 * t, a.g_v2d[2 * t], a.g_v2d[2 * t + 1], gx);
+            if (a.g_v2d) project_jacobian_t(a.K + 9 * (size_t)g, a.vertices + 3 * t, a.g_v2d[2 * t], a.g_v2d[2 * t + 1], gx);
             tsum[0] += (double)gx[0]; tsum[1] += (double)gx[1]; tsum[2] += (double)gx[2];
             const int e1 = min(a.bc.inv_ptr[v + 1], a.bc.n);
             for (int e = max(a.bc.inv_ptr[v], 0); e < e1; ++e) {      // sorted by joint: a fixed order
@@ -134,15 +120,8 @@ __global__ __launch_bounds__(VT * NW) void body_vertex_bwd_kernel(BwdArgs a) {
                 gx[0] = __builtin_fmaf(bw, gj[0], gx[0]); gx[1] = __builtin_fmaf(bw, gj[1], gx[1]); gx[2] = __builtin_fmaf(bw, gj[2], gx[2]);
             }
         }
-        float Tr[9];
-#pragma unroll
-        for (int e = 0; e < 9; ++e) Tr[e] = 0.f;
-        if (live)
-            for (int j = 0; j < J; ++j) {
-                const float wj = c.weights[(size_t)j * Vp + v];
-#pragma unroll
-                for (int e = 0; e < 9; ++e) Tr[e] = __builtin_fmaf(wj, A[12 * j + 4 * (e / 3) + e % 3], Tr[e]);
-            }
+        float Tr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (live) skin_blend(c, A, v, Tr);
 #pragma unroll
         for (int cc = 0; cc < 3; ++cc) sGV[w][cc][lane] = Tr[cc] * gx[0] + Tr[3 + cc] * gx[1] + Tr[6 + cc] * gx[2];
         for (int i = threadIdx.x; i < K * PG; i += VT * NW) smem[i] = F[i];
@@ -150,42 +129,19 @@ __global__ __launch_bounds__(VT * NW) void body_vertex_bwd_kernel(BwdArgs a) {
         // ---- 2. one pass over the basis: v_posed partials of 8 persons, and g_F of this wave's k
         float acc[PG][3], gv[PG][3];
 #pragma unroll
-        for (int p = 0; p < PG; ++p) {
-            acc[p][0] = acc[p][1] = acc[p][2] = 0.f;
-            gv[p][0] = sGV[p][0][lane]; gv[p][1] = sGV[p][1][lane]; gv[p][2] = sGV[p][2][lane];
-        }
-        const float* b = c.basis + (size_t)k0 * 3 * Vp + v;
-        for (int k = k0; k < k1; ++k, b += 3 * (size_t)Vp) {
-            const float b0 = b[0], b1 = b[Vp], b2 = b[2 * (size_t)Vp];
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(smem + k * PG), fb = *reinterpret_cast<const f32x4*>(smem + k * PG + 4);
-            const float f[PG] = {fa[0], fa[1], fa[2], fa[3], fb[0], fb[1], fb[2], fb[3]};
+        for (int p = 0; p < PG; ++p) { gv[p][0] = sGV[p][0][lane]; gv[p][1] = sGV[p][1][lane]; gv[p][2] = sGV[p][2][lane]; }
+        basis_pass<1>(c, smem, v, w, acc, [&](int k, float b0, float b1, float b2) {
             float d[PG];
 #pragma unroll
-            for (int p = 0; p < PG; ++p) {
-                acc[p][0] = __builtin_fmaf(f[p], b0, acc[p][0]);
-                acc[p][1] = __builtin_fmaf(f[p], b1, acc[p][1]);
-                acc[p][2] = __builtin_fmaf(f[p], b2, acc[p][2]);
-                d[p] = __builtin_fmaf(b2, gv[p][2], __builtin_fmaf(b1, gv[p][1], b0 * gv[p][0]));
-            }
+            for (int p = 0; p < PG; ++p) d[p] = __builtin_fmaf(b2, gv[p][2], __builtin_fmaf(b1, gv[p][1], b0 * gv[p][0]));
             const float tot = bfly8(d, lane);
             if (fwrite) fslice[k] = first ? (double)tot : fslice[k] + (double)tot;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < PG; ++p)
-#pragma unroll
-            for (int x = 0; x < 3; ++x) smem[(w * 24 + p * 3 + x) * VT + lane] = acc[p][x];
-        __syncthreads();
+        });
+        deposit_partial_tiles(smem, w, lane, acc);
         // ---- 3. g_A of person w
         if (live) {
             float vp[4];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) {
-                float s = c.vtemp[(size_t)x * Vp + v];
-#pragma unroll
-                for (int ww = 0; ww < NW; ++ww) s += smem[(ww * 24 + w * 3 + x) * VT + lane];
-                vp[x] = s;
-            }
+            v_posed(c, smem, w, lane, v, vp);
             vp[3] = 1.f;
             double* ga = slice + K;
             for (int j = 0; j < J; ++j) {
@@ -226,32 +182,17 @@ __global__ __launch_bounds__(256) void body_pose_bwd_kernel(BwdArgs a) {
         for (int r = 0; r < a.R; ++r) s += a.ws[((size_t)r * G + g) * S + i];
         sS[i] = s;
     }
+    Rodrigues<double> q;                                              // of joint tid: kept for its derivative at the end
     if (tid < J) {
-        const float* v = a.pose + ((size_t)g * J + tid) * 3;
-        const double x = v[0], y = v[1], z = v[2];
-        const double ex = x + 1e-8, ey = y + 1e-8, ez = z + 1e-8;
-        const double angle = sqrt(ex * ex + ey * ey + ez * ez);
-        const double rx = x / angle, ry = y / angle, rz = z / angle, s = sin(angle), omc = 1.0 - cos(angle);
-        const double kk[9] = {-(rz * rz) - ry * ry, rx * ry, rx * rz, rx * ry, -(rz * rz) - rx * rx, ry * rz, rx * rz, ry * rz, -(ry * ry) - rx * rx};
-        const double k1[9] = {0.0, -rz, ry, rz, 0.0, -rx, -ry, rx, 0.0};
+        q = rodrigues<double>(a.pose + ((size_t)g * J + tid) * 3);
 #pragma unroll
-        for (int e = 0; e < 9; ++e) sR[tid][e] = ((e & 3) == 0 ? 1.0 : 0.0) + (s * k1[e] + omc * kk[e]);
+        for (int e = 0; e < 9; ++e) sR[tid][e] = q.rotation(e);
     }
-    for (int t = tid; t < 3 * J; t += 256) {
-        double s = c.J0[t];
-        for (int k = 0; k < nc; ++k) s += (double)c.JS[(size_t)t * nc + k] * (double)a.coef[(size_t)g * nc + k];
-        sJ[t] = s;
-    }
+    for (int t = tid; t < 3 * J; t += 256) sJ[t] = shaped_joint<double>(c, a.coef + (size_t)g * nc, t);
     __syncthreads();
-    for (int i = 0; i < J; ++i) {                                     // G_i = G_p [R_i | J_i - J_p]
-        const int p = i == 0 ? -1 : min(max(c.parents[i], 0), i - 1);
-        if (tid < 12) {
-            const int r = tid >> 2, cc = tid & 3;
-            double l[3];
-#pragma unroll
-            for (int m = 0; m < 3; ++m) l[m] = cc < 3 ? sR[i][3 * m + cc] : (p < 0 ? sJ[3 * i + m] : sJ[3 * i + m] - sJ[3 * p + m]);
-            sG[i][tid] = p < 0 ? l[r] : sG[p][4 * r] * l[0] + sG[p][4 * r + 1] * l[1] + sG[p][4 * r + 2] * l[2] + (cc == 3 ? sG[p][4 * r + 3] : 0.0);
-        }
+    for (int i = 0; i < J; ++i) {
+        const int p = body_parent(c, i);
+        if (tid < 12) sG[i][tid] = chain_element<double>(sR, sJ, sG, i, p, tid);
         __syncthreads();
     }
     // A_i = [G_i^rot | G_i^t - G_i^rot J_i],  joints_i = G_i^t + transl
@@ -270,7 +211,7 @@ __global__ __launch_bounds__(256) void body_pose_bwd_kernel(BwdArgs a) {
     }
     __syncthreads();
     for (int i = J - 1; i > 0; --i) {                                 // children come after their parents: every gG[i] is complete here
-        const int p = min(max(c.parents[i], 0), i - 1);
+        const int p = body_parent(c, i);
         if (tid < 9) {
             const int r = tid / 3, cc = tid % 3;
             gR[i][tid] = sG[p][r] * gG[i][cc] + sG[p][4 + r] * gG[i][4 + cc] + sG[p][8 + r] * gG[i][8 + cc];
@@ -292,17 +233,13 @@ __global__ __launch_bounds__(256) void body_pose_bwd_kernel(BwdArgs a) {
         double Gm[9];
 #pragma unroll
         for (int e = 0; e < 9; ++e) Gm[e] = gR[tid][e] + (tid > 0 ? sS[nc + 9 * (tid - 1) + e] : 0.0);
+        // the derivative of rodrigues() along the factors it left
         const float* v = a.pose + ((size_t)g * J + tid) * 3;
         const double x[3] = {v[0], v[1], v[2]};
-        const double ev[3] = {x[0] + 1e-8, x[1] + 1e-8, x[2] + 1e-8};
-        const double angle = sqrt(ev[0] * ev[0] + ev[1] * ev[1] + ev[2] * ev[2]);
-        const double r[3] = {x[0] / angle, x[1] / angle, x[2] / angle}, s = sin(angle), co = cos(angle), omc = 1.0 - co;
-        const double rx = r[0], ry = r[1], rz = r[2];
-        const double kk[9] = {-(rz * rz) - ry * ry, rx * ry, rx * rz, rx * ry, -(rz * rz) - rx * rx, ry * rz, rx * rz, ry * rz, -(ry * ry) - rx * rx};
-        const double k1[9] = {0.0, -rz, ry, rz, 0.0, -rx, -ry, rx, 0.0};
+        const double angle = q.angle, s = q.s, co = q.co, omc = q.omc, *r = q.r, *ev = q.e, rx = r[0], ry = r[1], rz = r[2];
         double g_s = 0.0, g_omc = 0.0;
 #pragma unroll
-        for (int e = 0; e < 9; ++e) { g_s += Gm[e] * k1[e]; g_omc += Gm[e] * kk[e]; }
+        for (int e = 0; e < 9; ++e) { g_s += Gm[e] * q.k1[e]; g_omc += Gm[e] * q.kk[e]; }
         const double tr = Gm[0] + Gm[4] + Gm[8];
         double g_r[3] = {s * (Gm[7] - Gm[5]), s * (Gm[2] - Gm[6]), s * (Gm[3] - Gm[1])};     // through sin K(r)
 #pragma unroll
@@ -338,27 +275,20 @@ int tile_ranges(const mhmr_body_consts* c, int G) {
     return groups <= 0 ? 1 : std::max(1, std::min(tiles, (TARGET_WG + groups - 1) / groups));
 }
 
-bool bad_shape(const mhmr_body_consts* c) {
-    return c->V <= 0 || c->Vp < c->V || c->Vp % VT != 0 || c->J <= 0 || c->J > JMAX || c->nc < 0 || c->E < 0 || c->L < 0 ||
-           c->K != c->nc + 9 * (c->J - 1) || c->K <= 0 || c->K > KMAX;
-}
-
 }  // namespace
 
 extern "C" long long mhmr_body_backward_workspace_bytes(const mhmr_body_consts* c, int G) {
     if (!c || G < 0) return MHMR_ERR_BAD_ARG;
-    if (bad_shape(c)) return MHMR_ERR_BAD_SHAPE;
+    if (body_bad_shape(c)) return MHMR_ERR_BAD_SHAPE;
     return (long long)tile_ranges(c, G) * G * (c->K + 12 * c->J + 3) * (long long)sizeof(double);
 }
 
 extern "C" int mhmr_body_backward(const mhmr_body_backward_desc* d, void* stream) {
     if (!d || !d->c || d->G < 0) return MHMR_ERR_BAD_ARG;
     const mhmr_body_consts* c = d->c;
-    if (bad_shape(c) || (d->G + PG - 1) / PG > 65535) return MHMR_ERR_BAD_SHAPE;
+    if (body_bad_shape(c) || (d->G + PG - 1) / PG > 65535) return MHMR_ERR_BAD_SHAPE;
     if (d->G == 0) return 0;
-    if (!d->pose || (c->nc > 0 && !d->coef) || !d->ws_F || !d->ws_A || !d->vertices || !d->joints || !c->vtemp || !c->basis || !c->J0 ||
-        (c->nc > 0 && !c->JS) || !c->parents || !c->weights)
-        return MHMR_ERR_BAD_ARG;
+    if (body_missing_pointer(c, d->pose, d->coef, d->ws_F, d->ws_A, d->vertices, d->joints)) return MHMR_ERR_BAD_ARG;
     const mhmr_body_bwd_consts* bc = d->bc;
     if (!bc || !bc->inv_ptr || bc->n != c->E + 3 * c->L || (bc->n > 0 && (!bc->inv_joint || !bc->inv_w))) return MHMR_ERR_BAD_ARG;
     if ((d->g_v2d || d->g_j2d) && !d->K) return MHMR_ERR_BAD_ARG;

@@ -13,10 +13,11 @@
 //       waves in index order, one slot of the workspace per (person, tile); the finishing kernel adds the tiles in index order, adds the
 //       caller's own g_transl, and takes S_p off the centre joint's row.  No floating-point atomic anywhere.
 //   decode backward (mhmr_heads_decode_backward)     the derivative of hph_decode_kernel + loc_kernel (csrc/hph.hip): one thread per
-//       (person, joint) recomputes the decode from the saved fp32 read-out row in fp64 and differentiates exactly that evaluation; thread 0
-//       also does the distance chain and the offsets.  Each output is rounded to fp32 once.
+//       (person, joint) calls the forward's own decode functions (hph_shared.h, mhmr_common.h) at double on the saved fp32 read-out row and
+//       differentiates the intermediates they return; thread 0 also does the distance chain and the offsets.  Each output is rounded once.
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
+#include "hph_shared.h"
 
 namespace {
 
@@ -40,16 +41,12 @@ __device__ __forceinline__ f32x4 load16(const float* p) {       // 16 bytes from
 }
 __device__ __forceinline__ void store16(float* p, f32x4 v) { __builtin_memcpy(p, &v, 16); }
 
-// gx = g3 + J^T g2 at x = (u - jc) + t;  (u, v) = (K0 x/z + K1 y/z + K2, K3 x/z + K4 y/z + K5)   (as project_bwd of csrc/bodymodel_bwd.hip)
+// gx = g3 + J^T g2 at the placed point x = (u - jc) + t
 __device__ __forceinline__ void point_cotangent(const float* u, const float* jc, const float* t, const float* K, bool has2, float gu, float gv,
                                                 float* g) {
     if (!has2) return;
-    const float x = (u[0] - jc[0]) + t[0], y = (u[1] - jc[1]) + t[1], z = (u[2] - jc[2]) + t[2];
-    const float iz = 1.f / z;
-    const float a = gu * K[0] + gv * K[3], b = gu * K[1] + gv * K[4];
-    g[0] += a * iz;
-    g[1] += b * iz;
-    g[2] -= (a * x + b * y) * iz * iz;
+    const float x[3] = {(u[0] - jc[0]) + t[0], (u[1] - jc[1]) + t[1], (u[2] - jc[2]) + t[2]};
+    project_jacobian_t(K, x, gu, gv, g);
 }
 
 __global__ __launch_bounds__(NT) void heads_place_bwd_kernel(PlaceArgs a) {
@@ -166,47 +163,22 @@ __global__ __launch_bounds__(64) void heads_decode_bwd_kernel(DecodeBwdArgs a) {
     const float* dp = a.readout + (size_t)p * a.ldr;
     float* go = a.g_readout + (size_t)p * W;
     if (j < 53) {
-        // ---- the forward of hph_decode_kernel, in fp64
-        const double a6[3] = {dp[6 * j], dp[6 * j + 1], dp[6 * j + 2]}, b6[3] = {dp[6 * j + 3], dp[6 * j + 4], dp[6 * j + 5]};
-        const double nx = sqrt(a6[0] * a6[0] + a6[1] * a6[1] + a6[2] * a6[2]);
-        const double x[3] = {a6[0] / nx, a6[1] / nx, a6[2] / nx};
-        const double dxy = x[0] * b6[0] + x[1] * b6[1] + x[2] * b6[2];
-        const double yr[3] = {b6[0] - dxy * x[0], b6[1] - dxy * x[1], b6[2] - dxy * x[2]};
-        const double ny = sqrt(yr[0] * yr[0] + yr[1] * yr[1] + yr[2] * yr[2]);
-        const double y[3] = {yr[0] / ny, yr[1] / ny, yr[2] / ny};
-        const double z[3] = {x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]};
-        const double R[9] = {x[0], y[0], z[0], x[1], y[1], z[1], x[2], y[2], z[2]};
-        const double tr = R[0] + R[4] + R[8];
-        int choice = 0;
-        double best = R[0];
-        if (R[4] > best) { best = R[4]; choice = 1; }
-        if (R[8] > best) { best = R[8]; choice = 2; }
-        if (tr > best) { best = tr; choice = 3; }
-        const int ci = choice == 3 ? 0 : choice, cj = (ci + 1) % 3, ck = (cj + 1) % 3;
-        double q[4];                                                  // XYZW, before the normalisation
-        if (choice == 3) {
-            q[0] = R[7] - R[5]; q[1] = R[2] - R[6]; q[2] = R[3] - R[1]; q[3] = 1.0 + tr;
-        } else {
-            q[ci] = 1.0 - tr + 2.0 * R[ci * 3 + ci];
-            q[cj] = R[cj * 3 + ci] + R[ci * 3 + cj];
-            q[ck] = R[ck * 3 + ci] + R[ci * 3 + ck];
-            q[3] = R[ck * 3 + cj] - R[cj * 3 + ck];
-        }
-        const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        double u[4] = {q[0] / qn, q[1] / qn, q[2] / qn, q[3] / qn};   // the unit quaternion, before the flip
-        const double sgn = u[3] < 0.0 ? -1.0 : 1.0;
-        const double f[4] = {sgn * u[0], sgn * u[1], sgn * u[2], sgn * u[3]};
-        const double n3 = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
-        const double angle = 2.0 * atan2(n3, f[3]);
-        const bool series = fabs(angle) <= 1e-3;
-        double sc, dsc;                                               // the scale and its derivative by the angle
-        if (series) {
-            const double a2 = angle * angle;
-            sc = 2.0 + a2 / 12.0 + 7.0 * a2 * a2 / 2880.0;
-            dsc = angle / 6.0 + 7.0 * a2 * angle / 720.0;
+        // ---- the forward: hph_decode_kernel's own functions at double, which leave what is differentiated below
+        const double b6[3] = {dp[6 * j + 3], dp[6 * j + 4], dp[6 * j + 5]};
+        double R[9], rv[3];
+        const Rot6dSteps<double> gs = rot6d_to_rotmat<double>(dp[6 * j], dp[6 * j + 1], dp[6 * j + 2], b6[0], b6[1], b6[2], R);
+        const RotvecSteps<double> rs = rotmat_to_rotvec(R, rv);
+        const double *x = gs.x, *y = gs.y, nx = gs.nx, ny = gs.ny, dxy = gs.dxy;
+        const double *f = rs.f, qn = rs.qn, sgn = rs.sgn, n3 = rs.n3, angle = rs.angle, sc = rs.sc;
+        const int choice = rs.choice;
+        int ci, cj, ck;
+        quat_branch_axes(choice == 3 ? 0 : choice, ci, cj, ck);
+        const double u[4] = {sgn * f[0], sgn * f[1], sgn * f[2], sgn * f[3]};                  // the unit quaternion, before the flip
+        double dsc;                                                   // the derivative of the scale by the angle
+        if (rs.series) {
+            dsc = angle / 6.0 + 7.0 * (angle * angle) * angle / 720.0;
         } else {
             const double sh = sin(angle / 2.0), ch = cos(angle / 2.0);
-            sc = angle / sh;
             dsc = 1.0 / sh - angle * ch / (2.0 * sh * sh);
         }
         // ---- backwards: rotvec = sc * f_xyz
@@ -270,15 +242,10 @@ __global__ __launch_bounds__(64) void heads_decode_bwd_kernel(DecodeBwdArgs a) {
         double k[9], inv[9];
 #pragma unroll
         for (int e = 0; e < 9; ++e) k[e] = Kp[e];
-        const double det = k[0] * (k[4] * k[8] - k[5] * k[7]) - k[1] * (k[3] * k[8] - k[5] * k[6]) + k[2] * (k[3] * k[7] - k[4] * k[6]);
-        inv[0] = (k[4] * k[8] - k[5] * k[7]) / det; inv[1] = (k[2] * k[7] - k[1] * k[8]) / det; inv[2] = (k[1] * k[5] - k[2] * k[4]) / det;
-        inv[3] = (k[5] * k[6] - k[3] * k[8]) / det; inv[4] = (k[0] * k[8] - k[2] * k[6]) / det; inv[5] = (k[2] * k[3] - k[0] * k[5]) / det;
-        inv[6] = (k[3] * k[7] - k[4] * k[6]) / det; inv[7] = (k[1] * k[6] - k[0] * k[7]) / det; inv[8] = (k[0] * k[4] - k[1] * k[3]) / det;
-        const double d0 = dp[318 + nb], scale = k[0] / a.fn, dl = d0 * scale;
-        const double ex = a.nearness ? exp(dl) : 0.0, d = a.nearness ? ex - 1e-10 : dl;
-        const double dist = fmin(fmax(d, 0.0), 50.0);
-        const double loc[2] = {((double)a.det_x[p] + 0.5 + (double)a.offset[2 * p]) * (double)a.patch,
-                               ((double)a.det_y[p] + 0.5 + (double)a.offset[2 * p + 1]) * (double)a.patch};
+        inv3x3(k, inv);
+        const DistSteps<double> ds = decode_dist((double)dp[318 + nb], k[0], a.fn, a.nearness);
+        const double scale = ds.scale, ex = ds.ex, d = ds.d, dist = ds.dist;
+        const double loc[2] = {decode_loc(a.det_x[p], a.offset[2 * p], (double)a.patch), decode_loc(a.det_y[p], a.offset[2 * p + 1], (double)a.patch)};
         double gt[3] = {0.0, 0.0, 0.0};
         if (a.g_transl)
 #pragma unroll

@@ -410,10 +410,7 @@ __global__ __launch_bounds__(64) void hph_decode_kernel(const float* __restrict_
     if (j == 0) {
         const float d0 = dp[318 + nb];
         dist_pp[p] = d0;
-        const float focal = Kmat[det_b[p] * 9 + 0];
-        float d = d0 * (focal / fn);
-        if (nearness) d = expf(d) - 1e-10f;
-        dist[p] = fminf(fmaxf(d, 0.f), 50.f);
+        dist[p] = decode_dist(d0, Kmat[det_b[p] * 9 + 0], fn, nearness).dist;
     }
 }
 
@@ -422,8 +419,8 @@ __global__ void loc_kernel(const float* __restrict__ offset, const int* __restri
                            float patch, float* __restrict__ loc, int P) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
-    loc[2 * p] = ((float)det_x[p] + 0.5f + offset[2 * p]) * patch;
-    loc[2 * p + 1] = ((float)det_y[p] + 0.5f + offset[2 * p + 1]) * patch;
+    loc[2 * p] = decode_loc(det_x[p], offset[2 * p], patch);
+    loc[2 * p + 1] = decode_loc(det_y[p], offset[2 * p + 1], patch);
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// What the person head's forward (hph.hip, anny.hip) and its backward (hph_bwd.hip) both compute, defined once: the backward
+// What the person head's forward (hph.hip, anny.hip) and its backward (hph_bwd.hip, heads_bwd.hip) both compute, defined once: the backward
 // differentiates the evaluation the forward runs because both call the functions below.  Changing an expression, its association or a
 // branch here changes forward and backward together; nothing here may be copied into a kernel.
 #pragma once
@@ -169,48 +169,91 @@ __device__ __forceinline__ bool cross_attn_row(const float* __restrict__ q, cons
     return true;
 }
 
-// ---- read-out decode (roma special_gramschmidt / rotmat_to_rotvec), shared by hph_decode_kernel and anny_decode_kernel
+// ---- read-out decode (roma special_gramschmidt / rotmat_to_rotvec; utils/camera.py:71-90; model.py:272-275), shared by
+// hph_decode_kernel, loc_kernel and anny_decode_kernel at float and by heads_decode_bwd_kernel (heads_bwd.hip) at double.  Each function
+// returns the intermediates of its evaluation: the backward differentiates those, it does not form them again.
+template <typename T>
+struct Rot6dSteps {
+    T nx, x[3], dxy, ny, y[3];        // |a|, x = a / |a|, x . b, |b - (x . b) x|, y = the normalised remainder
+};
 // 6D -> rotation: x, y = the two given columns; R = [x' y' x'^y'] row-major (columns x', y', z)
-__device__ __forceinline__ void rot6d_to_rotmat(float x0, float x1, float x2, float y0, float y1, float y2, float (&R)[9]) {
-    const float nx = sqrtf(x0 * x0 + x1 * x1 + x2 * x2);
+template <typename T>
+__device__ __forceinline__ Rot6dSteps<T> rot6d_to_rotmat(T x0, T x1, T x2, T y0, T y1, T y2, T (&R)[9]) {
+    const T nx = sqrt(x0 * x0 + x1 * x1 + x2 * x2);
     x0 /= nx; x1 /= nx; x2 /= nx;
-    const float dxy = x0 * y0 + x1 * y1 + x2 * y2;
+    const T dxy = x0 * y0 + x1 * y1 + x2 * y2;
     y0 -= dxy * x0; y1 -= dxy * x1; y2 -= dxy * x2;
-    const float ny = sqrtf(y0 * y0 + y1 * y1 + y2 * y2);
+    const T ny = sqrt(y0 * y0 + y1 * y1 + y2 * y2);
     y0 /= ny; y1 /= ny; y2 /= ny;
-    const float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
+    const T z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
     R[0] = x0; R[1] = y0; R[2] = z0; R[3] = x1; R[4] = y1; R[5] = z1; R[6] = x2; R[7] = y2; R[8] = z2;
+    return {nx, {x0, x1, x2}, dxy, ny, {y0, y1, y2}};
 }
 
+template <typename T>
+struct RotvecSteps {
+    int choice;                       // argmax over (R00, R11, R22, trace), first maximal index wins
+    T q[4], qn;                       // the quaternion (XYZW) of that branch before the normalisation, its norm
+    T sgn, f[4];                      // -1 where w < 0 flipped the unit quaternion; the unit quaternion after the flip
+    T n3, angle, sc;                  // |f_xyz|, 2 atan2(n3, f_w), rotvec = sc f_xyz
+    bool series;                      // |angle| <= 1e-3: sc by its series
+};
+// the axes (i, j, k) of a branch choice < 3: q_i from the diagonal, q_j and q_k from the sums with axis i, w from the (k, j) difference
+__device__ __forceinline__ void quat_branch_axes(int choice, int& i, int& jj, int& kk) { i = choice; jj = (i + 1) % 3; kk = (jj + 1) % 3; }
 // rotmat -> unit quaternion (XYZW), branch on the largest of (R00, R11, R22, trace) -> rotation vector v[3]
-__device__ __forceinline__ void rotmat_to_rotvec(const float (&R)[9], float* __restrict__ v) {
-    const float tr = R[0] + R[4] + R[8];
-    float qx, qy, qz, qw;
-    int choice = 0;  // argmax over (R00, R11, R22, trace), first maximal index wins
-    float best = R[0];
+template <typename T>
+__device__ __forceinline__ RotvecSteps<T> rotmat_to_rotvec(const T (&R)[9], T* __restrict__ v) {
+    static_assert((float)1e-3 == 1e-3f && (float)1e-10 == 1e-10f, "the decode's constants are the same numbers at either scalar");
+    const T tr = R[0] + R[4] + R[8];
+    T qx, qy, qz, qw;
+    int choice = 0;
+    T best = R[0];
     if (R[4] > best) { best = R[4]; choice = 1; }
     if (R[8] > best) { best = R[8]; choice = 2; }
     if (tr > best) { best = tr; choice = 3; }
     if (choice == 3) {
-        qx = R[7] - R[5]; qy = R[2] - R[6]; qz = R[3] - R[1]; qw = 1.f + tr;
+        qx = R[7] - R[5]; qy = R[2] - R[6]; qz = R[3] - R[1]; qw = T(1) + tr;
     } else {
-        const int i = choice, jj = (i + 1) % 3, kk = (jj + 1) % 3;
-        float qq[3];
-        qq[i] = 1.f - tr + 2.f * R[i * 3 + i];
+        int i, jj, kk;
+        quat_branch_axes(choice, i, jj, kk);
+        T qq[3];
+        qq[i] = T(1) - tr + T(2) * R[i * 3 + i];
         qq[jj] = R[jj * 3 + i] + R[i * 3 + jj];
         qq[kk] = R[kk * 3 + i] + R[i * 3 + kk];
         qw = R[kk * 3 + jj] - R[jj * 3 + kk];
         qx = qq[0]; qy = qq[1]; qz = qq[2];
     }
-    const float qn = sqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
+    const T q0 = qx, q1 = qy, q2 = qz, q3 = qw;
+    const T qn = sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
     qx /= qn; qy /= qn; qz /= qn; qw /= qn;
-    if (qw < 0.f) { qx = -qx; qy = -qy; qz = -qz; qw = -qw; }
-    const float angle = 2.f * atan2f(sqrtf(qx * qx + qy * qy + qz * qz), qw);
-    float sc;
-    if (fabsf(angle) <= 1e-3f) sc = 2.f + angle * angle / 12.f + 7.f * angle * angle * angle * angle / 2880.f;
-    else sc = angle / sinf(angle / 2.f);
+    const T sgn = qw < T(0) ? T(-1) : T(1);
+    if (qw < T(0)) { qx = -qx; qy = -qy; qz = -qz; qw = -qw; }
+    const T n3 = sqrt(qx * qx + qy * qy + qz * qz);
+    const T angle = T(2) * atan2(n3, qw);
+    const bool series = fabs(angle) <= T(1e-3);
+    T sc;
+    if (series) sc = T(2) + angle * angle / T(12) + T(7) * angle * angle * angle * angle / T(2880);
+    else sc = angle / sin(angle / T(2));
     v[0] = sc * qx; v[1] = sc * qy; v[2] = sc * qz;
+    return {choice, {q0, q1, q2, q3}, qn, sgn, {qx, qy, qz, qw}, n3, angle, sc, series};
 }
+
+// distance post-processing (utils/camera.py:71-90, model.py:196-203): d0 focal / fn, exp(.) - 1e-10 with nearness, clamp to [0, 50]
+template <typename T>
+struct DistSteps {
+    T scale, ex, d, dist;             // focal / fn; exp(d0 scale) with nearness (else 0); the distance before the clamp and after
+};
+template <typename T>
+__device__ __forceinline__ DistSteps<T> decode_dist(T d0, T focal, T fn, int nearness) {
+    DistSteps<T> st = {focal / fn, T(0)};
+    st.d = d0 * st.scale;
+    if (nearness) { st.ex = exp(st.d); st.d = st.ex - T(1e-10); }
+    st.dist = fmin(fmax(st.d, T(0)), T(50));
+    return st;
+}
+// offsets -> loc, one coordinate:  loc = (cell + 0.5 + offset) * patch     (model.py:272-275)
+template <typename T>
+__device__ __forceinline__ T decode_loc(int cell, float offset, T patch) { return ((T)cell + T(0.5) + (T)offset) * patch; }
 
 // ---- detection: hidden16[row] . w2 over a wave (C % 128 == 0), the sum in every lane
 template <int DT>

@@ -116,14 +116,31 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// inverse of a row-major 3x3 by the adjugate, every cofactor TIMES 1 / det
-__device__ __forceinline__ void inv3x3(const float* k, float* o) {
-    const float a = k[0], b = k[1], c = k[2], d = k[3], e = k[4], f = k[5], g = k[6], h = k[7], i = k[8];
-    const float A = e * i - f * h, B = -(d * i - f * g), Cc = d * h - e * g;
-    const float id = 1.0f / (a * A + b * B + c * Cc);
+// inverse of a row-major 3x3 by the adjugate, every cofactor TIMES 1 / det (float: the forwards; double: the decode backward)
+template <typename T>
+__device__ __forceinline__ void inv3x3(const T* k, T* o) {
+    const T a = k[0], b = k[1], c = k[2], d = k[3], e = k[4], f = k[5], g = k[6], h = k[7], i = k[8];
+    const T A = e * i - f * h, B = -(d * i - f * g), Cc = d * h - e * g;
+    const T id = T(1) / (a * A + b * B + c * Cc);
     o[0] = A * id; o[1] = -(b * i - c * h) * id; o[2] = (b * f - c * e) * id;
     o[3] = B * id; o[4] = (a * i - c * g) * id;  o[5] = -(a * f - c * d) * id;
     o[6] = Cc * id; o[7] = -(a * h - b * g) * id; o[8] = (a * e - b * d) * id;
+}
+
+// Pinhole projection, utils/camera.py:14-27: y = x / x_z, then K y (all three terms, as the einsum), and its Jacobian.  One definition
+// for the body model's forward and backward and for the placement backward of the prediction decode.
+__device__ __forceinline__ void project(const float* __restrict__ K, float x, float y, float z, float* __restrict__ out) {
+    const float a = x / z, b = y / z, c = z / z;
+    out[0] = K[0] * a + K[1] * b + K[2] * c;
+    out[1] = K[3] * a + K[4] * b + K[5] * c;
+}
+// (u, v) = (K0 x/z + K1 y/z + K2, K3 x/z + K4 y/z + K5)  ->  g += J^T (gu, gv) at the point x
+__device__ __forceinline__ void project_jacobian_t(const float* __restrict__ K, const float* __restrict__ x, float gu, float gv, float* g) {
+    const float iz = 1.f / x[2];
+    const float a = gu * K[0] + gv * K[3], b = gu * K[1] + gv * K[4];
+    g[0] += a * iz;
+    g[1] += b * iz;
+    g[2] -= (a * x[0] + b * x[1]) * iz * iz;
 }
 
 // GELU for 16-bit outputs.  x Phi(x) = max(x, 0) - |x| Q(|x|), Q(a) = erfc(a / sqrt 2) / 2 the upper tail of the normal law (erf is

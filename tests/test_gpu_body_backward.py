@@ -240,3 +240,31 @@ def test_nobody(small):
     assert tuple(out.v2d.shape) == (0, 1000, 2) and tuple(out.j2d.shape) == (0, 127, 2) and out.vertices.is_cuda
     (out.vertices.sum() + out.j2d.sum()).backward()
     assert all(t.grad is not None and t.grad.shape == t.shape for t in (go_, betas, tr))
+
+
+def test_a_malformed_parent_table_is_the_same_tree_in_both_directions():
+    """csrc/body_shared.h body_parent: forward and backward read the parent of joint i clamped into [0, i - 1].  BodyModel refuses a table
+    with parents[5] = 7 or parents[3] = -1, so it is planted in the packed constants that go to mhmr_body_forward / mhmr_body_backward:
+    outputs and gradients must be bit-equal to the table that holds 4 and 0 there."""
+    d = dict(synthetic.make_smplx_data(3, num_verts=1000, num_faces=2000))
+    d["extra_joint_verts"] = np.arange(21) * 47 + 5
+    G = 2
+    a = dict(kind="smplx", nb=11)
+
+    def run(p5, p3):
+        m = BodyModel(d, "smplx", num_betas=11)
+        a["model"] = m
+        p = m._consts(torch.device(DEV))
+        table = torch.from_numpy(m.parents).to(torch.int32)
+        table[5], table[3] = p5, p3
+        assert int(table.min()) >= -1 and int(table.max()) < m.num_joints
+        p["parents"] = table.to(DEV)
+        p["struct"].parents = p["parents"].data_ptr()
+        pose, coef, transl, K = inputs(a, G, seed=111)
+        grads, out = kernel_grads(a, pose, coef, transl, K, cotangents(a, G, seed=112))
+        return [getattr(out, k).detach() for k in OUTS] + list(grads)
+
+    bad, good = run(7, -1), run(4, 0)
+    for n, x, y in zip(OUTS + ("g_pose", "g_coef", "g_transl"), bad, good):
+        assert bool(torch.isfinite(x).all()) and float(x.abs().max()) > 0, n
+        assert torch.equal(x, y), n

@@ -202,6 +202,22 @@ def test_no_dot_product_hides_inside_inline_assembly():
                 assert "v_dot" not in m.group(2), (f, m.group(2))
 
 
+def test_body_model_and_decode_constants_live_in_the_shared_headers_only():
+    """The body model's backward and the decode's backward differentiate the evaluation the forward runs because both call
+    csrc/body_shared.h, csrc/hph_shared.h and csrc/mhmr_common.h.  A kernel file that spells Rodrigues' offset or the
+    series coefficient of the rotation-vector scale again has restated a forward; the tile limits have one definition."""
+    csrc = os.path.join(ROOT, "multi_hmr_amd", "csrc")
+    strip = lambda f: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read())          # (comments may quote the formulas)
+    for f in ("bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph.hip", "anny.hip"):
+        text = strip(f)
+        for literal in ("1e-8", "2880"):
+            assert literal not in text, (f, literal)
+    assert "1e-8" in strip("body_shared.h") and "2880" in strip("hph_shared.h")
+    for name in ("PG", "KMAX", "JMAX"):
+        owners = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) and re.search(r"\b%s\s*=" % name, strip(f))]
+        assert owners == ["body_shared.h"], (name, owners)
+
+
 def test_pack_smplx_rejects_a_basis_outside_the_f16_pair_range(smplx_data):
     """The blend basis travels as an f16 pair scaled by 2^10: a body model whose blend shapes are 100x larger would overflow
     silently on the GPU; pack_smplx refuses it."""
