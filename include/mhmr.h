@@ -238,7 +238,11 @@ int mhmr_cls_linear16(const void* A, long long a_stride, const void* W, int ldw,
  * (MHMR_EPI_VT); out: op16 [B*Tp, C] = softmax_2(Q K^T) V over the T real keys of each image.
  * `out` (here, in mhmr_attention16_ex and as mhmr_vit_desc.att) must be ZERO-INITIALISED ONCE by the caller: a 128-query workgroup whose
  * rows are all padding (rows >= T of an image) returns without storing, so those rows keep what was allocated; the linears behind read
- * them (row-local: real rows never depend on them) and NaN / Inf bit patterns there would be carried along.                       */
+ * them (row-local: real rows never depend on them) and NaN / Inf bit patterns there would be carried along.
+ * Padding cannot reach a real row, bit for bit: keys >= T are masked behind the matrix pipe (their K rows and V^T columns may hold any
+ * finite values), and a QUERY row >= T that shares a wave with real rows is computed with Q = 0 whatever the buffer holds there (its output
+ * row is the finite mean of V), so it can neither move the wave's reference level nor flag its workgroup for the textbook pass.
+ * Every row < T is written on every call, whatever `out` held before.                                                              */
 int mhmr_attention16(const void* qk, const void* vt, void* out, int B, int T, int Tp, int C, int H, int dtype,
                      void* stream);
 /* The attention kernel forms (csrc/attention.hip), for tests and A/B measurements.  Every form subtracts a per-query reference
@@ -273,7 +277,8 @@ int mhmr_layernorm16_pitch(const float* in, const float* w, const float* b, void
                            int dtype, void* stream);
 /* The attention of the f16x3 mode (csrc/attention_f32.hip): qkv fp32 [B*Tp, 3C] = (Q | K | V) un-scaled, head h at columns h*64;
  * out op16 PAIR [B*Tp, 2C] = [hi | lo] of softmax(Q K^T / 8) V over the T real keys; every product on v_mfma_f32_16x16x4_f32 (exact fp32).
- * Rows >= T of an image are written as zeros or as the (finite) attention of a padding row: never left unwritten.   Tp % 64 == 0. */
+ * Rows >= T of an image are written as zeros or as the (finite) attention of a padding row: never left unwritten.   Tp % 64 == 0.
+ * hi and lo are taken from ONE fp32 value of o: hi + lo = o to 2^-22 (f16) / 2^-16 (bf16) relative, ties of op16(o) included. */
 int mhmr_attention_f32(const float* qkv, void* out, int B, int T, int Tp, int C, int H, int dtype, void* stream);
 /* Producers of operand PAIRS in the f16x3 mode: out16 rows of 2 C (2 N) values = [hi = op16(y) | lo = op16(y - hi)].
  * mhmr_layernorm16_pair: y = LayerNorm(in row) (C in {384, 768, 1024}); mhmr_gelu16_pair: y = gelu_erf(in[m][n]), in fp32 [M, N], N % 4 == 0. */

@@ -109,11 +109,17 @@ __device__ __forceinline__ void attn_body(
     const bool active = qt * QB + 32 * w < T;  // a wave whose 32 query rows are all padding (T = 64 n + 1: three of the four waves
                                                // of every image's last workgroup) skips the arithmetic and stores zeros
     const bool in_buf = qt * QB + 32 * w < Tp;   // QB = 256: the last workgroup's upper waves lie past the padded rows
+    // (a query row >= T is computed with Q = 0, whatever the buffer holds there: next to real rows in a wave, a padding row must not move
+    // MODE 2's wave-uniform level branch or raise MODE 3's flag -- either changes the rounding order of the REAL rows)
     V8 qf[4] = {};
     if (in_buf) {
         const Tt* qp = qk + (row0 + q_row) * ldq + h * 64 + 8 * hi;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const V8*)(qp + 16 * ks);
+        if (q_row >= T) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) qf[ks] = V8{};
+        }
     }
 
     // ---- staging addresses: one glds16 per thread moves 64 * NW chunks of 16 B = 8 * NW tile rows ----
@@ -874,13 +880,17 @@ __device__ __forceinline__ void attn16_tail(const typename Op<DT>::T* __restrict
     typedef typename Op<DT>::V4 V4;
     constexpr int QB = 128;
     // Q fragments (second operand): lane (j, g) holds Q[16 qb + j][32 ks + 8 g + 0..7]
+    // (a query row >= T is computed with Q = 0, whatever the buffer holds there: a padding row next to real ones in a wave must not be
+    // able to raise the workgroup's flag -- the textbook pass would then rewrite the REAL rows in another rounding order)
     V8 qf[2][2] = {};
-    if (in_buf) {
 #pragma unroll
-        for (int qb = 0; qb < NQB; ++qb) {
-            const Tt* qp = qk + (row0 + qt * QB + 32 * w + 16 * qb + j15) * ldq + h * 64 + 8 * g;
+    for (int qb = 0; qb < NQB; ++qb) {
+        const int q_row = qt * QB + 32 * w + 16 * qb + j15;
+        if (in_buf) {
+            const Tt* qp = qk + (row0 + q_row) * ldq + h * 64 + 8 * g;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) qf[qb][ks] = *(const V8*)(qp + 32 * ks);
+            if (q_row >= T) { qf[qb][0] = V8{}; qf[qb][1] = V8{}; }
         }
     }
     // staging: one copy per thread moves 32 tile rows; K with this kernel's swizzle, V^T with the common one

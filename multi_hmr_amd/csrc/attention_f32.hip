@@ -116,7 +116,12 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
     for (int ip = 0; ip < 4; ++ip)
 #pragma unroll
         for (int db = 0; db < 4; ++db) {
-            const float v = o[db][ip] * inv;
+            // v is ONE fp32 number, opaque to the optimiser.  Left to fold the product into the conversions, the f16 build measured lo against
+            // op16 of the UNROUNDED product (v_fma_mixlo_f16) but stored op16 of the rounded one (v_cvt_pk_f16_f32): where fl32(o * inv) fell
+            // exactly between two f16 values the two differed by an ulp, and hi + lo was off by 2^-11 relative -- one weight in ~10^4
+            // (tests/test_gpu_attention_keys.py; `#pragma clang fp contract(off)` does not stop that fold)
+            float v = o[db][ip] * inv;
+            asm volatile("" : "+v"(v));
             const int j = 4 * ip + db;
             const Tt hv = (Tt)v;
             hi[j >> 3][j & 7] = hv;
