@@ -297,7 +297,16 @@ int mhmr_layernorm16(const float* in, const float* w, const float* b, void* out1
 int mhmr_detect_scores(const void* hid16, int ld, const float* w2, const float* b2, float* scores, int rows, int C,
                        int dtype, void* stream);
 /* pass 1: counts[b] = number of cells with nms(score) >= thr.  pass 2 (after the host prefix sum `base`):
- * ordered compaction into det_b/det_y/det_x/det_score.                                                       */
+ * ordered compaction into det_b/det_y/det_x/det_score.
+ * The NMS window of cell (y, x) is (y - pad .. y - pad + k - 1) x (x - pad .. x - pad + k - 1), clipped to the image, pad = (k - 1) / 2
+ * for odd k.  For k = 2 and k = 4 the reference pads its max-pool by 1 and 2 and crops the larger output top-left, so the window is
+ * anchored up / left: k = 2 sees (y - 1 .. y) x (x - 1 .. x), k = 4 sees (y - 2 .. y + 1) x (x - 2 .. x + 1) -- a larger neighbour two
+ * cells above suppresses a cell at k = 4, one two cells below does not.  A cell that equals its window's maximum keeps its score (ties
+ * all survive); every other cell compares as score +0 against the threshold, so thr <= 0 returns EVERY cell, the suppressed ones with
+ * det_score 0 (heat * keep >= thr in the reference).  Even k > 4: the reference raises (pad = (k - 1) / 2 makes its max-pool output
+ * SMALLER than the map and the comparison with the map fails); these entry points do not refuse it and apply the same anchored window
+ * with pad = (k - 1) / 2 -- untested, and nothing to compare it with.  nms_kernel < 1 or B <= 0 (or cap < 0): MHMR_ERR_BAD_ARG,
+ * nothing is launched.                                                                                         */
 int mhmr_detect_count(const float* scores, int B, int G, int nms_kernel, float thr, int* counts, void* stream);
 int mhmr_detect_write(const float* scores, int B, int G, int nms_kernel, float thr, const int* base, int* det_b,
                       int* det_y, int* det_x, float* det_score, void* stream);

@@ -223,24 +223,13 @@ def test_person_groups_on_the_device_match_the_host_bookkeeping():
     pad_to_max, utils/tensor_manip.py:7-45): counts, write offsets, self-attention groups, <= 8-query work items -- from the detection
     counts and from a training-hook idx, with empty images, > 8 persons in one image, a capacity below the total, and launch bounds
     above the real table sizes (the padding entries must be empty groups / count-0 items)."""
-    import ctypes as C
+    from detect_cases import groups_oracle
     from multi_hmr_amd import _lib
     L = _lib.lib()
     st = torch.cuda.current_stream().cuda_stream
     for counts, cap in (([3, 0, 11, 1, 0, 8, 9], 64), ([3, 0, 11, 1, 0, 8, 9], 20), ([0, 0, 0], 8), ([17], 17), ([1] * 40, 64)):
         B, total = len(counts), sum(counts)
-        kept, left = [], cap
-        for c in counts:
-            kept.append(min(c, max(left, 0)))
-            left -= kept[-1]
-        gstart, chunks, start = [0], [], 0
-        for b, c in enumerate(kept):
-            if c == 0:
-                continue
-            for q0 in range(0, c, 8):
-                chunks += [b, start + q0, min(8, c - q0)]
-            start += c
-            gstart.append(start)
+        _, gstart, chunks, (start, _, _, _) = groups_oracle(counts, cap)       # the host bookkeeping, stated in tests/detect_cases.py
         ngc, ncc = min(B, cap) + 2, cap // 8 + min(B, cap) + 3          # bounds above the sufficient ones
         for from_counts in (True, False):
             if not from_counts and cap < total:
