@@ -490,6 +490,9 @@ typedef struct {
     float* g_ctx;                       /* [P, Kc] out, nullable: sum over the layers of dkv[det_row[p]] . to_kv */
     void* workspace;
     long long workspace_bytes;
+    /* appended (additive): the DENSE cotangent of the context's first feat_cols columns, for every row */
+    float* g_feat;                      /* [B N, ld_feat] out, nullable: sum over the layers of dkv . to_kv16[:, :feat_cols] */
+    int ld_feat, feat_cols;
 } mhmr_xattn_backward_desc;
 
 /* The forward overwrites x in place, so the backward first re-runs the forward's own launchers, out of place, into a tape
@@ -532,9 +535,52 @@ typedef struct {
     float *g_zc, *g_token;
     void* workspace;
     long long workspace_bytes;
+    /* appended (additive): the cotangent of feat32 itself, every row of every image */
+    float* g_feat;                      /* [B N, ld_feat >= C] out, nullable                                     */
+    int ld_feat;
 } mhmr_hph_backward_desc;
 long long mhmr_hph_backward_workspace_bytes(const mhmr_hph_desc* fwd, int B, int P);
 int mhmr_hph_backward(const mhmr_hph_backward_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The cotangent of the features: what the heads send back to feat32 [B N, C], straight-through past the
+ * 16-bit rounding of the context operand and of the detector's hidden layer; the rounded 16-bit weights are exact numbers.
+ *
+ *   g_feat[m][c] =  sum over the persons p whose cell is row m of g_zc[p][c] + g_token[p][c]
+ *                 + sum over the decoder layers l, in the order the backward visits them, of sum_n dkv_l[m][n] to_kv16_l[n][c]
+ *                 + sum_n (hid16[m][n] > 0 ? dl_m w2[n] : 0) cls0_w16[n][c]                       (the detector; dl as mhmr_detect_backward)
+ *
+ * The first two lines are mhmr_hph_backward_desc.g_feat (mhmr_xattn_backward_desc.g_feat is the second line alone, for its first
+ * feat_cols columns): the first layer visited WRITES every element of the B N rows, the later layers add, the persons' rows are added
+ * last; rows of images without queries hold exact zeros; P == 0 (or depth == 0) writes zeros.  NULL changes nothing.  With g_feat,
+ * C (feat_cols) % 128 == 0, C <= Kc and ld_feat >= C, MHMR_ERR_BAD_SHAPE otherwise.  The context row of a detected cell is
+ * op16(feat32 + cv_x + cv_y): its derivative with respect to feat32 is the identity, so the dense line covers those rows and g_ctx
+ * is not added again.  The third line is mhmr_detect_feature_grad.
+ *
+ * Both dense lines are one product, mhmr_rows_times_weight: out[m][c] (+)= sum_n left[m][n] w16[n][c] with left fp32 [rows, ldl >= n],
+ * w16 op16 [n, ldw >= C], out fp32 [rows, ldo >= C]; n % 16 == 0, C % 128 == 0.  Exact-fp32 MFMA (an fmaf chain per output element, of
+ * a shape the sizes alone fix); no sum crosses rows, so a row's bits do not depend on the other rows or on their number; no atomics;
+ * every element of the `rows` rows is written (pitch columns >= C are not touched); two calls give the same bits.  accumulate != 0:
+ * out = out + product (the bits of a write followed by an fp32 add).
+ * mhmr_detect_feature_grad forms the left operand of the detector's line in registers (the [rows, C] cotangent of the hidden layer is
+ * never stored) and writes g_feat [rows, ldg >= C]; rows outside the clamp (clamped != 0) and rows with a zero cotangent are exact
+ * zeros.  Its workspace is dl [rows] fp32 (mhmr_detect_feature_grad_workspace_bytes), left in place: dl_m as the product used it.
+ * mhmr_features_to_context: feat32 [rows, C] = features (skipped when features == feat32; any other overlap of the two is
+ * MHMR_ERR_BAD_ARG) and ctx16[m][c] = op16(features[m][c]) for c < C, round to nearest even -- what the final LayerNorm of
+ * mhmr_vit_forward leaves in those two buffers for the same fp32 values.  `features` is only read.
+ * MHMR_ERR_BAD_ARG: rows < 0, a NULL pointer that would be read or written, a short workspace; MHMR_ERR_BAD_SHAPE: the size rules
+ * above, a leading dimension smaller than its row, ldh odd, an unknown dtype, more than 2^24 - 1 workgroups of 64 rows x 128 columns
+ * (a launch limit), rows C >= 2^32 - 256 (mhmr_features_to_context), rows > 512 * 65535 (mhmr_detect_feature_grad).  rows == 0
+ * launches nothing and returns 0.  No allocation, no synchronisation; all validation happens before any launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int mhmr_rows_times_weight(const float* left, int ldl, const void* w16, int ldw, float* out, int ldo, int rows, int n, int C,
+                           int accumulate, int dtype, void* stream);
+long long mhmr_detect_feature_grad_workspace_bytes(int rows);
+int mhmr_detect_feature_grad(const void* hid16, int ldh, const void* cls0_w16, int ldw, const float* w2, const float* b2,
+                             const float* g_scores, int rows, int C, int clamped, int dtype, float* g_feat, int ldg,
+                             void* workspace, long long workspace_bytes, void* stream);
+int mhmr_features_to_context(const float* features, float* feat32, void* ctx16, int ldctx, int rows, int C, int dtype,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Backward of the detection head mlp_classif (csrc/detect_bwd.hip): the derivative of

@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -25,6 +25,12 @@ ATTN_QSCALE = 0.18033688011112042   # include/mhmr.h MHMR_ATTN_QSCALE
 VIT_FORM_BITS = ("rowmap", "allrows256", "nmask", "fold", "lo8_ranges", "cst", "ao", "splitk", "qkv_merge", "fc1map", "x3")
 
 _vp, _fp, _ip, _i, _f = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float  # all device pointers are void*
+_f32p = C.POINTER(C.c_float)        # a typed float*: the nullable outputs appended to a descriptor (set with f32p(tensor); NULL by default)
+
+
+def f32p(t):
+    """``float*`` of a torch tensor's data for a ``_f32p`` descriptor field (None -> NULL)."""
+    return C.cast(C.c_void_p(None if t is None else t.data_ptr()), _f32p)
 
 
 class MhmrError(RuntimeError):
@@ -141,7 +147,8 @@ class XattnBackwardDesc(C.Structure):
     """include/mhmr.h mhmr_xattn_backward_desc."""
     _fields_ = ([("layers", C.POINTER(HphLayer)), ("grads", C.POINTER(HphLayerGrads))] +
                 [(n, _i) for n in ("depth", "dim", "heads", "mlp", "Kc", "N", "B", "dtype", "P", "ngroups", "nmax", "nchunks", "ctx_valid")] +
-                [(n, _vp) for n in ("x0", "ctx16", "gstart", "chunks", "g_x_out", "g_x0", "det_row", "g_ctx", "workspace")] + [("workspace_bytes", C.c_longlong)])
+                [(n, _vp) for n in ("x0", "ctx16", "gstart", "chunks", "g_x_out", "g_x0", "det_row", "g_ctx", "workspace")] + [("workspace_bytes", C.c_longlong)] +
+                [("g_feat", _f32p), ("ld_feat", _i), ("feat_cols", _i)])
 
 
 class HphBackwardDesc(C.Structure):
@@ -150,7 +157,7 @@ class HphBackwardDesc(C.Structure):
     _fields_ = ([("fwd", C.POINTER(HphDesc))] + [(n, _vp) for n in ("ctx16", "det_y", "det_x", "gstart", "chunks")] +
                 [(n, _i) for n in ("ngroups", "nmax", "nchunks", "P", "B")] + [("g_readout", _vp), ("ldg", _i), ("g_offset", _vp)] +
                 [(n, _vp) for n in GRADS] + [("layer_grads", C.POINTER(HphLayerGrads)), ("g_zc", _vp), ("g_token", _vp), ("workspace", _vp),
-                                             ("workspace_bytes", C.c_longlong)])
+                                             ("workspace_bytes", C.c_longlong), ("g_feat", _f32p), ("ld_feat", _i)])
 
 
 class LbsConsts(C.Structure):
@@ -286,6 +293,10 @@ _SIGS = {
     "mhmr_hph_backward": ([C.POINTER(HphBackwardDesc), _vp], _i),
     "mhmr_detect_backward_workspace_bytes": ([_i, _i], C.c_longlong),
     "mhmr_detect_backward": ([_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _vp], _i),
+    "mhmr_rows_times_weight": ([_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "mhmr_detect_feature_grad_workspace_bytes": ([_i], C.c_longlong),
+    "mhmr_detect_feature_grad": ([_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, C.c_longlong, _vp], _i),
+    "mhmr_features_to_context": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mhmr_lbs_forward": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp], _i),
     "mhmr_preprocess_u8": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i] + [_i] * 7 + [_vp, _vp, _vp, _vp], _i),
     "mhmr_preprocess_u8_batch": ([C.POINTER(PreImage), _vp, _i, _i, _vp, _vp, _vp], _i),

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void detect_dl_kernel(const void* __restrict__
         const double t = exp(-fabs((double)s)), u = 1.0 + t;
         const double d = in ? (double)gs[row] * (t / (u * u)) : 0.0;
         dl[row] = (float)d;
-        dl64[row - row0] = d;
+        if (dl64) dl64[row - row0] = d;      // (no column sums follow the feature cotangent: it passes no scratch)
     }
 }
 
@@ -123,9 +123,39 @@ int launch(const void* hid16, int ldh, const void* ctx16, int ldx, const float* 
     return 0;
 }
 
+// The cotangent of the features: g_feat[m][c] = sum_n (hid16[m][n] > 0 ? dl_m w2[n] : 0) cls0_w16[n][c].  The row
+// pass above leaves dl [rows] fp32 in the workspace; the product is row_sums.h's rows times weight with the hidden layer's cotangent as
+// its left operand, formed in registers (one rounded fp32 product dl_m w2[n] per element, as if the array had been stored).
+template <int DT>
+int launch_feature_grad(const void* hid16, int ldh, const void* w16, int ldw, const float* w2, const float* b2, const float* gs, int rows, int C,
+                        int clamped, float* g_feat, int ldg, float* dl, hipStream_t s) {
+    hipLaunchKernelGGL((detect_dl_kernel<DT>), dim3((rows + 3) / 4), dim3(256), 0, s, hid16, ldh, w2, b2, gs, dl, (double*)nullptr, 0, rows, C, clamped);
+    MHMR_CHECK_LAUNCH();
+    return launch_rows_times_weight<DT>(LeftReluMaskW2<DT>{hid16, ldh, dl, w2}, w16, ldw, g_feat, ldg, rows, C, C, false, s);
+}
+
 }  // namespace
 
 extern "C" {
+
+long long mhmr_detect_feature_grad_workspace_bytes(int rows) {
+    if (rows < 0) return MHMR_ERR_BAD_ARG;
+    return align256(4LL * rows);
+}
+
+int mhmr_detect_feature_grad(const void* hid16, int ldh, const void* cls0_w16, int ldw, const float* w2, const float* b2, const float* g_scores,
+                             int rows, int C, int clamped, int dtype, float* g_feat, int ldg, void* workspace, long long workspace_bytes,
+                             void* stream) {
+    TRY(shape_rc(rows, C));
+    TRY(rows_times_weight_shape_rc(rows, C, C));
+    if (ldh < C || ldh % 2 || ldw < C || ldg < C || (dtype != MHMR_DT_F16 && dtype != MHMR_DT_BF16)) return MHMR_ERR_BAD_SHAPE;
+    if (rows == 0) return 0;
+    if (!hid16 || !cls0_w16 || !w2 || !b2 || !g_scores || !g_feat || !workspace || workspace_bytes < align256(4LL * rows)) return MHMR_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == MHMR_DT_F16)
+        return launch_feature_grad<MHMR_DT_F16>(hid16, ldh, cls0_w16, ldw, w2, b2, g_scores, rows, C, clamped, g_feat, ldg, (float*)workspace, s);
+    return launch_feature_grad<MHMR_DT_BF16>(hid16, ldh, cls0_w16, ldw, w2, b2, g_scores, rows, C, clamped, g_feat, ldg, (float*)workspace, s);
+}
 
 long long mhmr_detect_backward_workspace_bytes(int rows, int C) {
     const int rc = shape_rc(rows, C);

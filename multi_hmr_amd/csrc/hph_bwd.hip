@@ -16,6 +16,9 @@
 //                         so the to_kv reduction may run over all B N rows.
 //   to_kv gradient        dWkv[n][c] = sum_rows dkv[row][n] ctx16[row][c]: fp32 MFMA, the row range split into <= 16 slices whose
 //                         partial products are added in slice order (fp64) by a finishing pass; columns c >= cvalid are exact zeros.
+//   feature cotangent     (nullable g_feat) g_feat[m][c] = sum over the layers of dkv_l[m] . to_kv16_l[:, c] for every
+//                         context row (rows times weight of row_sums.h: the first layer visited writes, the others add), then
+//                         g_zc + g_token added at the persons' own rows.
 // The sliced outer product of the to_kv gradient, the two stages of the LayerNorm parameter sums and the workspace cursor are those of
 // row_sums.h, which detect_bwd.hip shares; this file holds the LayerNorm term, the launchers and the layouts.
 #include "mhmr_common.h"
@@ -512,6 +515,44 @@ int launch_op16_to_f32(const void* in, float* out, size_t n, int dtype, hipStrea
     return 0;
 }
 
+// dense cotangent of the context's first Cout columns (row_sums.h: rows times weight), layer by layer: the first call writes, the others add
+int launch_dense_ctx_grad(const float* dkv, int ldk, const void* to_kv16, int ldw, float* g_feat, int ldf, int rows, int Nn, int Cout,
+                          bool accumulate, int dtype, hipStream_t s) {
+    const LeftF32 left{dkv, ldk};
+    if (dtype == MHMR_DT_F16) return launch_rows_times_weight<MHMR_DT_F16>(left, to_kv16, ldw, g_feat, ldf, rows, Nn, Cout, accumulate, s);
+    return launch_rows_times_weight<MHMR_DT_BF16>(left, to_kv16, ldw, g_feat, ldf, rows, Nn, Cout, accumulate, s);
+}
+
+// g_feat[det_row[p]][c] += g_zc[p][c] + g_token[p][c]: the persons' own rows (distinct cells per image: one writer per element)
+__global__ __launch_bounds__(256) void person_rows_add_kernel(const float* __restrict__ g_zc, const float* __restrict__ g_token, int ldt,
+                                                              const int* __restrict__ det_row, float* g_feat, int ldf, int rows, int C) {
+    const int p = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+    const int row = det_row[p];
+    if (c >= C || row < 0 || row >= rows) return;
+    float* op = g_feat + (size_t)row * ldf + c;
+    *op = *op + (g_zc[(size_t)p * C + c] + g_token[(size_t)p * ldt + c]);
+}
+
+int launch_person_rows_add(const float* g_zc, const float* g_token, int ldt, const int* det_row, float* g_feat, int ldf, int rows, int C, int P,
+                           hipStream_t s) {
+    hipLaunchKernelGGL(person_rows_add_kernel, dim3(P, (C + 255) / 256), dim3(256), 0, s, g_zc, g_token, ldt, det_row, g_feat, ldf, rows, C);
+    MHMR_CHECK_LAUNCH();
+    return 0;
+}
+
+// the B N rows of g_feat as zeros (no person, or no layer: nothing else writes them)
+int zero_feature_grad(float* g_feat, int ldf, int rows, int C, hipStream_t s) {
+    if (rows <= 0) return 0;
+    return (int)hipMemset2DAsync(g_feat, (size_t)ldf * 4, 0, (size_t)C * 4, (size_t)rows, s);
+}
+
+// the rules of a dense feature cotangent [B N, ldf] of Cout columns beside a context of Kc columns
+int feature_grad_shape_rc(int B, int N, int heads, int Kc, int Cout, int ldf) {
+    if (Cout <= 0 || Cout > Kc || ldf < Cout) return MHMR_ERR_BAD_SHAPE;
+    if ((long long)B * N > 0x7fffffffLL) return MHMR_ERR_BAD_SHAPE;
+    return rows_times_weight_shape_rc(B * N, 64 * heads, Cout);
+}
+
 // ---------------------------------------------------------------- the stack's workspace: tape + scratch, every piece 256-byte aligned
 struct StackLayout {
     long long xs, qkv, o_sa, q, o_ca, z1, h1;        // tape, per layer (xs: 3 per layer)
@@ -657,7 +698,8 @@ int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream) 
     if ((d->nmax + 63) / 64 > 65535 || (d->P + 15) / 16 > 65535 || d->ctx_valid < 0 || d->ctx_valid > d->Kc) return MHMR_ERR_BAD_SHAPE;
     StackLayout L;
     if (!stack_layout(d->depth, d->dim, d->heads, d->mlp, d->Kc, d->N, d->B, d->P, &L)) return MHMR_ERR_BAD_SHAPE;
-    if (d->P == 0) return 0;
+    if (d->g_feat) TRY(feature_grad_shape_rc(d->B, d->N, d->heads, d->Kc, d->feat_cols, d->ld_feat));
+    if (d->P == 0) return d->g_feat ? zero_feature_grad(d->g_feat, d->ld_feat, d->B * d->N, d->feat_cols, (hipStream_t)stream) : 0;
     if (d->ngroups == 0 || d->nmax == 0 || d->nchunks == 0) return MHMR_ERR_BAD_ARG;      // persons without groups or without work items
     if (!d->layers || !d->grads || !d->x0 || !d->ctx16 || !d->gstart || !d->chunks || !d->g_x_out || !d->g_x0 || !d->workspace ||
         d->workspace_bytes < L.total || (d->g_ctx && !d->det_row))
@@ -696,6 +738,7 @@ int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream) 
     const float* g = d->g_x_out;
     float* gbuf[2] = {F(L.ga), F(L.gb)};
     int gi = 0;
+    if (d->depth == 0 && d->g_feat) TRY(zero_feature_grad(d->g_feat, d->ld_feat, rows, d->feat_cols, s));
     if (d->depth == 0) return (int)hipMemcpyAsync(d->g_x0, d->g_x_out, (size_t)P * dim * 4, hipMemcpyDeviceToDevice, s);
     for (int l = d->depth - 1; l >= 0; --l) {
         const mhmr_hph_layer& W = d->layers[l];
@@ -721,6 +764,9 @@ int mhmr_xattn_layers_backward(const mhmr_xattn_backward_desc* d, void* stream) 
         TRY(launch_cross_attn_bwd(q, kv, tin, d->chunks, d->nchunks, tbig, dkv, lse, heads, N, B, s));
         TRY(launch_grad_ctx_gemm(dkv, 2 * inner, d->ctx16, Kc, G.to_kv, rows, 2 * inner, Kc, d->ctx_valid > 0 ? d->ctx_valid : Kc, d->dtype,
                                  ctxws, s));
+        if (d->g_feat)       // the dense cotangent of the features, every row: g_feat (+)= dkv . to_kv16[:, :feat_cols], layers in this order
+            TRY(launch_dense_ctx_grad(dkv, 2 * inner, W.to_kv16, Kc, d->g_feat, d->ld_feat, rows, 2 * inner, d->feat_cols, l != d->depth - 1,
+                                      d->dtype, s));
         if (d->g_ctx) {      // context cotangent at the detected cells: g_ctx[p] (+)= dkv[det_row[p]] . Wkv, layers in this (descending) order
             TRY(launch_op16_to_f32(W.to_kv16, F(L.w32), (size_t)2 * inner * Kc, d->dtype, s));
             TRY(launch_linear_bwd_input(dkv, 2 * inner, d->det_row, nullptr, 0, F(L.w32), Kc, l == d->depth - 1 ? nullptr : d->g_ctx, Kc, d->g_ctx,
@@ -802,7 +848,8 @@ int mhmr_hph_backward(const mhmr_hph_backward_desc* d, void* stream) {
     if (d->ldg < f->Ndec || (d->nmax + 63) / 64 > 65535 || (d->P + 15) / 16 > 65535) return MHMR_ERR_BAD_SHAPE;
     const long long need = mhmr_hph_backward_workspace_bytes(f, d->B, d->P);
     if (need < 0) return (int)need;
-    if (d->P == 0) return 0;
+    if (d->g_feat) TRY(feature_grad_shape_rc(d->B, f->N, f->heads, f->Kc, f->C, d->ld_feat));
+    if (d->P == 0) return d->g_feat ? zero_feature_grad(d->g_feat, d->ld_feat, d->B * f->N, f->C, (hipStream_t)stream) : 0;
     if (d->ngroups == 0 || d->nmax == 0 || d->nchunks == 0) return MHMR_ERR_BAD_ARG;      // persons without groups or without work items
     const void* req[] = {f->off1_w, f->off1_b, f->off2_w, f->off2_b, f->tok_w, f->tok_b, f->layers, f->dec_w, f->zc, f->token, f->x, f->det_row,
                          d->ctx16, d->det_y, d->det_x, d->gstart, d->chunks, d->g_readout, d->g_offset, d->g_off1_w, d->g_off1_b, d->g_off2_w,
@@ -831,6 +878,7 @@ int mhmr_hph_backward(const mhmr_hph_backward_desc* d, void* stream) {
     sd.P = P; sd.ngroups = d->ngroups; sd.nmax = d->nmax; sd.nchunks = d->nchunks; sd.ctx_valid = Cc;
     sd.x0 = x0; sd.ctx16 = d->ctx16; sd.gstart = d->gstart; sd.chunks = d->chunks; sd.g_x_out = gx; sd.g_x0 = gx0;
     sd.det_row = f->det_row; sd.g_ctx = gctx;
+    sd.g_feat = d->g_feat; sd.ld_feat = d->ld_feat; sd.feat_cols = C;
     sd.workspace = ws + H.stack; sd.workspace_bytes = d->workspace_bytes - H.stack;
     TRY(mhmr_xattn_layers_backward(&sd, stream));
     if (f->depth == 0) TRY((int)hipMemsetAsync(gctx, 0, (size_t)P * Kc * 4, s));
@@ -846,6 +894,8 @@ int mhmr_hph_backward(const mhmr_hph_backward_desc* d, void* stream) {
     TRY(launch_linear_bwd_input(d->g_offset, 2, nullptr, nullptr, 0, f->off2_w, C, nullptr, 0, dh, C, P, 2, C, MHMR_ACT_NONE, s));
     TRY(launch_linear_bwd_weight(dh, C, z1, C, f->zc, C, d->g_off1_w, C, d->g_off1_b, P, C, C, MHMR_ACT_RELU, s));
     TRY(launch_linear_bwd_input(dh, C, nullptr, z1, C, f->off1_w, C, nullptr, 0, d->g_zc, C, P, C, C, MHMR_ACT_RELU, s));
+    // the persons' own rows of the feature cotangent, on top of the dense term the stack has written
+    if (d->g_feat) TRY(launch_person_rows_add(d->g_zc, d->g_token, Ktok, f->det_row, d->g_feat, d->ld_feat, d->B * f->N, C, P, s));
     return 0;
 }
 

@@ -4,7 +4,11 @@ and ``mlp_offset``; ``backward`` is ``mhmr_hph_backward``.
 
 The backward reads what the forward left in the model's per-batch workspace (the context operand with the detected cells' rows, the
 features) and in the packed head weights, so it must run BEFORE the next forward of the same batch size and before ``repack_heads()``:
-both move a generation counter, and a backward that finds it moved raises.  There is no CPU path."""
+both move a generation counter, and a backward that finds it moved raises.  There is no CPU path.
+
+``Model.forward_features`` passes the caller's feature tensor as one more input of the node: its gradient is the
+heads' share of the feature cotangent, ``mhmr_hph_backward_desc.g_feat`` -- the dense term of every context row plus ``g_zc`` and
+``g_token`` at the persons' rows."""
 from __future__ import annotations
 
 import ctypes as C
@@ -61,22 +65,23 @@ def layer_grad_shapes(inner: int, dim: int, mlp: int, Kc: int) -> dict:
 
 
 class _HeadsFunction(torch.autograd.Function):
-    """(head parameters) -> (readout, offset): the values are the ones the forward has already computed."""
+    """(features or None, head parameters) -> (readout, offset): the values are the ones the forward has already computed."""
 
     @staticmethod
-    def forward(ctx, model, st, *params):
+    def forward(ctx, model, st, features, *params):
         ctx.model, ctx.st = model, st
         ctx.shapes = [tuple(p.shape) for p in params]
+        ctx.feat_shape = None if features is None else tuple(features.shape)
         return st["readout"], st["offset"]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_readout, g_offset):
         model, st = ctx.model, ctx.st
-        need = ctx.needs_input_grad[2:]
+        need, need_feat = ctx.needs_input_grad[3:], ctx.needs_input_grad[2]
         dev, Pn, P = st["dev"], st["Pn"], st["P"]
-        if Pn == 0:      # no person: no contribution, the gradients are zeros
-            return (None, None) + tuple(torch.zeros(s, device=dev) if n else None for s, n in zip(ctx.shapes, need))
+        if Pn == 0:      # no person: no contribution, the gradients are zeros (None for the features: autograd's zero)
+            return (None, None, None) + tuple(torch.zeros(s, device=dev) if n else None for s, n in zip(ctx.shapes, need))
         if st["ws"].get("generation") != st["generation"] or P.get("heads_generation") != st["heads_generation"] or model._packed is not P:
             raise _lib.MhmrError("Model: backward must run before the next forward of the same batch size and before repack_heads() / "
                                  "repack(): the workspace (context operand, features) or the packed head weights this forward used have "
@@ -96,6 +101,7 @@ class _HeadsFunction(torch.autograd.Function):
                 setattr(lgrads[l], n, t.data_ptr())
             lbufs.append(row)
         g_zc, g_token = f(Pn, C_), f(Pn, Ktok)
+        g_feat = f(st["B"] * P["N"], C_) if need_feat else None
         fwd = st["desc"]
         nbytes = int(L.mhmr_hph_backward_workspace_bytes(C.byref(fwd), st["B"], Pn))
         if nbytes < 0:
@@ -112,21 +118,23 @@ class _HeadsFunction(torch.autograd.Function):
             setattr(d, n, t.data_ptr())
         d.layer_grads = C.cast(lgrads, C.POINTER(_lib.HphLayerGrads))
         d.g_zc, d.g_token, d.workspace, d.workspace_bytes = g_zc.data_ptr(), g_token.data_ptr(), wsb.data_ptr(), nbytes
+        d.g_feat, d.ld_feat = _lib.f32p(g_feat), C_
         with model._lock, torch.cuda.device(dev):
             _lib.check(L.mhmr_hph_backward(C.byref(d), stream), "mhmr_hph_backward")
         # the cotangents of the gathered features (rows of the persons), for a backbone backward
         model.heads_feature_grads = {"g_zc": g_zc, "g_token": g_token[:, :Cc]}
         named = packed_to_parameter_grads(g, lbufs, Cc, nb, dim)
-        return (None, None) + tuple(named[n] if k else None for n, k in zip(st["names"], need))
+        return (None, None, g_feat.view(ctx.feat_shape) if need_feat else None) + tuple(named[n] if k else None for n, k in zip(st["names"], need))
 
 
-def attach(model, st):
-    """-> (readout, offset) attached to autograd with respect to the head parameters that require grad (detached values otherwise)."""
+def attach(model, st, features=None, with_params=True):
+    """-> (readout, offset) attached to autograd with respect to the head parameters that require grad (``with_params``: train_heads) and
+    to ``features`` (the tensor ``Model.forward_features`` was given, when it requires grad); detached values otherwise."""
     names = head_parameter_names(st["P"]["hph"]["depth"])
     params = dict(model.named_parameters())
     st["names"] = names
     with torch.enable_grad():
-        return _HeadsFunction.apply(model, st, *[params[n] for n in names])
+        return _HeadsFunction.apply(model, st, features, *[params[n] if with_params else params[n].detach() for n in names])
 
 
 __all__ = ["head_parameter_names", "packed_to_parameter_grads", "layer_grad_shapes", "attach"]

@@ -579,15 +579,85 @@ class Model(nn.Module):
             self._bm32 = BodyModel(self._smplx_data, "smplx", num_betas=self.num_betas)
         return self._bm32
 
+    def _prepare_features(self, features):
+        """The checks of ``_prepare`` for a feature tensor [B, N, C] or [B N, C] -> (P, ws, stream, B, fp32 contiguous features).  A tensor
+        of another float dtype is widened (and must not require grad: its gradient would be that of the rounded copy)."""
+        if self.camera_embedding is None:
+            raise AttributeError("'Model' object has no attribute 'camera' (camera_embedding=None: the reference's forward fails the same "
+                                 "way at model.py:262 -> :183)")
+        if not isinstance(features, torch.Tensor) or not features.is_cuda:
+            raise _lib.MhmrError("multi_hmr_amd.Model.forward_features runs only on an MI355X (HIP) tensor; there is no CPU fallback")
+        N, Cd = (self.img_size // PATCH) ** 2, self.embed_dim
+        ok = features.is_floating_point() and ((features.dim() == 3 and tuple(features.shape[1:]) == (N, Cd)) or
+                                               (features.dim() == 2 and features.shape[1] == Cd and features.shape[0] > 0 and
+                                                features.shape[0] % N == 0))
+        if not ok:
+            raise ValueError(f"features must be a float tensor [B,{N},{Cd}] or [B*{N},{Cd}]")
+        if features.dtype != torch.float32 and features.requires_grad:
+            raise ValueError("features that require grad must be float32 (a 16-bit store is widened first and gets no gradient)")
+        B = features.shape[0] if features.dim() == 3 else features.shape[0] // N
+        if B < 1:
+            raise ValueError(f"features must be a float tensor [B,{N},{Cd}] or [B*{N},{Cd}]")
+        P = self._packed
+        if P is None or P["device"] != features.device:
+            P = self._pack(features.device)
+        ws = self._workspace(P, B)
+        return P, ws, torch.cuda.current_stream(features.device).cuda_stream, B, features.detach().float().contiguous()
+
+    @torch.no_grad()
+    def forward_features(self, features, idx=None, det_thresh=0.3, nms_kernel_size=3, K=None, is_training=False, *args, **kwargs):
+        """``forward`` from stored features: the same contract, keywords (``return_image_index``, ``return_batched``, ``return_readout``,
+        ``train_heads``, ``train_detection``) and return values, with ``features`` -- ``[B, N, C]`` or ``[B N, C]`` on the GPU, what
+        ``backbone_features(x)`` returns for the images -- in the place of the backbone.  For the fp32 features of ``x`` the results equal
+        ``forward(x, ...)`` bit for bit.  The tensor is only read (a clone of ``backbone_features(x)``, or that workspace view itself);
+        another float dtype is widened to fp32 first, so features rounded to the packed 16-bit type are a legitimate half-size store.
+
+        In training mode, when ``features.requires_grad`` (fp32 only, ``ValueError`` otherwise), ``out["scores"]`` and -- with
+        ``return_readout=True`` -- ``out["readout"]`` and ``out["offset"]`` are attached to autograd with respect to ``features``, whether or
+        not ``train_heads`` / ``train_detection`` are set; ``backward()`` then fills ``features.grad`` (straight-through
+        past the 16-bit roundings; once differentiable; ``K`` gets nothing).  Parameter gradients follow the rules of ``forward``.  The
+        backward reads this call's workspace: it must run before the next ``forward`` / ``forward_features`` of the same batch size."""
+        if kwargs.get("train_detection", False) and not is_training:
+            raise ValueError("train_detection=True needs is_training=True")
+        if kwargs.get("train_heads", False) and not (is_training and kwargs.get("return_readout", False)):
+            raise ValueError("train_heads=True needs is_training=True and return_readout=True")
+        with self._lock, torch.autocast("cuda", enabled=False):
+            P, ws, stream, B, f32 = self._prepare_features(features)
+            dev = features.device
+            K = K.to(device=dev, dtype=torch.float32).contiguous()
+            assert K.shape == (B, 3, 3)
+            self._features_in(P, ws, f32, B, stream)
+            self._front_heads(P, ws, B, K, stream)
+            leaf = features if (is_training and features.requires_grad) else None
+            return self._behind_front(P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training,
+                                      bool(kwargs.get("return_image_index", False)), bool(kwargs.get("return_batched", False)),
+                                      bool(kwargs.get("return_readout", False)), bool(kwargs.get("train_heads", False)),
+                                      bool(kwargs.get("train_detection", False)), leaf)
+
+    def _features_in(self, P, ws, f32, B, stream):
+        """Step 1 of the forward with the features given: ws["feat32"] = features (no copy when they ARE that buffer) and the context
+        operand's feature columns = their 16-bit rounding, as the backbone's final norm leaves both."""
+        ws["generation"] = ws.get("generation", 0) + 1      # as _run_backbone: a pending backward's features and context are overwritten
+        _lib.check(_lib.lib().mhmr_features_to_context(f32.data_ptr(), ws["feat32"].data_ptr(), ws["ctx16"].data_ptr(), P["Kc"], B * P["N"],
+                                                       P["C"], P["dt_id"], stream), "mhmr_features_to_context")
+
     def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, with_ids=False, batched=False, with_readout=False,
                  train_heads=False, train_detection=False):
-        L = _lib.lib()
         P, ws, stream = self._prepare(x)
-        dev, B, G = x.device, x.shape[0], P["G"]
+        dev, B = x.device, x.shape[0]
         K = K.to(device=dev, dtype=torch.float32).contiguous()
         assert K.shape == (B, 3, 3)
 
         self._front(P, ws, x, K, stream)
+        return self._behind_front(P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, with_ids, batched, with_readout,
+                                  train_heads, train_detection, None)
+
+    def _behind_front(self, P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, with_ids, batched, with_readout,
+                      train_heads, train_detection, features):
+        """Everything behind steps 1-3 (shared by ``forward`` and ``forward_features``).  ``features``: the caller's feature tensor when the
+        outputs are to be attached to autograd with respect to it (training mode, ``requires_grad``), else None."""
+        L = _lib.lib()
+        G = P["G"]
         scores = ws["scores"].view(B, G, G, 1)
 
         if is_training:
@@ -596,17 +666,20 @@ class Model(nn.Module):
             idx = tuple(i.to(dev) for i in idx)
             Pn = int(idx[0].shape[0])
             out = {"scores": scores.clone()}
-            if train_detection:
+            attach_heads = train_heads or (features is not None and with_readout)
+            if train_detection or features is not None:
                 from . import detect_train
                 out["scores"] = detect_train.attach(self, dict(P=P, ws=ws, dev=dev, rows=B * P["N"], generation=ws["generation"],
-                                                               heads_generation=P["heads_generation"], scores=out["scores"]))
+                                                               heads_generation=P["heads_generation"], scores=out["scores"]),
+                                                    features=features, with_params=train_detection)
             if Pn == 0:
                 if with_readout:
                     out["readout"] = torch.empty(0, 318 + P["hph"]["nb"] + 13, dtype=torch.float32, device=dev)
-                if train_heads:
+                if attach_heads:
                     from . import heads_train
                     out["readout"], _ = heads_train.attach(self, dict(P=P, dev=dev, Pn=0, readout=out["readout"],
-                                                                      offset=torch.empty(0, 2, dtype=torch.float32, device=dev)))
+                                                                      offset=torch.empty(0, 2, dtype=torch.float32, device=dev)),
+                                                           features=features, with_params=train_heads)
                 return out
             det = torch.stack([idx[0], idx[1], idx[2]]).to(torch.int32).contiguous()
             gstart_t, chunks_t, info, ngc, ncc = self._tables(B, Pn, dev)
@@ -617,12 +690,12 @@ class Model(nn.Module):
             out.update({n: t for n, t in heads.items() if n not in ("scores", "_flat")})      # (scores here = the [B, G, G, 1] map, model.py:349)
             if with_readout:
                 out["readout"] = keep["dec"][:, :318 + P["hph"]["nb"] + 13].contiguous()
-            if train_heads:
+            if attach_heads:
                 from . import heads_train
                 st = dict(P=P, ws=ws, dev=dev, Pn=Pn, B=B, generation=ws["generation"], heads_generation=P["heads_generation"],
                           desc=keep["desc"], wsp=keep["wsp"], det=det, gstart=gstart_t, chunks=chunks_t, ngc=ngc, ncc=ncc,
                           readout=out["readout"], offset=out["offset"].clone())
-                out["readout"], out["offset"] = heads_train.attach(self, st)
+                out["readout"], out["offset"] = heads_train.attach(self, st, features=features, with_params=train_heads)
             return out
 
         # NMS + threshold + ordered compaction (model.py:141-149)
@@ -659,11 +732,16 @@ class Model(nn.Module):
     # ---- the pieces of the inference forward (shared with graphed.GraphedForward, which records them into a hipGraph once)
     def _front(self, P, ws, x, K, stream):
         """Steps 1-3 of the forward: backbone, camera embedding, detection scores -> ws["feat32"], ws["ctx16"], ws["zK"], ws["scores"]."""
-        L = _lib.lib()
-        B, G, N, Cdim, Kc, dt = x.shape[0], P["G"], P["N"], P["C"], P["Kc"], P["dt_id"]
-        Mp = ws["ctx16"].shape[0]
         # 1. backbone (model.py:229) -> feat32 + 16-bit context operand
         self._run_backbone(P, ws, x)
+        self._front_heads(P, ws, x.shape[0], K, stream)
+
+    def _front_heads(self, P, ws, B, K, stream):
+        """Steps 2 and 3 of the forward, from ws["feat32"] / ws["ctx16"][:, :C] however they were filled (the backbone, or
+        ``forward_features``) -> ws["zK"], the camera columns of ws["ctx16"], ws["hid_cls"], ws["scores"]."""
+        L = _lib.lib()
+        G, N, Cdim, Kc, dt = P["G"], P["N"], P["C"], P["Kc"], P["dt_id"]
+        Mp = ws["ctx16"].shape[0]
         # 2. camera embedding (model.py:262) -> zK + context operand columns C..C+98
         _lib.check(L.mhmr_camera_embed(K.data_ptr(), P["freq"].data_ptr(), B, G, PATCH, ws["zK"].data_ptr(), ws["ctx16"].data_ptr(), Kc,
                                        Cdim, dt, P["nbands"], stream), "mhmr_camera_embed")
