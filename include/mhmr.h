@@ -1035,6 +1035,64 @@ int mhmr_loss_forward(const mhmr_loss_desc* d, void* ws, long long ws_bytes, voi
 int mhmr_loss_backward(const mhmr_loss_desc* d, const void* out, const float* grad_total, const mhmr_loss_grads* g, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Fused Adam step over a table of segments that also rewrites the packed copy of every element it updates
+ * (csrc/optim.hip).  One segment = one fp32 parameter tensor (contiguous, n elements) with
+ * its two moments, its gradient, and the place of its packed copy: element i of the parameter is element
+ * (i / cols) * pitch + i % cols of `packed` (cols == pitch: a plain copy; pitch > cols: a padded pitch whose
+ * padding is never written; `packed` may point into the middle of a larger buffer: a row offset).
+ *   packed_kind  MHMR_ADAM_PACK_NONE: nothing is written;  _F32: packed = p;  _F16 / _BF16: packed = the 16-bit
+ *                round-to-nearest-even cast of p;
+ *   addend       non-NULL (fp32, n elements, read only): packed = p + addend[i]      (dec_b = bias + init_*)
+ *   param2 ...   non-NULL (all four of param2, exp_avg2, exp_avg_sq2, grad2): a second parameter of n elements
+ *                updated by the same thread from its own gradient and moments; packed = p + p2
+ *                (tok_b = bias + pos_embedding[0, 0]).  Not together with addend.
+ *   grad         NULL: the segment is skipped -- parameter, moments and packed copy keep their bits.
+ *   step_size, bc2_sqrt (and *2 for param2): lr / (1 - beta1^t) and sqrt(1 - beta2^t) of THIS tensor's step
+ *                count t >= 1 after the increment, computed by the caller in double and rounded once.
+ *   chunk0       first chunk of the segment: chunk0 of segment 0 is 0, of segment s + 1 it is chunk0[s] +
+ *                ceil(n[s] / MHMR_ADAM_CHUNK).  One workgroup per chunk; skipped segments keep their chunks.
+ * Per element, in fp32, in the order of torch's single-tensor Adam (fma: one rounding; every other operation rounded on its own):
+ *   g' = g * coef (coef = 1 without clipping);  m = fma(w1, g' - m, m);  v = v * beta2;  v = fma(w2 * g', g', v);
+ *   p = p + (-step_size * m) / (sqrt(v) / bc2_sqrt + eps),     w1 = (float)(1 - beta1), w2 = (float)(1 - beta2), the
+ * differences taken in double.  No weight decay, no amsgrad, no maximize.
+ * Clipping (max_norm > 0): a first launch writes one fp64 partial sum of g^2 per chunk (0 for skipped segments;
+ * g and g2 both count), a second adds the partials in chunk order and leaves norm = (float)sqrt(sum) in
+ * norm_out[0]; coef = min(1, max_norm / (norm + 1e-6)).  `partials` holds at least the total chunk count.  No
+ * atomics: two calls give the same bits.  max_norm <= 0: one launch, partials / norm_out are not touched.
+ * `segs_host` and `segs_dev` are the SAME nsegs entries in host and in device memory: the host copy is validated
+ * before the first launch, the kernels read the device copy (which the caller has enqueued on `stream` before
+ * the call).  MHMR_ERR_BAD_ARG: nsegs < 0, a NULL table, a NULL param, NULL moments beside a gradient, an incomplete
+ * second parameter, addend together with a second parameter, a packed_kind outside the four values or without a
+ * `packed` pointer, a wrong chunk0, packed ranges of two segments that overlap, betas outside [0, 1), eps < 0, a
+ * step_size or bc2_sqrt that is not finite and positive, clipping without partials / norm_out or with
+ * partials_count below the chunk count.  MHMR_ERR_BAD_SHAPE: n < 1, cols < 1, pitch < cols, n % cols != 0, more
+ * than 2^31 - 1 chunks.  nsegs == 0 launches nothing.  16-byte loads and stores where every pointer of the segment
+ * and the pitch allow them, element by element otherwise: the same bits.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define MHMR_ADAM_CHUNK 2048
+#define MHMR_ADAM_PACK_NONE 0
+#define MHMR_ADAM_PACK_F32 1
+#define MHMR_ADAM_PACK_F16 2
+#define MHMR_ADAM_PACK_BF16 3
+typedef struct {
+    float* param;
+    float* exp_avg;
+    float* exp_avg_sq;
+    const float* grad;
+    float* param2;
+    float* exp_avg2;
+    float* exp_avg_sq2;
+    const float* grad2;
+    void* packed;
+    const float* addend;
+    long long n;
+    int cols, pitch, packed_kind, chunk0;
+    float step_size, bc2_sqrt, step_size2, bc2_sqrt2;
+} mhmr_adam_segment;
+int mhmr_adam_step(const mhmr_adam_segment* segs_host, const mhmr_adam_segment* segs_dev, int nsegs, double beta1, double beta2, double eps,
+                   double max_norm, double* partials, long long partials_count, float* norm_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement: hipEvent brackets around every launch of one kernel family (0 = GEMM, 1 = attention, 2 = LBS
  * vertex kernel), recorded on the launch stream.  enable(kind >= 0) starts a fresh window, enable(-1) stops;
  * collect() synchronises the recorded events and returns launches, summed milliseconds and summed work

@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -45,7 +45,9 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: per-translation-unit extra flags.  render.hip: every step rounded on its own (the render contract's fp64 geometry and fp32 blend
 #: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  scene.hip: the same fp64 geometry.
 #: loss.hip: every element of the training loss is the reference's fp32 subtraction(s), rounded one by one (its sign is the gradient).
-EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"]}
+#: optim.hip: the Adam update is torch's sequence of fp32 operations, each rounded on its own.
+EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
+               "optim.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -241,6 +243,17 @@ class LossGrads(C.Structure):
 LOSS_OUT_BYTES = 128                # include/mhmr.h MHMR_LOSS_OUT_BYTES
 
 
+class AdamSegment(C.Structure):
+    """include/mhmr.h mhmr_adam_segment."""
+    _fields_ = ([(n, _vp) for n in ("param", "exp_avg", "exp_avg_sq", "grad", "param2", "exp_avg2", "exp_avg_sq2", "grad2", "packed", "addend")] +
+                [("n", C.c_longlong)] + [(n, _i) for n in ("cols", "pitch", "packed_kind", "chunk0")] +
+                [(n, _f) for n in ("step_size", "bc2_sqrt", "step_size2", "bc2_sqrt2")])
+
+
+ADAM_CHUNK = 2048                   # include/mhmr.h MHMR_ADAM_CHUNK
+ADAM_PACK_NONE, ADAM_PACK_F32, ADAM_PACK_F16, ADAM_PACK_BF16 = range(4)
+
+
 _SIGS = {
     "mhmr_version": ([], _i),
     "mhmr_source_hash": ([], C.c_char_p),
@@ -323,6 +336,7 @@ _SIGS = {
     "mhmr_loss_workspace_bytes": ([], C.c_longlong),
     "mhmr_loss_forward": ([C.POINTER(LossDesc), _vp, C.c_longlong, _vp, _vp], _i),
     "mhmr_loss_backward": ([C.POINTER(LossDesc), _vp, _fp, C.POINTER(LossGrads), _vp], _i),
+    "mhmr_adam_step": ([C.POINTER(AdamSegment), _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_longlong, _vp, _vp], _i),
     "mhmr_prof_enable": ([_i], _i),
     "mhmr_prof_collect": ([C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)], _i),
 }

@@ -1,0 +1,220 @@
+"""``Trainer``: the loop around the training step -- epochs, meters, the log line, checkpoints, evaluation -- with the surface of the
+reference's ``train.py`` ``Trainer``, for what this package trains.
+
+Two differences from the reference, both on purpose:
+
+* it trains the heads (``x_attention_head``, ``mlp_offset``) and the detector (``mlp_classif``) on a FROZEN backbone -- the backbone has
+  no backward here -- so the optimiser holds ``model.heads_parameters()`` (+ ``model.detection_parameters()``), not ``model.parameters()``;
+* the master weights are fp32 and there is no autocast / AMP: the 16-bit operands of the forward are the model's packed copies, which the
+  optimiser step rewrites (``HeadsAdam``) or ``repack_heads()`` refreshes (any other ``torch.optim`` optimiser).
+
+The step has one legal order -- forward, ``decode_readout``, loss, ``backward()``, optimiser step, re-pack -- because ``backward()`` reads
+the forward's workspace and the packed weights; ``train_step`` / ``train_step_features`` are that order.  Dataset readers and a command
+line are not part of this module: ``data`` is any iterable of ``(x, y)`` as the reference's ``collate_fn`` yields them."""
+from __future__ import annotations
+
+import os
+import sys
+import time
+
+import torch
+
+from . import _lib
+from .evaluate import Evaluator, evaluate_dataset
+from .optim import HeadsAdam
+
+
+class AverageMeter:
+    """Running mean of a scalar (``val``: the last value, ``avg``: the mean so far)."""
+
+    def __init__(self, name):
+        self.name, self.val, self.sum, self.count, self.avg = name, 0.0, 0.0, 0, 0.0
+
+    def update(self, val, n=1):
+        self.val = float(val)
+        self.sum += float(val) * n
+        self.count += n
+        self.avg = self.sum / max(self.count, 1)
+
+
+class _NoWriter:
+    """The default ``writer``: scalars go nowhere (pass a tensorboard ``SummaryWriter`` -- or anything with ``add_scalar`` and ``flush`` --
+    to keep them)."""
+
+    def add_scalar(self, *a, **k):
+        pass
+
+    def flush(self):
+        pass
+
+
+def _arg(args, name, default):
+    v = getattr(args, name, None)
+    return default if v is None else v
+
+
+class Trainer:
+    """``Trainer(model, loss, optimizer, args, gt_builder, evaluator=None, writer=None)``.
+
+    ``model``: a ``Model`` on the GPU with ``train_heads_(True)`` and / or ``train_detection_(True)``; ``loss``: a ``Loss``; ``optimizer``: a
+    ``HeadsAdam`` (the step rewrites the packed weights) or any ``torch.optim`` optimiser over the same parameters (``repack_heads()`` then
+    runs after every step); ``gt_builder``: a ``GroundTruth``; ``evaluator``: an ``Evaluator`` whose regressors the evaluation uses.
+    ``args`` (a namespace) is read for ``save_dir`` ("logs"), ``name`` ("trainval"), ``max_epochs`` (1), ``log_freq`` (100), ``nb_max_ckpt``
+    (10), ``det_thresh`` (0.3) and ``nms_kernel_size`` (3); ``log_dir``, ``ckpt_dir`` and ``visu_dir`` are written back into it as the reference
+    does.  ``writer``: an object with ``add_scalar(tag, value, step)`` and ``flush()``; none by default (tensorboard is not a dependency)."""
+
+    def __init__(self, model, loss, optimizer, args, gt_builder, evaluator=None, writer=None, best_val=1e5):
+        self.model, self.loss, self.optimizer, self.args, self.gt_builder = model, loss, optimizer, args, gt_builder
+        self.evaluator, self.best_val = evaluator, best_val
+        self.current_epoch = self.current_iter = 0
+        self.device = next(iter(model.parameters())).device
+        args.log_dir = os.path.join(_arg(args, "save_dir", "logs"), _arg(args, "name", "trainval"))
+        args.ckpt_dir, args.visu_dir = os.path.join(args.log_dir, "checkpoints"), os.path.join(args.log_dir, "visu")
+        for d in (args.log_dir, args.ckpt_dir, args.visu_dir):
+            os.makedirs(d, exist_ok=True)
+        self.writer = writer if writer is not None else _NoWriter()
+
+    # ------------------------------------------------------------------------------------------------ one step
+    def prepare_gt(self, y):
+        """Annotations of a batch -> the training targets (``GroundTruth.prepare``; None for a batch without humans)."""
+        return self.gt_builder.prepare(y)
+
+    def _step(self, forward, x, y):
+        model, opt = self.model, self.optimizer
+        if "idx" not in y:                                    # (already prepared targets are taken as they are)
+            y = self.prepare_gt({k: (v.to(self.device) if isinstance(v, torch.Tensor) else v) for k, v in y.items()})
+        gt = y
+        if gt is None:
+            return None
+        heads = any(p.requires_grad for p in model.heads_parameters())
+        detection = any(p.requires_grad for p in model.detection_parameters())
+        if not (heads or detection):
+            raise _lib.MhmrError("Trainer: nothing to train -- call model.train_heads_(True) and / or model.train_detection_(True) first")
+        out = forward(x, idx=gt["idx"], K=gt["K"], is_training=True, return_readout=True, train_heads=heads, train_detection=detection)
+        pred = model.decode_readout(out["readout"], out["offset"], gt["idx"], gt["K"])
+        total, dict_loss = self.loss(dict(pred, scores=out["scores"]), gt, epoch=self.current_epoch, img_size=model.img_size)
+        total.backward()                                      # before the optimiser step: it reads the packed weights the step rewrites
+        opt.step()
+        if not isinstance(opt, HeadsAdam):
+            model.repack_heads()
+        opt.zero_grad(set_to_none=True)
+        return dict_loss
+
+    def train_step(self, x, y):
+        """Forward from the images ``x [B, 3, S, S]``, decode, loss, backward, optimiser step (and re-pack) -> ``dict_loss`` (detached 0-d
+        device tensors; None for a batch without humans, which is skipped)."""
+        return self._step(self.model, x.to(self.device), y)
+
+    def train_step_features(self, features, y):
+        """``train_step`` from stored backbone features (``Model.forward_features``)."""
+        return self._step(self.model.forward_features, features.to(self.device), y)
+
+    @torch.no_grad()
+    def cache_features(self, batches, dtype=torch.float32):
+        """The backbone once per batch: ``[(features [B, N, C] of ``dtype``, y)]`` for ``train_step_features`` / ``train_n_iters``.  fp16 halves
+        the store (the features are widened again and the results are those of the rounded features)."""
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError("cache_features: dtype is torch.float32 or torch.float16")
+        return [(self.model.backbone_features(x.to(self.device)).clone().to(dtype), y) for x, y in batches]
+
+    # ------------------------------------------------------------------------------------------------ the loop
+    def train_n_iters(self, data):
+        """One pass over ``data``: ``(x, y)`` with images ``x [B, 3, S, S]`` or stored features ``x [B, N, C]``."""
+        print("\nTRAIN: ")
+        self.model.train()
+        meters = {k: AverageMeter(k) for k in ("workload/data", "workload/batch", "workload/ratio_data")}
+        n_total = len(data) if hasattr(data, "__len__") else 0
+        log_freq = max(int(_arg(self.args, "log_freq", 100)), 1)
+        t_end = time.time()
+        for i, (x, y) in enumerate(data):
+            y = {k: (v.to(self.device) if isinstance(v, torch.Tensor) else v) for k, v in y.items()}
+            t_data = time.time() - t_end
+            dict_loss = self.train_step(x, y) if x.dim() == 4 else self.train_step_features(x, y)
+            if dict_loss is None:
+                t_end = time.time()
+                continue
+            keys = list(dict_loss)
+            vals = torch.stack([dict_loss[k].detach().float() for k in keys]).tolist()      # the one host read of the step
+            t_batch = time.time() - t_end
+            meters["workload/data"].update(t_data)
+            meters["workload/batch"].update(t_batch)
+            meters["workload/ratio_data"].update(t_data / t_batch)
+            for k, v in zip(keys, vals):
+                meters.setdefault(f"loss/{k}", AverageMeter(f"loss/{k}")).update(v)
+            if i % log_freq == 0:
+                avg = lambda k: meters[k].avg if k in meters else float("nan")
+                print(f"EPOCH={self.current_epoch:03d} - i={i:05d}/{n_total:05d} - workload/ratio_data={avg('workload/ratio_data'):.2f} - "
+                      f"loss={avg('loss/total'):.2f} - bce={avg('loss/bce'):.2f} - v3d={avg('loss/v3d'):.2f} - transl={avg('loss/transl'):.2f}")
+                for k, m in meters.items():
+                    self.writer.add_scalar(k, m.avg, self.current_iter)
+                self.writer.flush()
+                sys.stdout.flush()
+            self.current_iter += 1
+            t_end = time.time()
+        return 1
+
+    def save_checkpoint(self):
+        """``ckpt_dir/{epoch:05d}.pt`` = ``{epoch, iter, model_state_dict, args, optimizer_state_dict}``; the body-model layers
+        (``smpl_layer_*``) are left out of the state dict as in the reference, and only the newest ``nb_max_ckpt`` files stay."""
+        sd = {k: v for k, v in self.model.state_dict().items() if "smpl_layer_" not in k}
+        path = os.path.join(self.args.ckpt_dir, f"{self.current_epoch:05d}.pt")
+        torch.save({"epoch": self.current_epoch, "iter": self.current_iter, "model_state_dict": sd, "args": self.args,
+                    "optimizer_state_dict": self.optimizer.state_dict()}, path)
+        epochs = sorted(int(f[:-3]) for f in os.listdir(self.args.ckpt_dir) if f.endswith(".pt") and f[:-3].isdigit())
+        keep = epochs[-max(int(_arg(self.args, "nb_max_ckpt", 10)), 1):]
+        for e in epochs:
+            if e not in keep:
+                try:
+                    os.remove(os.path.join(self.args.ckpt_dir, f"{e:05d}.pt"))
+                except OSError:
+                    print(f"could not remove checkpoint {e:05d}.pt")
+        return path
+
+    def resume(self, path):
+        """Restore a checkpoint written by ``save_checkpoint``: the model's weights (the packed copies are dropped and rebuilt by the next
+        forward), the optimiser state, the iteration count; training continues with the epoch AFTER the saved one."""
+        ckpt = torch.load(path, map_location=self.device, weights_only=False)
+        self.model.load_state_dict(ckpt["model_state_dict"], strict=False)
+        if ckpt.get("optimizer_state_dict") is not None:
+            self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        self.current_epoch, self.current_iter = int(ckpt["epoch"]) + 1, int(ckpt["iter"])
+        return ckpt
+
+    def fit(self, data_train, l_data_val=()):
+        """Epochs ``current_epoch .. args.max_epochs - 1``: train, checkpoint, evaluate every set of ``l_data_val``."""
+        for _ in range(self.current_epoch, int(_arg(self.args, "max_epochs", 1))):
+            t0 = time.time()
+            self.train_n_iters(data_train)
+            t_train = time.time() - t0
+            self.save_checkpoint()
+            t0 = time.time()
+            for data_val in l_data_val:
+                self.evaluate(data_val)
+            t_eval = time.time() - t0
+            self.writer.add_scalar("workload/train_n_iters", t_train, self.current_epoch)
+            self.writer.add_scalar("workload/evaluate", t_eval, self.current_epoch)
+            self.writer.add_scalar("workload/ratio_trainVal", t_eval / max(t_train + t_eval, 1e-12), self.current_epoch)
+            self.current_epoch += 1
+        return 1
+
+    @torch.no_grad()
+    def evaluate(self, data):
+        """``evaluate_dataset`` over ``data`` with the args' ``det_thresh`` / ``nms_kernel_size``; the metrics go to the writer under the data
+        set's ``name`` (``data.dataset.name`` or ``data.name``, "val" otherwise); returns the PVE in mm."""
+        print("\nEVAL: ")
+        self.model.eval()
+        ev = Evaluator(self.evaluator.smplx2smpl, self.evaluator.h36m_regressor) if self.evaluator is not None else Evaluator()
+        summary = evaluate_dataset(self.model, data, self.gt_builder, det_thresh=_arg(self.args, "det_thresh", 0.3),
+                                   nms_kernel_size=_arg(self.args, "nms_kernel_size", 3), evaluator=ev)
+        name = getattr(getattr(data, "dataset", data), "name", "val")
+        print(f"***EVAL METRICS - {name}***")
+        for k, v in summary.items():
+            self.writer.add_scalar(f"{name}/{k}", v, self.current_iter)
+            print(f"    - {k}: {v:.1f}")
+        self.writer.flush()
+        sys.stdout.flush()
+        self.last_eval = summary
+        return summary["pve"]
+
+
+__all__ = ["AverageMeter", "Trainer"]
