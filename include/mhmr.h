@@ -21,7 +21,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
+#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_pre_image_o, mhmr_preprocess_u8_batch_oriented; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
 #define MHMR_OK 0
 #define MHMR_ERR_BAD_ARG (-1)
@@ -701,6 +701,31 @@ typedef struct {
 } mhmr_pre_image;
 int mhmr_preprocess_u8_batch(const mhmr_pre_image* host, const mhmr_pre_image* dev, int B, int S, const float* lut,
                              float* out, void* stream);
+
+/* mhmr_preprocess_u8_batch for sources that are read through a rotation and / or a mirror, as the training loaders orient
+ * them (datasets/bedlam.py:222-229: img.rotate(-90, expand=True) for the "closeup" sequences, then ImageOps.mirror for
+ * the random flip, then contain + pad): no oriented copy of the source is made, the horizontal pass addresses the stored
+ * buffer through the permutation.  orient: bit 0 (MHMR_ORIENT_MIRROR) = mirror, applied AFTER the rotation; bit 1
+ * (MHMR_ORIENT_ROT90) = rotate by 90 degrees clockwise (PIL's Transpose.ROTATE_270).  With (oW, oH) = (H, W) if rotated,
+ * (W, H) otherwise, the ORIENTED image is
+ *     or[y][x] = rotated ? img[H - 1 - x'][y] : img[y][x'],    x' = mirrored ? oW - 1 - x : x,    0 <= x < oW, 0 <= y < oH.
+ * H and W describe the STORED buffer img [H][W][3]; everything else -- the tables kh / bh / kv / bv, ow, oh, y0, rows,
+ * pad_x, pad_y and tmp [rows][ow][3] -- describes the oriented image, exactly as mhmr_preprocess_u8 would be given them
+ * for an oW x oH source (y0 + rows <= oH).  Per output pixel the arithmetic is mhmr_preprocess_u8's; with orient = 0 the
+ * output equals mhmr_preprocess_u8_batch's bit for bit.  Two launches, one descriptor per image, host / dev as above; no
+ * allocation, no synchronisation, no atomics.  A bit of orient other than 0 and 1 -> MHMR_ERR_BAD_ARG; the other conditions
+ * and codes are those of mhmr_preprocess_u8_batch; every descriptor is checked before the first launch. */
+#define MHMR_ORIENT_MIRROR 1
+#define MHMR_ORIENT_ROT90 2
+typedef struct {
+    const void* img;                                   /* uint8 [H][W][3] as stored, device */
+    int H, W, ow, oh, y0, rows, pad_x, pad_y, ksh, ksv;
+    const int *kh, *bh, *kv, *bv;                      /* device; tables of the oriented image */
+    void* tmp;                                         /* uint8 [rows][ow][3], device */
+    int orient;                                        /* MHMR_ORIENT_* bits */
+} mhmr_pre_image_o;
+int mhmr_preprocess_u8_batch_oriented(const mhmr_pre_image_o* host, const mhmr_pre_image_o* dev, int B, int S,
+                                      const float* lut, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Accuracy metrics of the reference's evaluation loop, train.py:372-395 (PVE, PA-PVE) and

@@ -227,6 +227,15 @@ class PreImage(C.Structure):
                 [(n, _vp) for n in ("kh", "bh", "kv", "bv", "tmp")])
 
 
+class PreImageO(C.Structure):
+    """include/mhmr.h mhmr_pre_image_o: one image of mhmr_preprocess_u8_batch_oriented (PreImage's fields; H, W = the stored buffer, the
+    rest = the oriented image; ``orient`` = ORIENT_* bits)."""
+    _fields_ = PreImage._fields_ + [("orient", _i)]
+
+
+ORIENT_MIRROR, ORIENT_ROT90 = 1, 2  # include/mhmr.h MHMR_ORIENT_*
+
+
 class LossDesc(C.Structure):
     """include/mhmr.h mhmr_loss_desc."""
     TENSORS = ("scores", "offset", "rotmat", "shape", "dist", "transl", "pelvis", "j3d", "v3d", "j2d", "v2d")
@@ -313,6 +322,7 @@ _SIGS = {
     "mhmr_lbs_forward": ([C.POINTER(LbsConsts)] + [_vp] * 7 + [_i] + [_vp] * 8 + [_vp], _i),
     "mhmr_preprocess_u8": ([_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i] + [_i] * 7 + [_vp, _vp, _vp, _vp], _i),
     "mhmr_preprocess_u8_batch": ([C.POINTER(PreImage), _vp, _i, _i, _vp, _vp, _vp], _i),
+    "mhmr_preprocess_u8_batch_oriented": ([C.POINTER(PreImageO), _vp, _i, _i, _vp, _vp, _vp], _i),
     "mhmr_eval_mesh_errors": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),
     "mhmr_body_forward": ([C.POINTER(BodyConsts), _vp, _vp, _vp, _vp, _i] + [_vp] * 6 + [_vp], _i),
     "mhmr_body_backward_workspace_bytes": ([C.POINTER(BodyConsts), _i], C.c_longlong),

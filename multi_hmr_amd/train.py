@@ -9,8 +9,9 @@ Two differences from the reference, both on purpose:
   optimiser step rewrites (``HeadsAdam``) or ``repack_heads()`` refreshes (any other ``torch.optim`` optimiser).
 
 The step has one legal order -- forward, ``decode_readout``, loss, ``backward()``, optimiser step, re-pack -- because ``backward()`` reads
-the forward's workspace and the packed weights; ``train_step`` / ``train_step_features`` are that order.  Dataset readers and a command
-line are not part of this module: ``data`` is any iterable of ``(x, y)`` as the reference's ``collate_fn`` yields them."""
+the forward's workspace and the packed weights; ``train_step`` / ``train_step_features`` are that order.  ``data`` is any iterable of
+``(x, y)`` as the reference's ``collate_fn`` yields them: a ``data.TrainLoader`` (section 27), or a list.  ``main`` is the command line:
+``python -m multi_hmr_amd.train --pretrained NAME --train_data BEDLAM ...``."""
 from __future__ import annotations
 
 import os
@@ -217,4 +218,87 @@ class Trainer:
         return summary["pve"]
 
 
-__all__ = ["AverageMeter", "Trainer"]
+def build_parser():
+    """The reference's ``train.py`` arguments where they apply to what this package trains, with its names and defaults; ``--n_iter``
+    (``--n_iters_per_epoch``, ``-iter``) training batches make an epoch and ``--max_epochs`` epochs are run (``--max_iter``, if given, sets
+    ``max_epochs = max_iter // n_iter`` as the reference does).  The loss weights are ``Loss.add_specific_args``."""
+    from argparse import ArgumentParser
+    from .loss import Loss
+    p = ArgumentParser(description="Train the heads and the detector of a Multi-HMR checkpoint on a frozen backbone")
+    p.add_argument("--train_data", type=str, default="BEDLAM", choices=["BEDLAM"])
+    p.add_argument("--train_split", type=str, default="training")
+    p.add_argument("--train_n", type=int, default=-1)
+    p.add_argument("--train_subsample", type=int, default=1)
+    p.add_argument("--val_data", type=str, nargs="*", default=["BEDLAM"], choices=["BEDLAM", "EHF", "THREEDPW"])
+    p.add_argument("--val_split", type=str, nargs="*", default=["validation"])
+    p.add_argument("--val_n", type=int, nargs="*", default=None)
+    p.add_argument("--val_subsample", type=int, nargs="*", default=None)
+    p.add_argument("--save_dir", type=str, default="logs")
+    p.add_argument("--name", type=str, default="trainval")
+    p.add_argument("--pretrained", type=str, required=True, help="checkpoint name under models/multiHMR (demo.load_model): the backbone is not trained here")
+    p.add_argument("--batch_size", type=int, default=2)
+    p.add_argument("--num_workers", "-j", type=int, default=8)
+    p.add_argument("--img_size", type=int, default=None, help="default: the checkpoint's")
+    p.add_argument("--n_iter", "--n_iters_per_epoch", "-iter", type=int, default=100)
+    p.add_argument("--max_epochs", type=int, default=1)
+    p.add_argument("--max_iter", type=int, default=None)
+    p.add_argument("--log_freq", type=int, default=100)
+    p.add_argument("--nb_max_ckpt", type=int, default=10)
+    p.add_argument("--learning_rate", "-lr", type=float, default=5e-6)
+    p.add_argument("--train_detection", type=int, default=1, choices=[0, 1])
+    p.add_argument("--extension", type=str, default="png", choices=["png", "jpg"])
+    p.add_argument("--res", type=int, default=None)
+    p.add_argument("--flip", type=int, default=1, choices=[0, 1])
+    p.add_argument("--det_thresh", type=float, default=0.2)
+    p.add_argument("--nms_kernel_size", type=int, default=3)
+    p.add_argument("--seed", type=int, default=None, help="seeds the draws of the training set (images and flips)")
+    p.add_argument("--data_dir", type=str, default="data", help="annotation pickles, and BEDLAM/ EHF/ 3DPW/ below it")
+    p.add_argument("--smplx_dir", type=str, default="models", help="smplx/SMPLX_NEUTRAL.npz, smpl/SMPL_MALE.pkl, smpl/SMPL_FEMALE.pkl")
+    return Loss.add_specific_args(p)
+
+
+def main(argv=None):
+    """``python -m multi_hmr_amd.train --pretrained NAME ...``: ``load_model`` -> ``train_heads_`` / ``train_detection_`` -> ``HeadsAdam`` ->
+    ``Trainer.fit`` over a ``TrainLoader`` of the training set, with one loader per validation set."""
+    from . import data
+    from .bodymodel import BodyModel
+    from .demo import load_model
+    from .groundtruth import GroundTruth
+    from .loss import Loss
+    args = build_parser().parse_args(argv)
+    if args.max_iter is not None:
+        args.max_epochs = args.max_iter // max(args.n_iter, 1)
+    device = torch.device("cuda")
+    model = load_model(args.pretrained, device=device, **({} if args.img_size is None else {"img_size": args.img_size}))
+    args.img_size = S = int(model.img_size)
+    model = model.eval().train_heads_(True).train_detection_(bool(args.train_detection))
+    optimizer = HeadsAdam(model, lr=args.learning_rate, detection=bool(args.train_detection))
+    body = lambda *parts: os.path.join(args.smplx_dir, *parts)
+    smpl = {g: (BodyModel(body("smpl", f"SMPL_{g.upper()}.pkl"), "smpl", num_betas=10) if os.path.isfile(body("smpl", f"SMPL_{g.upper()}.pkl")) else None)
+            for g in ("male", "female")}
+    gt = GroundTruth(S, patch_size=14, nearness=getattr(model, "nearness", True), person_center=getattr(model, "person_center", "head"),
+                     smplx_neutral=BodyModel(body("smplx", "SMPLX_NEUTRAL.npz"), "smplx", num_betas=11), smpl_male=smpl["male"],
+                     smpl_female=smpl["female"])
+    roots = {"BEDLAM": "BEDLAM", "EHF": "EHF", "THREEDPW": "3DPW"}
+    make = lambda name, **kw: getattr(data, name)(img_size=S, root_dir=os.path.join(args.data_dir, roots[name]), annotations_dir=args.data_dir, **kw)
+    train_set = make(args.train_data, split=args.train_split, training=True, n_iter=args.batch_size * args.n_iter, subsample=args.train_subsample,
+                     n=args.train_n, extension=args.extension, res=args.res, flip=args.flip, seed=args.seed)
+    print(train_set)
+    train = data.TrainLoader(train_set, args.batch_size, device, workers=args.num_workers)
+    vals = []
+    for i, (name, split) in enumerate(zip(args.val_data, args.val_split)):
+        kw = dict(split=split, training=False, subsample=args.val_subsample[i] if args.val_subsample else 1)
+        if name == "BEDLAM":
+            kw.update(n=args.val_n[i] if args.val_n else -1, extension=args.extension, res=args.res)
+        vals.append(data.TrainLoader(make(name, **kw), 1, device, workers=args.num_workers))      # the reference evaluates image by image
+        print(vals[-1].dataset)
+    trainer = Trainer(model, Loss(args), optimizer, args, gt)
+    trainer.fit(train, vals)
+    return trainer
+
+
+__all__ = ["AverageMeter", "Trainer", "build_parser", "main"]
+
+
+if __name__ == "__main__":
+    main()
