@@ -154,6 +154,13 @@ typedef struct {
      * launches of qkv / fc1 turn into (mean, rstd) themselves -- the forward then issues no statistics launch of its own (47 fewer
      * launches per ViT-L forward).  NULL = mhmr_ln_stats-style launches as before. */
     float* cls_pstats;
+    /* The tap, or NULL: before block l >= tap_first the fp32 residual stream is copied into slot l - tap_first of
+     * `tap`, [L - tap_first][B*Tp, C] fp32 -- the block inputs mhmr_vit_tail_backward differentiates at.  One hipMemcpyAsync per slot on
+     * the caller's stream (capturable).  NULL issues exactly the launches of a forward without it; with or without a tap feat32, ctx16 and
+     * mhmr_vit_form_bits are the same bit for bit, and `resid` holds the stream the final norm read.  0 <= tap_first <= L
+     * (MHMR_ERR_BAD_ARG otherwise). */
+    float* tap;
+    int tap_first;
 } mhmr_vit_desc;
 
 /* x: [B,3,S,S] fp32 (ImageNet-normalised).  feat32: [B*N, C] fp32 patch features (token n = y*G + x).
@@ -1116,6 +1123,102 @@ typedef struct {
 } mhmr_adam_segment;
 int mhmr_adam_step(const mhmr_adam_segment* segs_host, const mhmr_adam_segment* segs_dev, int nsegs, double beta1, double beta2, double eps,
                    double max_norm, double* partials, long long partials_count, float* norm_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Backward of one ViT block: the derivative of the fp32 function
+ *     x -> x + ls1 * proj(MHSA(norm1(x))),  then  x -> x + ls2 * fc2(gelu(fc1(norm2(x))))
+ * (attention scale head_dim^-0.5, erf GELU, LayerNorm eps 1e-6) with the fp32 master weights in torch layout,
+ * evaluated at the block input x_in that the inference forward produced.  The backward recomputes the block's
+ * activations from x_in in fp32 (the tape) and reads none of the forward's 16-bit workspaces: the 16-bit roundings of
+ * the forward are straight-through.  Sums across rows are fp64 or fp32 MFMA chains whose shape the sizes alone fix,
+ * there are no floating-point atomics, every element of every output is written, two calls give the same bits; no
+ * entry allocates or synchronises, and all validation happens before the first launch.
+ *
+ *   mhmr_attention_f32_tape:      qkv [B*Tp, 3C] fp32 = (Q | K | V), un-scaled, head h at columns h*64 (the input of
+ *       mhmr_attention_f32) -> out32 [B*Tp, C] fp32 and lse [B, H, Tp] = max + log2(sum) of a query's logits in the
+ *       exp2 domain (logit = q.k * MHMR_ATTN_QSCALE).  Keys at rows >= T are masked; rows >= T of out32 and lse are zeros.
+ *   mhmr_attention_f32_backward:  qkv, out32, lse as above, dO [B*Tp, lddo] (head h at columns h*64) -> dqkv [B*Tp, 3C]
+ *       with respect to the un-scaled Q, K and V.  Every product on v_mfma_f32_16x16x4_f32.  Two passes, no sum crosses a
+ *       workgroup: a query-tile pass over the keys (per query r = 1 / sum exp2(s - lse) and D = sum P dP with
+ *       P = exp2(s - lse) r, then dQ) and a key-tile pass over the queries (dK, dV).  D is summed from the P and dP that
+ *       form dS = P (dP - D) -- closer to fp64 than dO . O where dP - D cancels -- so out32 must be given but is not read.
+ *       Keys and queries at rows >= T are masked: whatever finite numbers qkv, dO and out32 hold there moves no bit of a
+ *       real row, and rows >= T of dqkv are exact zeros.  workspace: D | r, [B, H, Tp] each.
+ *   mhmr_vit_block_backward:      recomputes the tape, then the backward.  Only the T real rows of an image contribute
+ *       to the parameter gradients (rows >= T of g_out are not read as cotangents); rows >= T of g_in are zeros.
+ * Shapes: B, T >= 1, Tp % 64 == 0, Tp >= T, C == 64 H (C <= 2048 for the block), lddo >= C and lddo % 4 == 0, H and B at
+ * most 65535, B * Tp at most 16 * 65535 for the block, MHMR_ERR_BAD_SHAPE otherwise (negative counts: MHMR_ERR_BAD_ARG).  A NULL pointer,
+ * a pointer of the attention entries that is not 16-byte aligned, or a short workspace: MHMR_ERR_BAD_ARG.
+ * ---------------------------------------------------------------------------------------------------------- */
+int mhmr_attention_f32_tape(const float* qkv, float* out32, float* lse, int B, int T, int Tp, int C, int H, void* stream);
+long long mhmr_attention_f32_backward_workspace_bytes(int B, int Tp, int H);
+int mhmr_attention_f32_backward(const float* qkv, const float* out32, const float* lse, const float* dO, int lddo, float* dqkv,
+                                int B, int T, int Tp, int C, int H, void* workspace, long long workspace_bytes, void* stream);
+
+typedef struct {
+    int B, T, Tp, C, H;
+    /* the fp32 master tensors of blocks.i, torch layout: qkv_w [3C, C], proj_w [C, C], fc1_w [4C, C], fc2_w [C, 4C] */
+    const float* ln1_w;
+    const float* ln1_b;
+    const float* qkv_w;
+    const float* qkv_b;
+    const float* proj_w;
+    const float* proj_b;
+    const float* ls1;
+    const float* ln2_w;
+    const float* ln2_b;
+    const float* fc1_w;
+    const float* fc1_b;
+    const float* fc2_w;
+    const float* fc2_b;
+    const float* ls2;
+    const float* x_in;  /* [B*Tp, C] the residual stream entering the block               */
+    const float* g_out; /* [B*Tp, C] cotangent of the block's output                       */
+    float* g_in;        /* [B*Tp, C] cotangent of x_in (may not alias g_out)               */
+    /* one gradient buffer per master tensor, of its shape */
+    float* g_ln1_w;
+    float* g_ln1_b;
+    float* g_qkv_w;
+    float* g_qkv_b;
+    float* g_proj_w;
+    float* g_proj_b;
+    float* g_ls1;
+    float* g_ln2_w;
+    float* g_ln2_b;
+    float* g_fc1_w;
+    float* g_fc1_b;
+    float* g_fc2_w;
+    float* g_fc2_b;
+    float* g_ls2;
+    void* workspace;
+    long long workspace_bytes; /* >= mhmr_vit_block_backward_workspace_bytes(B, Tp, C) */
+} mhmr_vit_block_backward_desc;
+long long mhmr_vit_block_backward_workspace_bytes(int B, int Tp, int C);
+int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream);
+
+/* The backbone tail: the backward of the final LayerNorm -- patch rows only: g_feat [B*N, C] is the cotangent of feat32, the class
+ * row and the padding rows of the stream cotangent are zeros -- then mhmr_vit_block_backward for the last n blocks, last block first,
+ * each at its tapped input.  The gradient stops at the input of block L - n (g_stream); there is no patch- or position-embedding
+ * gradient.  blocks: HOST array of n descriptors in block order (L - n first) of which the fourteen master tensors and the fourteen
+ * gradient buffers are read; their shapes, x_in, g_out, g_in and workspace fields are ignored.  tap: [n][B*Tp, C], slot i = the stream
+ * entering block L - n + i (mhmr_vit_desc.tap with tap_first = L - n); resid: the stream the final norm read.
+ * n >= 1, N == T - 1, and the shape rules of the block (MHMR_ERR_BAD_SHAPE); NULL pointers, a short workspace: MHMR_ERR_BAD_ARG. */
+typedef struct {
+    int B, N, T, Tp, C, H, n;
+    const float* norm_w;
+    const float* norm_b;
+    const mhmr_vit_block_backward_desc* blocks;
+    const float* tap;
+    const float* resid;
+    const float* g_feat;
+    float* g_norm_w;
+    float* g_norm_b;
+    float* g_stream; /* [B*Tp, C] cotangent of the stream entering block L - n; rows >= T are zeros */
+    void* workspace;
+    long long workspace_bytes; /* >= mhmr_vit_tail_backward_workspace_bytes(B, Tp, C) */
+} mhmr_vit_tail_backward_desc;
+long long mhmr_vit_tail_backward_workspace_bytes(int B, int Tp, int C);
+int mhmr_vit_tail_backward(const mhmr_vit_tail_backward_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Measurement: hipEvent brackets around every launch of one kernel family (0 = GEMM, 1 = attention, 2 = LBS

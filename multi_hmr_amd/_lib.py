@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -121,7 +121,8 @@ class VitDesc(C.Structure):
                 [("patch_w", _vp), ("patch_b", _vp), ("cls_pos0", _vp), ("pos", _vp), ("blocks", C.POINTER(VitBlock)),
                  ("norm_w", _vp), ("norm_b", _vp)] +
                 [(n, _vp) for n in ("a_patch", "resid", "xn", "qk", "vt", "att", "hid", "attn_flags", "pstats", "rowstats")] +
-                [("lo8", _i), ("x3", _i), ("qkv32", _vp), ("hid32", _vp), ("splitk", _vp), ("splitk_bytes", C.c_longlong), ("cpad", _i), ("v16", _vp), ("cls_pstats", _vp)])
+                [("lo8", _i), ("x3", _i), ("qkv32", _vp), ("hid32", _vp), ("splitk", _vp), ("splitk_bytes", C.c_longlong), ("cpad", _i), ("v16", _vp), ("cls_pstats", _vp),
+                 ("tap", _vp), ("tap_first", _i)])
 
 
 class HphLayer(C.Structure):
@@ -259,6 +260,21 @@ class AdamSegment(C.Structure):
                 [(n, _f) for n in ("step_size", "bc2_sqrt", "step_size2", "bc2_sqrt2")])
 
 
+class VitBlockBackwardDesc(C.Structure):
+    """include/mhmr.h mhmr_vit_block_backward_desc: the fp32 master tensors of one block (torch layout), the block input, the cotangent
+    of its output, and one gradient buffer per tensor."""
+    PARAMS = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")
+    _fields_ = ([(n, _i) for n in ("B", "T", "Tp", "C", "H")] + [(n, _vp) for n in PARAMS] + [(n, _vp) for n in ("x_in", "g_out", "g_in")] +
+                [("g_" + n, _vp) for n in PARAMS] + [("workspace", _vp), ("workspace_bytes", C.c_longlong)])
+
+
+class VitTailBackwardDesc(C.Structure):
+    """include/mhmr.h mhmr_vit_tail_backward_desc: final norm + the last n blocks, at the tapped streams."""
+    _fields_ = ([(n, _i) for n in ("B", "N", "T", "Tp", "C", "H", "n")] + [("norm_w", _vp), ("norm_b", _vp),
+                ("blocks", C.POINTER(VitBlockBackwardDesc))] + [(n, _vp) for n in ("tap", "resid", "g_feat", "g_norm_w", "g_norm_b", "g_stream",
+                                                                                   "workspace")] + [("workspace_bytes", C.c_longlong)])
+
+
 ADAM_CHUNK = 2048                   # include/mhmr.h MHMR_ADAM_CHUNK
 ADAM_PACK_NONE, ADAM_PACK_F32, ADAM_PACK_F16, ADAM_PACK_BF16 = range(4)
 
@@ -347,6 +363,13 @@ _SIGS = {
     "mhmr_loss_forward": ([C.POINTER(LossDesc), _vp, C.c_longlong, _vp, _vp], _i),
     "mhmr_loss_backward": ([C.POINTER(LossDesc), _vp, _fp, C.POINTER(LossGrads), _vp], _i),
     "mhmr_adam_step": ([C.POINTER(AdamSegment), _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_longlong, _vp, _vp], _i),
+    "mhmr_attention_f32_tape": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "mhmr_attention_f32_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_attention_f32_backward": ([_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
+    "mhmr_vit_block_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_vit_block_backward": ([C.POINTER(VitBlockBackwardDesc), _vp], _i),
+    "mhmr_vit_tail_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_vit_tail_backward": ([C.POINTER(VitTailBackwardDesc), _vp], _i),
     "mhmr_prof_enable": ([_i], _i),
     "mhmr_prof_collect": ([C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)], _i),
 }

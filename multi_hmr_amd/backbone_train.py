@@ -1,0 +1,194 @@
+"""Training the last backbone blocks: the backward of a ViT block and of the self-attention over all tokens of an
+image, in fp32 at the fp32 master weights, evaluated at the residual stream the inference forward produced.
+
+The functions here run the kernels of csrc/vit_bwd.hip on device tensors and allocate their outputs and workspaces.  There is no CPU
+path.  Token rows follow the forward's layout: ``Tp`` rows per image, patch rows first, the class token at row ``N = T - 1``, padding
+behind it."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+#: descriptor field (``_lib.VitBlockBackwardDesc.PARAMS``) -> parameter name inside ``backbone.encoder.blocks.<l>``
+BLOCK_FIELDS = dict(ln1_w="norm1.weight", ln1_b="norm1.bias", qkv_w="attn.qkv.weight", qkv_b="attn.qkv.bias", proj_w="attn.proj.weight",
+                    proj_b="attn.proj.bias", ls1="ls1.gamma", ln2_w="norm2.weight", ln2_b="norm2.bias", fc1_w="mlp.fc1.weight",
+                    fc1_b="mlp.fc1.bias", fc2_w="mlp.fc2.weight", fc2_b="mlp.fc2.bias", ls2="ls2.gamma")
+ENCODER = "backbone.encoder."
+
+
+def backbone_parameter_names(depth: int, n: int = 1) -> list:
+    """``named_parameters`` keys of the final norm and of the last ``n`` blocks of a ``depth``-block encoder, in the order
+    ``Model.backbone_parameters`` returns: norm.weight, norm.bias, then blocks ``depth - n .. depth - 1`` field by field."""
+    if not 1 <= n <= depth:
+        raise ValueError(f"n must be in [1, {depth}]")
+    names = [ENCODER + "norm.weight", ENCODER + "norm.bias"]
+    for l in range(depth - n, depth):
+        names += [f"{ENCODER}blocks.{l}.{BLOCK_FIELDS[f]}" for f in _lib.VitBlockBackwardDesc.PARAMS]
+    return names
+
+
+def _bytes(rc, what):
+    rc = int(rc)
+    if rc < 0:
+        _lib.check(rc, what)
+    return rc
+
+
+def _f32(t):
+    if not t.is_cuda:
+        raise _lib.MhmrError("multi_hmr_amd.backbone_train runs only on an MI355X (HIP) tensor; there is no CPU fallback")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def attention_tape(qkv, B, T, Tp, H, stream=None):
+    """``mhmr_attention_f32_tape``: qkv [B*Tp, 3C] fp32 -> (out32 [B*Tp, C], lse [B, H, Tp])."""
+    qkv = _f32(qkv)
+    dev, Cd = qkv.device, qkv.shape[1] // 3
+    out32 = torch.empty(B * Tp, Cd, dtype=torch.float32, device=dev)
+    lse = torch.empty(B, H, Tp, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().mhmr_attention_f32_tape(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), B, T, Tp, Cd, H, stream),
+               "mhmr_attention_f32_tape")
+    return out32, lse
+
+
+def attention_backward(qkv, out32, lse, dO, B, T, Tp, H, stream=None, dqkv=None):
+    """``mhmr_attention_f32_backward``: -> dqkv [B*Tp, 3C] with respect to the un-scaled Q, K and V."""
+    L = _lib.lib()
+    qkv, out32, lse = _f32(qkv), _f32(out32), _f32(lse)
+    dev, Cd = qkv.device, qkv.shape[1] // 3
+    if dO.dtype != torch.float32 or dO.stride(-1) != 1:
+        dO = _f32(dO)
+    if dqkv is None:
+        dqkv = torch.empty(B * Tp, 3 * Cd, dtype=torch.float32, device=dev)
+    nbytes = _bytes(L.mhmr_attention_f32_backward_workspace_bytes(B, Tp, H), "mhmr_attention_f32_backward_workspace_bytes")
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(L.mhmr_attention_f32_backward(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), dO.data_ptr(), dO.stride(0), dqkv.data_ptr(), B,
+                                             T, Tp, Cd, H, wsb.data_ptr(), nbytes, stream), "mhmr_attention_f32_backward")
+    return dqkv
+
+
+def block_tensors(block, device=None) -> dict:
+    """{descriptor field: fp32 contiguous tensor} of a block module with DINOv2's parameter names (the nn.Parameters themselves when they
+    already are fp32, contiguous and on the device)."""
+    named = dict(block.named_parameters())
+    out = {}
+    for f, n in BLOCK_FIELDS.items():
+        t = named[n].detach()
+        out[f] = t.to(device=device if device is not None else t.device, dtype=torch.float32).contiguous()
+    return out
+
+
+def fill_block_desc(d, params: dict, grads: dict, B, T, Tp, Cd, H):
+    """Set the shape, the fourteen master tensors and the fourteen gradient buffers of a ``_lib.VitBlockBackwardDesc``."""
+    d.B, d.T, d.Tp, d.C, d.H = B, T, Tp, Cd, H
+    for f in _lib.VitBlockBackwardDesc.PARAMS:
+        setattr(d, f, params[f].data_ptr())
+        setattr(d, "g_" + f, grads[f].data_ptr())
+    return d
+
+
+def block_backward(params: dict, x_in, g_out, B, T, Tp, H, stream=None):
+    """``mhmr_vit_block_backward`` on device tensors: ``params`` = {descriptor field: fp32 tensor} (``block_tensors``), x_in and g_out
+    [B*Tp, C] -> (g_in [B*Tp, C], {field: gradient of the parameter's shape})."""
+    L = _lib.lib()
+    x_in, g_out = _f32(x_in), _f32(g_out)
+    dev, Cd = x_in.device, x_in.shape[1]
+    grads = {f: torch.empty_like(params[f]) for f in _lib.VitBlockBackwardDesc.PARAMS}
+    g_in = torch.empty_like(x_in)
+    nbytes = _bytes(L.mhmr_vit_block_backward_workspace_bytes(B, Tp, Cd), "mhmr_vit_block_backward_workspace_bytes")
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    d = fill_block_desc(_lib.VitBlockBackwardDesc(), params, grads, B, T, Tp, Cd, H)
+    d.x_in, d.g_out, d.g_in, d.workspace, d.workspace_bytes = x_in.data_ptr(), g_out.data_ptr(), g_in.data_ptr(), wsb.data_ptr(), nbytes
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(L.mhmr_vit_block_backward(C.byref(d), stream), "mhmr_vit_block_backward")
+    return g_in, grads
+
+
+def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H, stream=None):
+    """``mhmr_vit_tail_backward`` on device tensors: final norm + the blocks of ``blocks`` ([{descriptor field: fp32 tensor}], first block
+    first) at the tapped streams ``tap [n, B*Tp, C]``; ``resid [B*Tp, C]`` the stream the final norm read; ``g_feat [B*N, C]``
+    -> (g_stream [B*Tp, C], g_norm_w, g_norm_b, [{field: gradient}] per block)."""
+    L = _lib.lib()
+    n, dev, Cd = len(blocks), resid.device, resid.shape[-1]
+    g_feat = _f32(g_feat).reshape(B * N, Cd)
+    assert tap.dtype == resid.dtype == torch.float32 and tap.is_contiguous() and resid.is_contiguous() and tap.numel() == n * B * Tp * Cd
+    grads = [{f: torch.empty_like(b[f]) for f in _lib.VitBlockBackwardDesc.PARAMS} for b in blocks]
+    descs = (_lib.VitBlockBackwardDesc * n)()
+    for i in range(n):
+        fill_block_desc(descs[i], blocks[i], grads[i], B, N + 1, Tp, Cd, H)
+    g_norm_w, g_norm_b = torch.empty_like(norm_w), torch.empty_like(norm_b)
+    g_stream = torch.empty(B * Tp, Cd, dtype=torch.float32, device=dev)
+    nbytes = _bytes(L.mhmr_vit_tail_backward_workspace_bytes(B, Tp, Cd), "mhmr_vit_tail_backward_workspace_bytes")
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    d = _lib.VitTailBackwardDesc()
+    d.B, d.N, d.T, d.Tp, d.C, d.H, d.n = B, N, N + 1, Tp, Cd, H, n
+    d.norm_w, d.norm_b, d.blocks = norm_w.data_ptr(), norm_b.data_ptr(), C.cast(descs, C.POINTER(_lib.VitBlockBackwardDesc))
+    d.tap, d.resid, d.g_feat = tap.data_ptr(), resid.data_ptr(), g_feat.data_ptr()
+    d.g_norm_w, d.g_norm_b, d.g_stream, d.workspace, d.workspace_bytes = g_norm_w.data_ptr(), g_norm_b.data_ptr(), g_stream.data_ptr(), wsb.data_ptr(), nbytes
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(L.mhmr_vit_tail_backward(C.byref(d), stream), "mhmr_vit_tail_backward")
+    return g_stream, g_norm_w, g_norm_b, grads
+
+
+def model_tail_backward(model, P, ws, B, g_feat, n):
+    """The tail backward of ``model`` on the workspace of its last ``train_backbone`` forward of batch size B: the fp32 master weights
+    are the ``nn.Parameter``s themselves; one call per image block of the workspace (``Model._nsplit``), the parameter gradients of the
+    blocks added in block order.  -> {parameter name: gradient} for ``backbone_parameter_names(depth, n)``."""
+    enc = model.backbone.encoder
+    depth, N, Cd, H = len(enc.blocks), P["N"], P["C"], P["H"]
+    if ws.get("tap_blocks") != n:
+        raise _lib.MhmrError(f"Model: this workspace taps {ws.get('tap_blocks')} blocks, the backward needs {n}")
+    dev = ws["feat32"].device
+    norm_w, norm_b = _f32(enc.norm.weight), _f32(enc.norm.bias)
+    blocks = [block_tensors(enc.blocks[l], dev) for l in range(depth - n, depth)]
+    g_feat = _f32(g_feat).reshape(B * N, Cd)
+    total = None
+    for part in ws["parts"]:
+        Bh, i0, bufs = part["B"], part["img0"], part["bufs"]
+        _, gw, gb, grads = tail_backward(norm_w, norm_b, blocks, bufs["tap"], bufs["resid"], g_feat[i0 * N:(i0 + Bh) * N], Bh, N, ws["Tp"], H)
+        flat = [gw, gb] + [g[f] for g in grads for f in _lib.VitBlockBackwardDesc.PARAMS]
+        total = flat if total is None else [a + b for a, b in zip(total, flat)]
+    return dict(zip(backbone_parameter_names(depth, n), total))
+
+
+class _TailFunction(torch.autograd.Function):
+    """(the parameters of backbone_parameter_names) -> features [B, N, C]: the values are the ones the forward has already computed."""
+
+    @staticmethod
+    def forward(ctx, model, st, *params):
+        ctx.model, ctx.st = model, st
+        return st["features"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_feat):
+        model, st = ctx.model, ctx.st
+        P, ws = st["P"], st["ws"]
+        if ws.get("generation") != st["generation"] or P.get("backbone_generation", 0) != st["backbone_generation"] or model._packed is not P:
+            raise _lib.MhmrError("Model: backward must run before the next forward of the same batch size and before repack_backbone() / "
+                                 "repack(): the workspace (the tapped residual streams) this forward used has been overwritten since")
+        need = ctx.needs_input_grad[2:]
+        with model._lock, torch.cuda.device(st["dev"]):
+            grads = model_tail_backward(model, P, ws, st["B"], g_feat, st["n"])
+        return (None, None) + tuple(grads[k].view_as(p) if want else None for (k, p), want in zip(st["named"], need))
+
+
+def attach(model, P, ws, B):
+    """-> the features of the forward that has just run on ``ws`` (a clone, [B, N, C]) attached to autograd with respect to
+    ``model.backbone_parameters(n)``: the node that hands the feature cotangent to ``mhmr_vit_tail_backward``."""
+    n = int(getattr(model, "_backbone_n", 1))
+    params = dict(model.named_parameters())
+    named = [(k, params[k]) for k in backbone_parameter_names(len(model.backbone.encoder.blocks), n)]
+    st = dict(P=P, ws=ws, B=B, n=n, dev=ws["feat32"].device, generation=ws["generation"], backbone_generation=P.get("backbone_generation", 0),
+              named=named, features=ws["feat32"].view(B, P["N"], P["C"]).clone())
+    with torch.enable_grad():
+        return _TailFunction.apply(model, st, *[p for _, p in named])
+
+
+__all__ = ["BLOCK_FIELDS", "backbone_parameter_names", "attention_tape", "attention_backward", "block_tensors", "block_backward", "tail_backward",
+           "model_tail_backward", "attach"]

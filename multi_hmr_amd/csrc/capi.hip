@@ -244,6 +244,15 @@ int mhmr_gelu16_pair(const float* in, void* out16, long long M, int N, int dtype
 // The f16x3 precision mode (include/mhmr.h, mhmr_vit_desc.x3): the same block structure with every linear as three 16-bit products per
 // term over operand PAIRS, fp32 LayerNorm / GELU / attention / residual.  All B * Tp rows go through every linear (no token-row map, no
 // LayerNorm fold, no class-row kernel): this mode buys accuracy, at ~3x the matrix work and a 1/16-rate attention.
+// The tap (include/mhmr.h, mhmr_vit_desc.tap): before block l >= tap_first the residual stream goes into slot l - tap_first.  An ordinary
+// stream operation: it waits for every launch in front of it, any-order launches included.  NULL: nothing is issued.
+static int vit_tap(const mhmr_vit_desc* d, int l, hipStream_t s) {
+    if (!d->tap || l < d->tap_first) return 0;
+    const size_t n = (size_t)d->B * d->Tp * d->C;
+    const hipError_t e = hipMemcpyAsync(d->tap + (size_t)(l - d->tap_first) * n, d->resid, n * sizeof(float), hipMemcpyDeviceToDevice, s);
+    return e == hipSuccess ? 0 : (int)e;
+}
+
 static int vit_forward_x3(const mhmr_vit_desc* d, const float* x, float* feat32, void* ctx16, int ldctx, hipStream_t s) {
     const int dt = d->dtype, B = d->B, C = d->C, Tp = d->Tp, M = B * Tp, Kp = d->Kp;
     const int Mp = (B * d->N + 127) / 128 * 128;
@@ -260,6 +269,7 @@ static int vit_forward_x3(const mhmr_vit_desc* d, const float* x, float* feat32,
     for (int l = 0; l < d->L; ++l) {
         const mhmr_vit_block& k = d->blocks[l];
         if (k.flags || k.v_w2 || k.proj_w2) return MHMR_ERR_BAD_ARG;
+        TRY(vit_tap(d, l, s));
         // x = x + ls1 * proj(MHSA(norm1(x)))
         TRY(mhmr_launch_layernorm_pair(d->resid, k.ln1_w, k.ln1_b, d->xn, M, C, 1e-6f, dt, s));
         {
@@ -539,6 +549,7 @@ int vit_launch(const mhmr_vit_desc* d, const VitForm& f, const float* x, float* 
         const mhmr_vit_block& k = d->blocks[l];
         const VitBlockOps b = vit_block_ops(d, f, l);
         if (b.rc) return b.rc;
+        TRY(vit_tap(d, l, s));
 
         // ---- x = x + ls1 * proj(MHSA(norm1(x)))
         if (b.f1) { if (!stats_fresh) TRY(ln_stats()); }
@@ -638,6 +649,7 @@ int vit_form_of(const mhmr_vit_desc* d, hipStream_t s, VitForm* f) {
     if (d->S % 14 || d->G * 14 != d->S || d->N != d->G * d->G || d->T != d->N + 1 || d->Tp % 64 || d->Tp < d->T ||
         d->C != d->H * 64 || d->Kp % 64 || d->Kp < 588 || (d->C != 384 && d->C != 768 && d->C != 1024))
         return MHMR_ERR_BAD_SHAPE;
+    if (d->tap && (d->tap_first < 0 || d->tap_first > d->L || !d->resid)) return MHMR_ERR_BAD_ARG;
     if (d->x3) { *f = VitForm{}; f->x3 = true; return 0; }      // vit_forward_x3: none of the choices below exists there
     const VitSwitches w = vit_switches();
     *f = vit_form(d, w, mhmr_cu_count(), w.anyorder && stream_takes_anyorder(s));

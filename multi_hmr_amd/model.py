@@ -431,6 +431,48 @@ class Model(nn.Module):
             p.requires_grad_(bool(flag))
         return self
 
+    def backbone_parameters(self, n=1):
+        """The final norm and the last ``n`` blocks of the encoder (``backbone_train.backbone_parameter_names``): what
+        ``train_backbone=True`` differentiates.  They stay ``requires_grad=False`` until ``train_backbone_(n)``."""
+        from .backbone_train import backbone_parameter_names
+        params = dict(self.named_parameters())
+        return [params[k] for k in backbone_parameter_names(len(self.backbone.encoder.blocks), n)]
+
+    def train_backbone_(self, n=1, flag=True):
+        """Set ``requires_grad`` of ``backbone_parameters(n)`` (``1 <= n <= depth``) and remember ``n``: a ``train_backbone=True`` forward
+        taps the residual stream in front of the last ``n`` blocks and its backward stops there.  Returns self."""
+        for p in self.backbone_parameters(n):
+            p.requires_grad_(bool(flag))
+        self._backbone_n = int(n)
+        return self
+
+    def repack_backbone(self):
+        """Re-pack the final norm and the last ``n`` blocks (``train_backbone_``'s n) into the buffers the descriptors already point to --
+        after an optimiser step on ``backbone_parameters(n)``.  Fold, column sums, low halves and fp8 rows of a block are derived again
+        from its parameters by the code that packed them (``vit.pack_block``), so the next forward equals ``repack()`` + forward bit for
+        bit (the precision a pack resolved from ``'auto'`` is kept).  The head pack and the workspaces stay.  A pending ``backward`` must
+        run first."""
+        with self._lock:
+            P = self._packed
+            if P is None:
+                return
+            enc, v = self.backbone.encoder, P["vit"]
+            L = len(enc.blocks)
+            f32 = lambda t: t.detach().to(device=P["device"], dtype=torch.float32).contiguous()
+            with torch.no_grad():
+                for l in range(L - int(getattr(self, "_backbone_n", 1)), L):
+                    new, scalars = vit.pack_block(P, enc.blocks[l], l)
+                    for name, t in new.items():
+                        old = v["block_t"][l][name]
+                        assert (t is None) == (old is None) and (t is None or t.shape == old.shape), name
+                        if t is not None:
+                            old.copy_(t)
+                    for name, val in scalars.items():
+                        setattr(v["blocks"][l], name, val)
+                v["norm_t"]["norm_w"].copy_(f32(enc.norm.weight))
+                v["norm_t"]["norm_b"].copy_(f32(enc.norm.bias))
+            P["backbone_generation"] = P.get("backbone_generation", 0) + 1
+
     @property
     def packed_precision(self):
         """The operand format the current pack runs ('f16', 'bf16' or 'f16x3'); None before the first forward / after a repack."""
@@ -458,13 +500,13 @@ class Model(nn.Module):
             n -= 1
         return n
 
-    def _workspace(self, P, B):
+    def _workspace(self, P, B, tap=0):
         def extra(P, B, z):
             Mp = roundup(B * P["N"], 128)
             return dict(ctx16=z(Mp, P["Kc"]), zK=z(B * P["N"], P["E"], dtype=torch.float32), scores=z(B * P["N"], dtype=torch.float32),
                         counts=z(B, dtype=torch.int32), kv=z(Mp, P["hph"]["n_kv"], dtype=torch.float32),
                         hid_cls=z(Mp, P["C"]))
-        return self._ws.get(P, B, extra, self._nsplit(B))
+        return self._ws.get(P, B, extra, self._nsplit(B), tap)
 
     # -------------------------------------------------------------------------------------------------- forward
     def _side_streams(self, dev, n):
@@ -505,14 +547,23 @@ class Model(nn.Module):
         for ev in joins:
             main.wait_event(ev)
 
-    def backbone_features(self, x):
-        """[B,3,S,S] -> [B,N,C] fp32 patch features (reference blocks/dinov2.py:16-26), as a view of the workspace."""
+    def backbone_features(self, x, train_backbone=False):
+        """[B,3,S,S] -> [B,N,C] fp32 patch features (reference blocks/dinov2.py:16-26), as a view of the workspace.
+        ``train_backbone=True``: a ``.clone()`` of them instead, attached to autograd with respect to ``backbone_parameters(n)``
+        (``train_backbone_``'s n): the backbone tail on its own.  Its backward reads this call's workspace (the tapped streams), so it must
+        run before the next forward of the same batch size."""
         with self._lock:                      # (workspaces belong to the instance: same lock as forward(); round-5 advisor finding)
+            if train_backbone:
+                x = x.float().contiguous()
+                P, ws, stream = self._prepare(x, tap=int(getattr(self, "_backbone_n", 1)))
+                self._run_backbone(P, ws, x)
+                from . import backbone_train
+                return backbone_train.attach(self, P, ws, x.shape[0])
             P, ws, stream = self._prepare(x)
             self._run_backbone(P, ws, x)
             return ws["feat32"].view(x.shape[0], P["N"], P["C"])
 
-    def _prepare(self, x):
+    def _prepare(self, x, tap=0):
         if self.camera_embedding is None:
             raise AttributeError("'Model' object has no attribute 'camera' (camera_embedding=None: the reference's forward fails the same "
                                  "way at model.py:262 -> :183)")
@@ -523,7 +574,7 @@ class Model(nn.Module):
         P = self._packed
         if P is None or P["device"] != x.device:
             P = self._pack(x.device)
-        ws = self._workspace(P, x.shape[0])
+        ws = self._workspace(P, x.shape[0], tap)
         return P, ws, torch.cuda.current_stream(x.device).cuda_stream
 
     @torch.no_grad()
@@ -542,7 +593,14 @@ class Model(nn.Module):
         ``train_detection=True`` (needs ``is_training=True``; independent of ``return_readout`` and ``train_heads``): the same dict, key for
         key and bit for bit, with ``out["scores"]`` attached to autograd with respect to ``detection_parameters()`` (those that require
         grad: ``train_detection_(True)``).  The same rule for the backward; with no person the detection gradients are NOT zeros (every
-        cell is a negative of the focal term)."""
+        cell is a negative of the focal term).
+        ``train_backbone=True`` (needs ``is_training=True``; composes with the other switches and ``return_readout``): the same dict, key
+        for key and bit for bit, with its outputs attached to autograd with respect to ``backbone_parameters(n)`` (``train_backbone_``'s
+        n): the forward taps the residual stream in front of the last n blocks, the feature cotangent of
+        ``forward_features`` carries the gradient to the features, and one node hands it to ``mhmr_vit_tail_backward``.  The same rule
+        for the backward; afterwards an optimiser step and ``repack_backbone()``."""
+        if kwargs.get("train_backbone", False) and not is_training:
+            raise ValueError("train_backbone=True needs is_training=True")
         if kwargs.get("train_detection", False) and not is_training:
             raise ValueError("train_detection=True needs is_training=True")
         if kwargs.get("train_heads", False) and not (is_training and kwargs.get("return_readout", False)):
@@ -551,7 +609,7 @@ class Model(nn.Module):
             return self._forward(x.float().contiguous(), idx, det_thresh, nms_kernel_size, K, is_training,
                                  bool(kwargs.get("return_image_index", False)), bool(kwargs.get("return_batched", False)),
                                  bool(kwargs.get("return_readout", False)), bool(kwargs.get("train_heads", False)),
-                                 bool(kwargs.get("train_detection", False)))
+                                 bool(kwargs.get("train_detection", False)), bool(kwargs.get("train_backbone", False)))
 
     supports_image_index = True
     supports_batched = True
@@ -642,15 +700,19 @@ class Model(nn.Module):
                                                        P["C"], P["dt_id"], stream), "mhmr_features_to_context")
 
     def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, with_ids=False, batched=False, with_readout=False,
-                 train_heads=False, train_detection=False):
-        P, ws, stream = self._prepare(x)
+                 train_heads=False, train_detection=False, train_backbone=False):
+        P, ws, stream = self._prepare(x, tap=int(getattr(self, "_backbone_n", 1)) if train_backbone else 0)
         dev, B = x.device, x.shape[0]
         K = K.to(device=dev, dtype=torch.float32).contiguous()
         assert K.shape == (B, 3, 3)
 
         self._front(P, ws, x, K, stream)
+        features = None
+        if train_backbone:          # the features as a tensor attached to the backbone parameters: the route of forward_features from here on
+            from . import backbone_train
+            features = backbone_train.attach(self, P, ws, B)
         return self._behind_front(P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, with_ids, batched, with_readout,
-                                  train_heads, train_detection, None)
+                                  train_heads, train_detection, features)
 
     def _behind_front(self, P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, with_ids, batched, with_readout,
                       train_heads, train_detection, features):

@@ -89,15 +89,26 @@ class Trainer:
             return None
         heads = any(p.requires_grad for p in model.heads_parameters())
         detection = any(p.requires_grad for p in model.detection_parameters())
-        if not (heads or detection):
+        # backbone parameters in the optimiser's groups (any torch.optim optimiser; HeadsAdam covers the heads and the detector only)
+        in_opt = {id(p) for g in getattr(opt, "param_groups", ()) for p in g["params"]}
+        backbone = any(p.requires_grad and id(p) in in_opt for p in model.backbone_parameters(int(getattr(model, "_backbone_n", 1))))
+        if not (heads or detection or backbone):
             raise _lib.MhmrError("Trainer: nothing to train -- call model.train_heads_(True) and / or model.train_detection_(True) first")
-        out = forward(x, idx=gt["idx"], K=gt["K"], is_training=True, return_readout=True, train_heads=heads, train_detection=detection)
+        kw = {}
+        if backbone:
+            if forward is not model:
+                raise ValueError("Trainer.train_step_features: stored features cannot follow a backbone that is being trained "
+                                 "(backbone parameters that require grad are in the optimiser); use train_step")
+            kw["train_backbone"] = True
+        out = forward(x, idx=gt["idx"], K=gt["K"], is_training=True, return_readout=True, train_heads=heads, train_detection=detection, **kw)
         pred = model.decode_readout(out["readout"], out["offset"], gt["idx"], gt["K"])
         total, dict_loss = self.loss(dict(pred, scores=out["scores"]), gt, epoch=self.current_epoch, img_size=model.img_size)
         total.backward()                                      # before the optimiser step: it reads the packed weights the step rewrites
         opt.step()
         if not isinstance(opt, HeadsAdam):
             model.repack_heads()
+        if backbone:
+            model.repack_backbone()
         opt.zero_grad(set_to_none=True)
         return dict_loss
 

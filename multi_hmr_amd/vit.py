@@ -180,7 +180,6 @@ def pack_encoder(enc, img_size: int, precision: str, device, wlo: str | None = N
     G = img_size // PATCH
     N, T = G * G, G * G + 1
     f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
-    op = lambda t: t.detach().to(device=device, dtype=torch.float32).to(tdt).contiguous()
     keep = []
 
     def k(t):
@@ -208,35 +207,58 @@ def pack_encoder(enc, img_size: int, precision: str, device, wlo: str | None = N
     blocks = (_lib.VitBlock * L)()
     if x3:
         # every linear as three products over operand pairs; fp32 LayerNorm / GELU / attention (csrc/capi.hip vit_forward_x3)
-        tr = lambda t: triple(f32(t), tdt)
-        P["wlo"], P["fold"] = {}, False
-        for i, b in enumerate(enc.blocks):
-            blk = blocks[i]
-            blk.flags, blk.v_w2, blk.proj_w2, blk.qkv_colsum, blk.fc1_colsum = 0, None, None, None, None
-            blk.ln1_w, blk.ln1_b = k(f32(b.norm1.weight)), k(f32(b.norm1.bias))
-            blk.qkv_w, blk.qkv_b = k(tr(b.attn.qkv.weight)), k(f32(b.attn.qkv.bias))
-            blk.proj_w, blk.proj_b, blk.ls1 = k(tr(b.attn.proj.weight)), k(f32(b.attn.proj.bias)), k(f32(b.ls1.gamma))
-            blk.ln2_w, blk.ln2_b = k(f32(b.norm2.weight)), k(f32(b.norm2.bias))
-            blk.fc1_w, blk.fc1_b = k(tr(b.mlp.fc1.weight)), k(f32(b.mlp.fc1.bias))
-            blk.fc2_w, blk.fc2_b, blk.ls2 = k(tr(b.mlp.fc2.weight)), k(f32(b.mlp.fc2.bias)), k(f32(b.ls2.gamma))
-        P["vit"] = dict(blocks=blocks, patch_w=k(triple(pw, tdt)), patch_b=k(f32(enc.patch_embed.proj.bias)),
-                        cls_pos0=k(cls_pos0.contiguous()), pos=k(pos.contiguous()), norm_w=k(f32(enc.norm.weight)),
-                        norm_b=k(f32(enc.norm.bias)))
-        P["keep"] = keep
-        return P
-    lo_passes = parse_wlo(default_wlo(Cd) if wlo is None else wlo, L)
-    P["wlo"] = {i: sorted(v) for i, v in lo_passes.items()}
-    # LayerNorm fold: norm2 -> fc1 in every block, norm1 -> qkv from block 1 on (block 0's norm1 follows the patch embedding, whose
-    # epilogue leaves no row statistics: it stays a LayerNorm pass).  A folded linear consumes the RAW 16-bit residual rows:
-    #   y = rstd (x16 . W'^T - mean colsum) + b',   W' = W diag(w_ln) (rounded to 16 bits AFTER the fold),  b' = b + W b_ln,
-    #   colsum[n] = sum_k W'[n][k] over exactly the 16-bit values the matrix pipe multiplies (hi + lo where there is a low half)
-    P["fold"] = fold_eligible(Cd, N) if lnfold is None else bool(lnfold)
-    if P["fold"] and Cd % 128:
-        raise ValueError("lnfold needs embed_dim to be a multiple of 128")
-    # C = 384 with the fold: every array indexed by the output channel of the C-wide linears (V, proj, fc2) is zero-padded to Cp = 512 rows /
-    # entries -- they run as N = 512 on the 256x256 kernel with the last 128 columns masked (include/mhmr.h, mhmr_vit_desc.cpad)
+        P["wlo"], P["fold"], P["lo_passes"] = {}, False, {}
+    else:
+        lo_passes = parse_wlo(default_wlo(Cd) if wlo is None else wlo, L)
+        P["wlo"], P["lo_passes"] = {i: sorted(v) for i, v in lo_passes.items()}, lo_passes
+        # LayerNorm fold: norm2 -> fc1 in every block, norm1 -> qkv from block 1 on (block 0's norm1 follows the patch embedding, whose
+        # epilogue leaves no row statistics: it stays a LayerNorm pass).  A folded linear consumes the RAW 16-bit residual rows:
+        #   y = rstd (x16 . W'^T - mean colsum) + b',   W' = W diag(w_ln) (rounded to 16 bits AFTER the fold),  b' = b + W b_ln,
+        #   colsum[n] = sum_k W'[n][k] over exactly the 16-bit values the matrix pipe multiplies (hi + lo where there is a low half)
+        P["fold"] = fold_eligible(Cd, N) if lnfold is None else bool(lnfold)
+        if P["fold"] and Cd % 128:
+            raise ValueError("lnfold needs embed_dim to be a multiple of 128")
+        # C = 384 with the fold: every array indexed by the output channel of the C-wide linears (V, proj, fc2) is zero-padded to Cp = 512 rows /
+        # entries -- they run as N = 512 on the 256x256 kernel with the last 128 columns masked (include/mhmr.h, mhmr_vit_desc.cpad)
+        P["cpad"] = roundup(Cd, 256) if (P["fold"] and Cd % 256) else 0
+        P["lo8"] = lo8_eligible(Cd) and bool(lo_passes)
+    block_t = []
+    for i, b in enumerate(enc.blocks):
+        t, scalars = pack_block(P, b, i)
+        block_t.append(t)
+        for n, v in t.items():
+            setattr(blocks[i], n, None if v is None else k(v))
+        for n, v in scalars.items():
+            setattr(blocks[i], n, v)
+    norm_t = dict(norm_w=f32(enc.norm.weight), norm_b=f32(enc.norm.bias))
+    P["vit"] = dict(blocks=blocks, patch_w=k(triple(pw, tdt) if x3 else pw.to(tdt).contiguous()), patch_b=k(f32(enc.patch_embed.proj.bias)),
+                    cls_pos0=k(cls_pos0.contiguous()), pos=k(pos.contiguous()), norm_w=k(norm_t["norm_w"]), norm_b=k(norm_t["norm_b"]),
+                    block_t=block_t, norm_t=norm_t)
+    P["keep"] = keep
+    return P
+
+
+def pack_block(P: dict, b, i: int):
+    """The packed tensors of ONE encoder block under the pack's choices (``P``: precision, fold, cpad, lo8, lo_passes) ->
+    ({mhmr_vit_block pointer field: tensor or None}, {scalar field: int}).  Everything -- the LayerNorm fold, the column sums, the low
+    halves and their fp8 rows -- derives from the block's parameters here, so ``pack_encoder`` and ``Model.repack_backbone`` (which copies
+    a re-packed block into the tensors the descriptors already point to) cannot drift apart."""
+    device, tdt, Cd = P["device"], P["tdt"], P["C"]
+    f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+    op = lambda t: t.detach().to(device=device, dtype=torch.float32).to(tdt).contiguous()
+    t = dict.fromkeys(("ln1_w", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2",
+                       "v_w2", "proj_w2", "qkv_colsum", "fc1_colsum", "v_w8", "proj_w8"))
+    if P.get("x3"):
+        tr = lambda w: triple(f32(w), tdt)
+        t["ln1_w"], t["ln1_b"] = f32(b.norm1.weight), f32(b.norm1.bias)
+        t["qkv_w"], t["qkv_b"] = tr(b.attn.qkv.weight), f32(b.attn.qkv.bias)
+        t["proj_w"], t["proj_b"], t["ls1"] = tr(b.attn.proj.weight), f32(b.attn.proj.bias), f32(b.ls1.gamma)
+        t["ln2_w"], t["ln2_b"] = f32(b.norm2.weight), f32(b.norm2.bias)
+        t["fc1_w"], t["fc1_b"] = tr(b.mlp.fc1.weight), f32(b.mlp.fc1.bias)
+        t["fc2_w"], t["fc2_b"], t["ls2"] = tr(b.mlp.fc2.weight), f32(b.mlp.fc2.bias), f32(b.ls2.gamma)
+        return t, dict(flags=0)
+    lo_passes = P["lo_passes"]
     Cp = roundup(Cd, 256)
-    P["cpad"] = Cp if (P["fold"] and Cd % 256) else 0
 
     def padn(t, n=None):
         """zero-pad dim 0 to n (default Cp) entries when this pack runs the masked form"""
@@ -244,8 +266,6 @@ def pack_encoder(enc, img_size: int, precision: str, device, wlo: str | None = N
         if not P["cpad"] or t.shape[0] >= n:
             return t.contiguous()
         return torch.cat([t, t.new_zeros((n - t.shape[0],) + tuple(t.shape[1:]))], 0).contiguous()
-
-    P["lo8"] = lo8_eligible(Cd) and bool(lo_passes)
 
     def folded(lin, norm, lo_rows=None):
         """-> (op16 W' [N, K], fp32 b' [N], fp32 colsum [N], hi|lo of rows lo_rows or None, their fp8 form (rows, scale) or None)"""
@@ -266,44 +286,35 @@ def pack_encoder(enc, img_size: int, precision: str, device, wlo: str | None = N
                 w8 = (rows8, sc)
         return W16.contiguous(), bias.contiguous(), colsum.float().contiguous(), w2, w8
 
-    for i, b in enumerate(enc.blocks):
-        blk = blocks[i]
-        f1, f2 = P["fold"] and i > 0, P["fold"]            # block 0's norm1 reads the patch embedding: no producer to fold into
-        v_rows = slice(2 * Cd, 3 * Cd)
-        blk.flags = (1 if f1 else 0) | (2 if f2 else 0)
-        blk.proj_w2 = k(padn(hi_lo(f32(b.attn.proj.weight), tdt))) if "proj" in lo_passes.get(i, ()) else None
-        blk.v_w8, blk.proj_w8, blk.v_w8_scale, blk.proj_w8_scale = None, None, 127, 127
-        if P["lo8"] and "proj" in lo_passes.get(i, ()):
-            pw32 = f32(b.attn.proj.weight)
-            rows8, blk.proj_w8_scale, _ = lo8_rows(pw32.to(tdt), pw32)
-            blk.proj_w8 = k(rows8)
-        blk.ln1_w, blk.ln1_b = k(f32(b.norm1.weight)), k(f32(b.norm1.bias))
-        if f1:
-            w16, bias, colsum, v2, v8 = folded(b.attn.qkv, b.norm1, v_rows if "v" in lo_passes.get(i, ()) else None)
-            blk.qkv_w, blk.qkv_b, blk.qkv_colsum = k(padn(w16, 2 * Cd + Cp)), k(padn(bias, 2 * Cd + Cp)), k(padn(colsum, 2 * Cd + Cp))
-            blk.v_w2 = k(padn(v2)) if v2 is not None else None
-            if v8 is not None:
-                blk.v_w8, blk.v_w8_scale = k(v8[0]), v8[1]
-        else:
-            blk.qkv_w, blk.qkv_b, blk.qkv_colsum = k(padn(op(b.attn.qkv.weight), 2 * Cd + Cp)), k(padn(f32(b.attn.qkv.bias), 2 * Cd + Cp)), None
-            blk.v_w2 = k(padn(hi_lo(f32(b.attn.qkv.weight)[v_rows], tdt))) if "v" in lo_passes.get(i, ()) else None
-            if P["lo8"] and "v" in lo_passes.get(i, ()):
-                vw32 = f32(b.attn.qkv.weight)[v_rows]
-                rows8, blk.v_w8_scale, _ = lo8_rows(vw32.to(tdt), vw32)
-                blk.v_w8 = k(rows8)
-        blk.proj_w, blk.proj_b, blk.ls1 = k(padn(op(b.attn.proj.weight))), k(padn(f32(b.attn.proj.bias))), k(padn(f32(b.ls1.gamma)))
-        blk.ln2_w, blk.ln2_b = k(f32(b.norm2.weight)), k(f32(b.norm2.bias))
-        if f2:
-            w16, bias, colsum, _, _ = folded(b.mlp.fc1, b.norm2)
-            blk.fc1_w, blk.fc1_b, blk.fc1_colsum = k(w16), k(bias), k(colsum)
-        else:
-            blk.fc1_w, blk.fc1_b, blk.fc1_colsum = k(op(b.mlp.fc1.weight)), k(f32(b.mlp.fc1.bias)), None
-        blk.fc2_w, blk.fc2_b, blk.ls2 = k(padn(op(b.mlp.fc2.weight))), k(padn(f32(b.mlp.fc2.bias))), k(padn(f32(b.ls2.gamma)))
-    P["vit"] = dict(blocks=blocks, patch_w=k(pw.to(tdt).contiguous()), patch_b=k(f32(enc.patch_embed.proj.bias)),
-                    cls_pos0=k(cls_pos0.contiguous()), pos=k(pos.contiguous()), norm_w=k(f32(enc.norm.weight)),
-                    norm_b=k(f32(enc.norm.bias)))
-    P["keep"] = keep
-    return P
+    f1, f2 = P["fold"] and i > 0, P["fold"]            # block 0's norm1 reads the patch embedding: no producer to fold into
+    v_rows = slice(2 * Cd, 3 * Cd)
+    sc = dict(flags=(1 if f1 else 0) | (2 if f2 else 0), v_w8_scale=127, proj_w8_scale=127)
+    t["proj_w2"] = padn(hi_lo(f32(b.attn.proj.weight), tdt)) if "proj" in lo_passes.get(i, ()) else None
+    if P["lo8"] and "proj" in lo_passes.get(i, ()):
+        pw32 = f32(b.attn.proj.weight)
+        t["proj_w8"], sc["proj_w8_scale"], _ = lo8_rows(pw32.to(tdt), pw32)
+    t["ln1_w"], t["ln1_b"] = f32(b.norm1.weight), f32(b.norm1.bias)
+    if f1:
+        w16, bias, colsum, v2, v8 = folded(b.attn.qkv, b.norm1, v_rows if "v" in lo_passes.get(i, ()) else None)
+        t["qkv_w"], t["qkv_b"], t["qkv_colsum"] = padn(w16, 2 * Cd + Cp), padn(bias, 2 * Cd + Cp), padn(colsum, 2 * Cd + Cp)
+        t["v_w2"] = padn(v2) if v2 is not None else None
+        if v8 is not None:
+            t["v_w8"], sc["v_w8_scale"] = v8[0], v8[1]
+    else:
+        t["qkv_w"], t["qkv_b"] = padn(op(b.attn.qkv.weight), 2 * Cd + Cp), padn(f32(b.attn.qkv.bias), 2 * Cd + Cp)
+        t["v_w2"] = padn(hi_lo(f32(b.attn.qkv.weight)[v_rows], tdt)) if "v" in lo_passes.get(i, ()) else None
+        if P["lo8"] and "v" in lo_passes.get(i, ()):
+            vw32 = f32(b.attn.qkv.weight)[v_rows]
+            t["v_w8"], sc["v_w8_scale"], _ = lo8_rows(vw32.to(tdt), vw32)
+    t["proj_w"], t["proj_b"], t["ls1"] = padn(op(b.attn.proj.weight)), padn(f32(b.attn.proj.bias)), padn(f32(b.ls1.gamma))
+    t["ln2_w"], t["ln2_b"] = f32(b.norm2.weight), f32(b.norm2.bias)
+    if f2:
+        w16, bias, colsum, _, _ = folded(b.mlp.fc1, b.norm2)
+        t["fc1_w"], t["fc1_b"], t["fc1_colsum"] = w16, bias, colsum
+    else:
+        t["fc1_w"], t["fc1_b"] = op(b.mlp.fc1.weight), f32(b.mlp.fc1.bias)
+    t["fc2_w"], t["fc2_b"], t["ls2"] = padn(op(b.mlp.fc2.weight)), padn(f32(b.mlp.fc2.bias)), padn(f32(b.ls2.gamma))
+    return t, sc
 
 
 def tiny_batch(P: dict, B: int) -> bool:
@@ -355,15 +366,19 @@ class WorkspaceCache:
     def clear(self):
         self._ws = {}
 
-    def get(self, P: dict, B: int, extra, nsplit: int = 1):
+    def get(self, P: dict, B: int, extra, nsplit: int = 1, tap: int = 0):
         """extra(P, B, z) -> dict of additional workspace tensors (z = zero-tensor factory in the operand dtype).
+
+        tap > 0: every image block also gets ``tap`` fp32 slots [Bh*Tp, C] into which the forward copies the residual stream entering each
+        of the last ``tap`` blocks (``mhmr_vit_desc.tap``).  ``tap`` is part of the key: a workspace asked for
+        without it has none, and its forward issues exactly the launches it always did.
 
         nsplit > 1: the batch is cut into nsplit contiguous image blocks with a backbone workspace + descriptor each (``ws["parts"]``:
         dicts with ``desc``, ``B``, ``img0``), so that the blocks can run on different streams (model.Model, MHMR_SPLIT); ``feat32`` and
         the extras cover the whole batch.  The top-level buffer names (``hid`` ...) are those of part 0."""
         if B % nsplit:
             raise ValueError(f"batch {B} does not split into {nsplit} equal image blocks")
-        key = (id(P), B, nsplit, padded_tokens(P, B // nsplit))       # (the row padding follows environment switches: A/B runs in one process)
+        key = (id(P), B, nsplit, padded_tokens(P, B // nsplit), tap)  # (the row padding follows environment switches: A/B runs in one process)
         if key in self._ws:
             self._ws[key] = self._ws.pop(key)             # most recent last
             return self._ws[key]
@@ -416,10 +431,13 @@ class WorkspaceCache:
             d.cpad = P.get("cpad", 0) if not x3 else 0
             d.v16 = b["v16"].data_ptr() if "v16" in b else None
             d.cls_pstats = b["cls_pstats"].data_ptr() if "cls_pstats" in b else None
+            if tap:
+                b["tap"] = z(tap, Bh * Tp, Cd, dtype=torch.float32)
+                d.tap, d.tap_first = b["tap"].data_ptr(), P["L"] - tap
             parts.append(dict(desc=d, B=Bh, img0=i * Bh, bufs=b))
         ws = dict(parts[0]["bufs"])
         ws["feat32"] = z(B * N, Cd, dtype=torch.float32)
         ws.update(extra(P, B, z))
-        ws["parts"], ws["vit_desc"], ws["Tp"] = parts, parts[0]["desc"], Tp
+        ws["parts"], ws["vit_desc"], ws["Tp"], ws["tap_blocks"] = parts, parts[0]["desc"], Tp, tap
         self._ws[key] = ws
         return ws

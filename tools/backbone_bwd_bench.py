@@ -1,0 +1,129 @@
+"""Time the backward of the last backbone block next to the forward of the same run, by device events, medians
+of alternating repetitions after warm-up.  Per configuration -- ViT-L 896^2 with 8 and 32 images, ViT-S 672^2 with 16 --
+  tape            mhmr_attention_f32_tape on random (Q | K | V) of the configuration's shape
+  attention_bwd   mhmr_attention_f32_backward on the same operands
+  block_bwd       mhmr_vit_block_backward (tape + backward) on a random block and stream
+  forward         Model.forward in training mode (the inference kernels; no gradient)
+  train_step      Model.forward(train_backbone=True) with n = 1 + backward of a random-cotangent scalar on the scores: the tap, the feature
+                  cotangent of the detector, the final norm and one block
+The attention lines carry the fraction of the 155 TFLOP/s fp32 matrix rate that their useful products reach (tape 4 T^2 64 per head and
+image, backward 14 T^2 64: seven products, of which the kernels compute nine -- S and dP twice in the query pass).
+One JSON line per measurement, printed and appended to --out (default profiles/backbone_bwd_bench.txt).
+  python tools/backbone_bwd_bench.py [--config all|vitl_896_8|vitl_896_32|vits_672_16] [--reps 3] [--warmup 1] [--skip-model]"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import synthetic  # noqa: E402
+from multi_hmr_amd import Model, _lib, backbone_train as bt  # noqa: E402
+from multi_hmr_amd.constants import VIT_CFG  # noqa: E402
+from eval_bench import DEV, report  # noqa: E402
+
+FP32_MFMA_FLOPS = 155e12
+CONFIGS = {"vitl_896_8": ("dinov2_vitl14", 896, 8), "vitl_896_32": ("dinov2_vitl14", 896, 32), "vits_672_16": ("dinov2_vits14", 672, 16)}
+
+
+def timed(forms, a):
+    ms = {k: [] for k in forms}
+    for r in range(a.warmup + a.reps):
+        for name, fn in forms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if r >= a.warmup:
+                ms[name].append(e0.elapsed_time(e1))
+    return ms
+
+
+def kernels(name, backbone, S, B, a):
+    Cd, H = VIT_CFG[backbone]["embed_dim"], VIT_CFG[backbone]["num_heads"]
+    T = (S // 14) ** 2 + 1
+    Tp = (T + 63) // 64 * 64
+    M = B * Tp
+    g = torch.Generator(device=DEV).manual_seed(3)
+    rn = lambda *s: torch.randn(*s, generator=g, device=DEV)
+    shape = dict(config=name, backbone=backbone, size=S, images=B, T=T, Tp=Tp, C=Cd, H=H)
+    qkv, dO = rn(M, 3 * Cd), rn(M, Cd)
+    qkv[:, :Cd] *= 2.0
+    out32, lse = bt.attention_tape(qkv, B, T, Tp, H)
+    dqkv = torch.empty(M, 3 * Cd, device=DEV)
+    ms = timed({"tape": lambda: bt.attention_tape(qkv, B, T, Tp, H),
+                "attention_bwd": lambda: bt.attention_backward(qkv, out32, lse, dO, B, T, Tp, H, dqkv=dqkv)}, a)
+    unit = float(B) * H * T * T * 64
+    med = lambda v: sorted(v)[len(v) // 2]
+    lines = [report("attention", ms, dict(shape, tape_gflop=round(4 * unit / 1e9, 1), backward_gflop=round(14 * unit / 1e9, 1),
+                                          tape_fraction_of_fp32_mfma_peak=round(4 * unit / FP32_MFMA_FLOPS / (med(ms["tape"]) * 1e-3), 4),
+                                          backward_fraction_of_fp32_mfma_peak=round(14 * unit / FP32_MFMA_FLOPS / (med(ms["attention_bwd"]) * 1e-3), 4)))]
+    del qkv, dO, out32, lse, dqkv
+    params = dict(ln1_w=1 + 0.1 * rn(Cd), ln1_b=0.1 * rn(Cd), qkv_w=rn(3 * Cd, Cd) * Cd ** -0.5, qkv_b=0.1 * rn(3 * Cd), proj_w=rn(Cd, Cd) * Cd ** -0.5,
+                  proj_b=0.1 * rn(Cd), ls1=0.5 + 0.1 * rn(Cd), ln2_w=1 + 0.1 * rn(Cd), ln2_b=0.1 * rn(Cd), fc1_w=rn(4 * Cd, Cd) * Cd ** -0.5,
+                  fc1_b=0.1 * rn(4 * Cd), fc2_w=rn(Cd, 4 * Cd) * (4 * Cd) ** -0.5, fc2_b=0.1 * rn(Cd), ls2=0.5 + 0.1 * rn(Cd))
+    x_in, g_out = rn(M, Cd), rn(M, Cd)
+    ms = timed({"block_bwd": lambda: bt.block_backward(params, x_in, g_out, B, T, Tp, H)}, a)
+    lin = 3 * 2.0 * M * 12 * Cd * Cd                       # tape, input side and weight side of the four linears
+    lines.append(report("block_backward", ms, dict(shape, workspace_bytes=int(_lib.lib().mhmr_vit_block_backward_workspace_bytes(B, Tp, Cd)),
+                                                   linear_gflop=round(lin / 1e9, 1), attention_gflop=round(18 * unit / 1e9, 1),
+                                                   fraction_of_fp32_mfma_peak=round((lin + 18 * unit) / FP32_MFMA_FLOPS / (med(ms["block_bwd"]) * 1e-3), 4),
+                                                   note="tape + backward; the linears run on the person head's fp32 kernels (16-row tiles)")))
+    return lines
+
+
+def model_level(name, backbone, S, B, a):
+    smplx_data, mean_params = synthetic.make_smplx_data(0), synthetic.make_mean_params(0)
+    m = Model(backbone=backbone, img_size=S, smplx_data=smplx_data, mean_params=mean_params, precision="f16")
+    m.load_state_dict(synthetic.make_state_dict(backbone, S, seed=0, mean_params=mean_params), strict=True)
+    m = m.to(DEV).eval().train_backbone_(1)
+    G = S // 14
+    x = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(0)).to(DEV)
+    K = synthetic.get_camera_K(S, B).to(DEV)
+    idx = tuple(t.to(DEV) for t in synthetic.make_pinned_idx(B, G, 1, seed=0))
+    cs = torch.randn(B, G, G, 1, generator=torch.Generator(device=DEV).manual_seed(5), device=DEV)
+
+    def step():
+        for p in m.backbone_parameters(1):
+            p.grad = None
+        out = m(x, idx=idx, K=K, is_training=True, train_backbone=True)
+        (out["scores"] * cs).sum().backward()
+    ms = timed({"forward": lambda: m(x, idx=idx, K=K, is_training=True), "train_step": step}, a)
+    med = lambda v: sorted(v)[len(v) // 2]
+    return [report("model", ms, dict(config=name, backbone=backbone, size=S, images=B, dtype=m.packed_precision, trainable_blocks=1,
+                                     image_blocks=m._nsplit(B), median_ratio_train_step_over_forward=round(med(ms["train_step"]) / med(ms["forward"]), 2),
+                                     note="train_step = the forward with the tap + backward of a random-cotangent scalar on the scores (detector's "
+                                          "feature cotangent, final norm, one block); no optimiser step, no re-pack"))]
+
+
+def main(a):
+    names = list(CONFIGS) if a.config == "all" else [a.config]
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as fh:
+        fh.write("# tools/backbone_bwd_bench.py: attention tape / backward, block backward and a train_backbone step next to the forward\n")
+        for name in names:
+            backbone, S, B = CONFIGS[name]
+            for line in kernels(name, backbone, S, B, a) + ([] if a.skip_model else model_level(name, backbone, S, B, a)):
+                fh.write(json.dumps(line) + "\n")
+                fh.flush()
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="all", choices=["all"] + list(CONFIGS))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "backbone_bwd_bench.txt"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("backbone_bwd_bench measures on the GPU; there is none here")
+    main(a)
