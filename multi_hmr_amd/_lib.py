@@ -403,6 +403,14 @@ def check(rc: int, what: str):
         raise MhmrError(f"{what} failed: {kind}")
 
 
+def workspace_bytes(name: str, *args) -> int:
+    """The byte count a ``mhmr_*_workspace_bytes`` entry answers for these arguments; its negative answers are error codes and raise."""
+    n = int(getattr(lib(), name)(*args))
+    if n < 0:
+        check(n, name)
+    return n
+
+
 def ptr(t) -> int | None:
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

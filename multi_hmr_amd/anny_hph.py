@@ -187,10 +187,8 @@ class _StackFn(torch.autograd.Function):
                 setattr(grads[l], name, t.data_ptr())
                 row.append(t)
             bufs.append(row)
-        nbytes = L.mhmr_xattn_layers_backward_workspace_bytes(hph.depth, dim, hph.heads, hph.mlp_dim, Kc, st["N"], st["Bp"], Pn)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "mhmr_xattn_layers_backward_workspace_bytes")
-        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        nbytes = _lib.workspace_bytes("mhmr_xattn_layers_backward_workspace_bytes", hph.depth, dim, hph.heads, hph.mlp_dim, Kc, st["N"], st["Bp"], Pn)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         g = g.float().contiguous()
         g_x0 = torch.empty(Pn, dim, dtype=torch.float32, device=dev)
         ng = len(st["gstart"])
@@ -199,7 +197,7 @@ class _StackFn(torch.autograd.Function):
                                    P=Pn, ngroups=ng - 1, nmax=max(st["counts"]), nchunks=len(st["chunks"]) // 3, ctx_valid=dim,
                                    x0=x0.data_ptr(), ctx16=st["ctx16"].data_ptr(), gstart=st["meta"][:ng].data_ptr(),
                                    chunks=st["meta"][ng:].data_ptr(), g_x_out=g.data_ptr(), g_x0=g_x0.data_ptr(), workspace=ws.data_ptr(),
-                                   workspace_bytes=int(nbytes))
+                                   workspace_bytes=nbytes)
         _lib.check(L.mhmr_xattn_layers_backward(C.byref(d), torch.cuda.current_stream(dev).cuda_stream), "mhmr_xattn_layers_backward")
         out = []
         for l in range(hph.depth):

@@ -30,13 +30,6 @@ def backbone_parameter_names(depth: int, n: int = 1) -> list:
     return names
 
 
-def _bytes(rc, what):
-    rc = int(rc)
-    if rc < 0:
-        _lib.check(rc, what)
-    return rc
-
-
 def _f32(t):
     if not t.is_cuda:
         raise _lib.MhmrError("multi_hmr_amd.backbone_train runs only on an MI355X (HIP) tensor; there is no CPU fallback")
@@ -64,7 +57,7 @@ def attention_backward(qkv, out32, lse, dO, B, T, Tp, H, stream=None, dqkv=None)
         dO = _f32(dO)
     if dqkv is None:
         dqkv = torch.empty(B * Tp, 3 * Cd, dtype=torch.float32, device=dev)
-    nbytes = _bytes(L.mhmr_attention_f32_backward_workspace_bytes(B, Tp, H), "mhmr_attention_f32_backward_workspace_bytes")
+    nbytes = _lib.workspace_bytes("mhmr_attention_f32_backward_workspace_bytes", B, Tp, H)
     wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     _lib.check(L.mhmr_attention_f32_backward(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), dO.data_ptr(), dO.stride(0), dqkv.data_ptr(), B,
@@ -100,7 +93,7 @@ def block_backward(params: dict, x_in, g_out, B, T, Tp, H, stream=None):
     dev, Cd = x_in.device, x_in.shape[1]
     grads = {f: torch.empty_like(params[f]) for f in _lib.VitBlockBackwardDesc.PARAMS}
     g_in = torch.empty_like(x_in)
-    nbytes = _bytes(L.mhmr_vit_block_backward_workspace_bytes(B, Tp, Cd), "mhmr_vit_block_backward_workspace_bytes")
+    nbytes = _lib.workspace_bytes("mhmr_vit_block_backward_workspace_bytes", B, Tp, Cd)
     wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     d = fill_block_desc(_lib.VitBlockBackwardDesc(), params, grads, B, T, Tp, Cd, H)
     d.x_in, d.g_out, d.g_in, d.workspace, d.workspace_bytes = x_in.data_ptr(), g_out.data_ptr(), g_in.data_ptr(), wsb.data_ptr(), nbytes
@@ -123,7 +116,7 @@ def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H,
         fill_block_desc(descs[i], blocks[i], grads[i], B, N + 1, Tp, Cd, H)
     g_norm_w, g_norm_b = torch.empty_like(norm_w), torch.empty_like(norm_b)
     g_stream = torch.empty(B * Tp, Cd, dtype=torch.float32, device=dev)
-    nbytes = _bytes(L.mhmr_vit_tail_backward_workspace_bytes(B, Tp, Cd), "mhmr_vit_tail_backward_workspace_bytes")
+    nbytes = _lib.workspace_bytes("mhmr_vit_tail_backward_workspace_bytes", B, Tp, Cd)
     wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     d = _lib.VitTailBackwardDesc()
     d.B, d.N, d.T, d.Tp, d.C, d.H, d.n = B, N, N + 1, Tp, Cd, H, n
@@ -169,9 +162,7 @@ class _TailFunction(torch.autograd.Function):
     def backward(ctx, g_feat):
         model, st = ctx.model, ctx.st
         P, ws = st["P"], st["ws"]
-        if ws.get("generation") != st["generation"] or P.get("backbone_generation", 0) != st["backbone_generation"] or model._packed is not P:
-            raise _lib.MhmrError("Model: backward must run before the next forward of the same batch size and before repack_backbone() / "
-                                 "repack(): the workspace (the tapped residual streams) this forward used has been overwritten since")
+        model._require_current(st["taken"])
         need = ctx.needs_input_grad[2:]
         with model._lock, torch.cuda.device(st["dev"]):
             grads = model_tail_backward(model, P, ws, st["B"], g_feat, st["n"])
@@ -181,10 +172,10 @@ class _TailFunction(torch.autograd.Function):
 def attach(model, P, ws, B):
     """-> the features of the forward that has just run on ``ws`` (a clone, [B, N, C]) attached to autograd with respect to
     ``model.backbone_parameters(n)``: the node that hands the feature cotangent to ``mhmr_vit_tail_backward``."""
-    n = int(getattr(model, "_backbone_n", 1))
+    n = model._backbone_n
     params = dict(model.named_parameters())
     named = [(k, params[k]) for k in backbone_parameter_names(len(model.backbone.encoder.blocks), n)]
-    st = dict(P=P, ws=ws, B=B, n=n, dev=ws["feat32"].device, generation=ws["generation"], backbone_generation=P.get("backbone_generation", 0),
+    st = dict(P=P, ws=ws, B=B, n=n, dev=ws["feat32"].device, taken=model._take(P, ws, "backbone_generation"),
               named=named, features=ws["feat32"].view(B, P["N"], P["C"]).clone())
     with torch.enable_grad():
         return _TailFunction.apply(model, st, *[p for _, p in named])

@@ -299,9 +299,7 @@ class _BodyFunction(torch.autograd.Function):
         if G and any(t is not None for t in (g_pose, g_coef, g_transl)):
             p, pb = model._consts(dev), model._bwd_consts(dev)
             lib = _lib.lib()
-            nbytes = int(lib.mhmr_body_backward_workspace_bytes(p["struct"], G))
-            if nbytes < 0:
-                _lib.check(nbytes, "mhmr_body_backward_workspace_bytes")
+            nbytes = _lib.workspace_bytes("mhmr_body_backward_workspace_bytes", p["struct"], G)
             ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
             d = _lib.BodyBackwardDesc()
             d.c, d.bc, d.G = C.pointer(p["struct"]), C.pointer(pb["struct"]), G

@@ -22,9 +22,7 @@ def detect_backward(hid16, ctx16, w2, b2, g_scores, rows, C_, clamped, dt_id, st
     L, dev = _lib.lib(), hid16.device
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     g_w1, g_b1, g_w2, g_b2 = f(C_, C_), f(C_), f(C_), f(1)
-    nbytes = int(L.mhmr_detect_backward_workspace_bytes(rows, C_))
-    if nbytes < 0:
-        _lib.check(nbytes, "mhmr_detect_backward_workspace_bytes")
+    nbytes = _lib.workspace_bytes("mhmr_detect_backward_workspace_bytes", rows, C_)
     wsb = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     _lib.check(L.mhmr_detect_backward(hid16.data_ptr(), hid16.stride(0), ctx16.data_ptr(), ctx16.stride(0), w2.data_ptr(), b2.data_ptr(),
                                       g_scores.data_ptr(), rows, C_, int(clamped), dt_id, g_w1.data_ptr(), g_b1.data_ptr(), g_w2.data_ptr(),
@@ -38,9 +36,7 @@ def detect_feature_grad(hid16, w16, w2, b2, g_scores, rows, C_, clamped, dt_id, 
     L, dev = _lib.lib(), hid16.device
     if g_feat is None:
         g_feat = torch.empty(rows, C_, dtype=torch.float32, device=dev)
-    nbytes = int(L.mhmr_detect_feature_grad_workspace_bytes(rows))
-    if nbytes < 0:
-        _lib.check(nbytes, "mhmr_detect_feature_grad_workspace_bytes")
+    nbytes = _lib.workspace_bytes("mhmr_detect_feature_grad_workspace_bytes", rows)
     wsb = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
     _lib.check(L.mhmr_detect_feature_grad(hid16.data_ptr(), hid16.stride(0), w16.data_ptr(), w16.stride(0), w2.data_ptr(), b2.data_ptr(),
                                           g_scores.data_ptr(), rows, C_, int(clamped), dt_id, g_feat.data_ptr(), g_feat.stride(0) if rows else C_,
@@ -63,10 +59,7 @@ class _DetectFunction(torch.autograd.Function):
         model, st = ctx.model, ctx.st
         need, need_feat = ctx.needs_input_grad[3:], ctx.needs_input_grad[2]
         dev, P, ws = st["dev"], st["P"], st["ws"]
-        if ws.get("generation") != st["generation"] or P.get("heads_generation") != st["heads_generation"] or model._packed is not P:
-            raise _lib.MhmrError("Model: backward must run before the next forward of the same batch size and before repack_heads() / "
-                                 "repack(): the workspace (context operand, features) or the packed head weights this forward used have "
-                                 "been overwritten since")
+        model._require_current(st["taken"])
         g_scores = g_scores.to(torch.float32).contiguous()
         g_feat, grads = None, (None,) * 4
         with model._lock, torch.cuda.device(dev):

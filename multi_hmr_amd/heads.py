@@ -54,10 +54,10 @@ class _DecodeFunction(torch.autograd.Function):
     def forward(ctx, model, readout, offset, det, K):
         dev, Pn = readout.device, int(readout.shape[0])
         readout, offset = readout.contiguous(), offset.contiguous()
-        packed = model._packed if model._packed is not None and model._packed["device"] == dev else model._pack(dev)
+        packed = model._packed_for(dev)
         nb, lb = packed["hph"]["nb"], packed["lbs"]
         V = lb["V"]
-        shapes = dict(_output_shapes(model, nb, V))
+        shapes = dict(model._output_shapes(packed))
         o = {n: torch.empty(Pn, *shapes[n], dtype=torch.float32, device=dev) for n in DECODE_KEYS if n != "offset"}
         o["offset"] = offset.clone()
         if Pn:
@@ -70,15 +70,9 @@ class _DecodeFunction(torch.autograd.Function):
                          ("loc", o["loc"]), ("rotmat", o["rotmat"]), ("rotvec", o["rotvec"]), ("shape", o["shape"]), ("expression", o["expression"]),
                          ("dist_postprocessed", o["dist_postprocessed"]), ("dist", o["dist"])):
                 setattr(d, n, t.data_ptr())
-            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-            rup = -(-Pn // 16) * 16
-            ws_F, ws_A, ws_xf = f(rup, lb["Kb"]), f(rup, 768), f(Pn, 24)
             with torch.cuda.device(dev):
                 _lib.check(L.mhmr_heads_decode(C.byref(d), stream), "mhmr_heads_decode")
-                _lib.check(L.mhmr_lbs_forward(C.byref(packed["lbs_struct"]), o["rotvec"].data_ptr(), o["shape"].data_ptr(), o["expression"].data_ptr(),
-                                              o["loc"].data_ptr(), o["dist"].data_ptr(), K.data_ptr(), det[0].data_ptr(), Pn, ws_F.data_ptr(),
-                                              ws_A.data_ptr(), ws_xf.data_ptr(), o["v3d"].data_ptr(), o["v2d"].data_ptr(), o["j3d"].data_ptr(),
-                                              o["j2d"].data_ptr(), o["transl"].data_ptr(), stream), "mhmr_lbs_forward")
+                model._lbs(packed, o, K, det[0], Pn, stream)
         ctx.model, ctx.nb, ctx.V = model, nb, V
         ctx.center = int(lb["center_joint"])
         ctx.save_for_backward(readout, offset, det, K, o["rotvec"], o["shape"], o["expression"], o["transl"])
@@ -118,9 +112,7 @@ class _DecodeFunction(torch.autograd.Function):
                 _lib.check(L.mhmr_body_forward(p["struct"], pose.data_ptr(), coef.data_ptr(), None, None, Pn, ws_F.data_ptr(), ws_A.data_ptr(),
                                                U.data_ptr(), UJ.data_ptr(), None, None, stream), "mhmr_body_forward")
                 # 2. placement backward: recentring, transl, projection
-                nbytes = int(L.mhmr_heads_place_workspace_bytes(V, NJ, Pn))
-                if nbytes < 0:
-                    _lib.check(nbytes, "mhmr_heads_place_workspace_bytes")
+                nbytes = _lib.workspace_bytes("mhmr_heads_place_workspace_bytes", V, NJ, Pn)
                 ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
                 gx_v, gx_j, g_transl_total = f(Pn, V, 3), f(Pn, NJ, 3), f(Pn, 3)
                 d = _lib.HeadsPlaceDesc()
@@ -132,9 +124,7 @@ class _DecodeFunction(torch.autograd.Function):
                 d.workspace_bytes = nbytes
                 _lib.check(L.mhmr_heads_place_backward(C.byref(d), stream), "mhmr_heads_place_backward")
                 # 3. body backward with the two 3D cotangents
-                nbytes = int(L.mhmr_body_backward_workspace_bytes(p["struct"], Pn))
-                if nbytes < 0:
-                    _lib.check(nbytes, "mhmr_body_backward_workspace_bytes")
+                nbytes = _lib.workspace_bytes("mhmr_body_backward_workspace_bytes", p["struct"], Pn)
                 ws2 = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
                 g_pose, g_coef = f(Pn, J, 3), f(Pn, nb + 10)
                 b = _lib.BodyBackwardDesc()
@@ -161,19 +151,12 @@ class _DecodeFunction(torch.autograd.Function):
         return None, (g_readout if ctx.needs_input_grad[1] else None), (g_offset if ctx.needs_input_grad[2] else None), None, None
 
 
-def _output_shapes(model, nb, V):
-    """Trailing shapes of the decode outputs (``Model.OUTPUT_SHAPES`` with the variable ones filled in)."""
-    var = {"shape": (nb,), "v3d": (V, 3), "v2d": (V, 2)}
-    return [(n, var[n] if s is None else s) for n, s in model.OUTPUT_SHAPES if n != "scores"]
-
-
 def decode_readout(model, readout, offset, idx, K):
     """``Model.decode_readout``: see there."""
     if not (readout.is_cuda and offset.is_cuda):
         raise _lib.MhmrError("Model.decode_readout runs on the HIP device only (no CPU fallback)")
     dev = readout.device
-    packed = model._packed if model._packed is not None and model._packed["device"] == dev else model._pack(dev)
-    nb = packed["hph"]["nb"]
+    nb = model._packed_for(dev)["hph"]["nb"]
     Pn = int(readout.shape[0])
     if readout.dim() != 2 or readout.shape[1] != readout_width(nb) or tuple(offset.shape) != (Pn, 2):
         raise ValueError(f"readout must be [P, {readout_width(nb)}] and offset [P, 2]")

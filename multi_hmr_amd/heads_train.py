@@ -82,10 +82,7 @@ class _HeadsFunction(torch.autograd.Function):
         dev, Pn, P = st["dev"], st["Pn"], st["P"]
         if Pn == 0:      # no person: no contribution, the gradients are zeros (None for the features: autograd's zero)
             return (None, None, None) + tuple(torch.zeros(s, device=dev) if n else None for s, n in zip(ctx.shapes, need))
-        if st["ws"].get("generation") != st["generation"] or P.get("heads_generation") != st["heads_generation"] or model._packed is not P:
-            raise _lib.MhmrError("Model: backward must run before the next forward of the same batch size and before repack_heads() / "
-                                 "repack(): the workspace (context operand, features) or the packed head weights this forward used have "
-                                 "been overwritten since")
+        model._require_current(st["taken"])
         h = P["hph"]
         L, stream = _lib.lib(), torch.cuda.current_stream(dev).cuda_stream
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -103,9 +100,7 @@ class _HeadsFunction(torch.autograd.Function):
         g_zc, g_token = f(Pn, C_), f(Pn, Ktok)
         g_feat = f(st["B"] * P["N"], C_) if need_feat else None
         fwd = st["desc"]
-        nbytes = int(L.mhmr_hph_backward_workspace_bytes(C.byref(fwd), st["B"], Pn))
-        if nbytes < 0:
-            _lib.check(nbytes, "mhmr_hph_backward_workspace_bytes")
+        nbytes = _lib.workspace_bytes("mhmr_hph_backward_workspace_bytes", C.byref(fwd), st["B"], Pn)
         wsb = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         g_readout, g_offset = g_readout.to(torch.float32).contiguous(), g_offset.to(torch.float32).contiguous()
         d = _lib.HphBackwardDesc()

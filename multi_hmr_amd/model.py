@@ -9,9 +9,11 @@ CPU / eager fallback: without the library, or on a non-GPU tensor, ``forward`` r
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 import threading
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -224,8 +226,39 @@ def _load_mean_params(explicit):
     return dict(np.load(MEAN_PARAMS))
 
 
+def _f32(t, device):
+    return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+class Switches(NamedTuple):
+    """What the keywords of one ``forward`` / ``forward_features`` call ask for."""
+    with_ids: bool
+    batched: bool
+    with_readout: bool
+    train_heads: bool
+    train_detection: bool
+    train_backbone: bool
+
+
+def call_switches(is_training, kwargs, from_features=False) -> Switches:
+    """The switches of ``Model.forward(..., is_training, **kwargs)`` -- or, ``from_features``, of ``forward_features``, which has no backbone
+    to train and does not read ``train_backbone``.  Combinations that make no sense raise ``ValueError``; keywords that are none of ours are
+    ignored, as the reference's ``*args, **kwargs`` ignores them."""
+    on = lambda name: bool(kwargs.get(name, False))
+    train_backbone = on("train_backbone") and not from_features
+    if train_backbone and not is_training:
+        raise ValueError("train_backbone=True needs is_training=True")
+    if on("train_detection") and not is_training:
+        raise ValueError("train_detection=True needs is_training=True")
+    if on("train_heads") and not (is_training and on("return_readout")):
+        raise ValueError("train_heads=True needs is_training=True and return_readout=True")
+    return Switches(on("return_image_index"), on("return_batched"), on("return_readout"), on("train_heads"), on("train_detection"),
+                    train_backbone)
+
+
 class Model(nn.Module):
     """A ViT backbone followed by the HPH head and the SMPL-X layer, on hand-written gfx950 kernels."""
+    _backbone_n = 1         # blocks a train_backbone forward taps (train_backbone_)
 
     def __init__(self, backbone="dinov2_vitb14", pretrained_backbone=False, img_size=896, camera_embedding="geometric",
                  camera_embedding_num_bands=16, camera_embedding_max_resolution=64, nearness=True, xat_depth=2,
@@ -334,7 +367,7 @@ class Model(nn.Module):
                 setattr(layers[l], n, k(lt[n]))
         P["hph"] = dict(layers=layers, heads=heads, depth=depth, dim=dim, mlp=mlp, nb=nb, inner=inner, n_kv=n_kv, Ktok=Ktok,
                         Ndec=318 + nb + 13, **{n: k(ht[n]) for n in self.HEAD_TENSORS})
-        P["hph_t"], P["heads_generation"] = ht, 0
+        P["hph_t"], P["heads_generation"], P["backbone_generation"] = ht, 0, 0
         assert n_kv == 2 * inner, "xat_num_heads must be even (to_kv rows are tiled by 128)"
 
         # SMPL-X
@@ -351,7 +384,7 @@ class Model(nn.Module):
     def _head_tensors(self, device, tdt, Cc, Kc):
         """The packed copies of the head parameters: fp32, the 16-bit to_kv, the padded token embedding and the folded biases
         (tok_b = bias + pos_embedding[0, 0]; dec_b = the four read-out biases + init_*).  -> {name: tensor, "layers": [{field: tensor}]}."""
-        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        f32 = functools.partial(_f32, device=device)
         hp = self.x_attention_head
         heads, dim, nb = self.xat_num_heads, 1024, self.num_betas
         inner = 32 * heads
@@ -381,9 +414,9 @@ class Model(nn.Module):
 
     def _detect_tensors(self, device, tdt):
         """The packed copies of the ``mlp_classif`` parameters: the 16-bit first-layer weight, fp32 biases and second-layer row."""
-        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
-        return dict(cls0_w=f32(self.mlp_classif[0].weight).to(tdt).contiguous(), cls0_b=f32(self.mlp_classif[0].bias),
-                    cls2_w=f32(self.mlp_classif[2].weight.reshape(-1)), cls2_b=f32(self.mlp_classif[2].bias))
+        cls = self.mlp_classif
+        return dict(cls0_w=_f32(cls[0].weight, device).to(tdt).contiguous(), cls0_b=_f32(cls[0].bias, device),
+                    cls2_w=_f32(cls[2].weight.reshape(-1), device), cls2_b=_f32(cls[2].bias, device))
 
     def repack_heads(self):
         """Re-pack ONLY the head weights (``mlp_offset``, ``x_attention_head``, ``mlp_classif``) into the buffers the descriptors and
@@ -458,9 +491,8 @@ class Model(nn.Module):
                 return
             enc, v = self.backbone.encoder, P["vit"]
             L = len(enc.blocks)
-            f32 = lambda t: t.detach().to(device=P["device"], dtype=torch.float32).contiguous()
             with torch.no_grad():
-                for l in range(L - int(getattr(self, "_backbone_n", 1)), L):
+                for l in range(L - self._backbone_n, L):
                     new, scalars = vit.pack_block(P, enc.blocks[l], l)
                     for name, t in new.items():
                         old = v["block_t"][l][name]
@@ -469,9 +501,38 @@ class Model(nn.Module):
                             old.copy_(t)
                     for name, val in scalars.items():
                         setattr(v["blocks"][l], name, val)
-                v["norm_t"]["norm_w"].copy_(f32(enc.norm.weight))
-                v["norm_t"]["norm_b"].copy_(f32(enc.norm.bias))
-            P["backbone_generation"] = P.get("backbone_generation", 0) + 1
+                v["norm_t"]["norm_w"].copy_(_f32(enc.norm.weight, P["device"]))
+                v["norm_t"]["norm_b"].copy_(_f32(enc.norm.bias, P["device"]))
+            P["backbone_generation"] += 1
+
+    def _packed_for(self, device):
+        """The pack for this device, or pack now."""
+        P = self._packed
+        return P if P is not None and P["device"] == device else self._pack(device)
+
+    # ---- a pending backward reads the workspace of its forward and the packed weights: every rewrite of either moves a counter
+    #: pack counter a node depends on -> what its backward says when that counter, the workspace's or the pack itself has moved
+    STALE = {"heads_generation": "Model: backward must run before the next forward of the same batch size and before repack_heads() / "
+                                 "repack(): the workspace (context operand, features) or the packed head weights this forward used have "
+                                 "been overwritten since",
+             "backbone_generation": "Model: backward must run before the next forward of the same batch size and before repack_backbone() / "
+                                    "repack(): the workspace (the tapped residual streams) this forward used has been overwritten since"}
+
+    @staticmethod
+    def _overwriting(ws):
+        """The features and the context operand of ``ws`` are about to be overwritten: a backward still pending on them must raise."""
+        ws["generation"] += 1
+
+    @staticmethod
+    def _take(P, ws, counter):
+        """What an autograd node's backward depends on, as it is now: the pack, the workspace and their counters (``counter``: a key of
+        ``STALE``) -- for ``_require_current`` at backward time."""
+        return P, ws, counter, ws["generation"], P[counter]
+
+    def _require_current(self, taken):
+        P, ws, counter, ws_generation, pack_generation = taken
+        if ws["generation"] != ws_generation or P[counter] != pack_generation or self._packed is not P:
+            raise _lib.MhmrError(self.STALE[counter])
 
     @property
     def packed_precision(self):
@@ -523,7 +584,7 @@ class Model(nn.Module):
         everything enqueued after sees every block's output)."""
         L = _lib.lib()
         dev, parts, Kc, N, Cd = x.device, ws["parts"], P["Kc"], P["N"], P["C"]
-        ws["generation"] = ws.get("generation", 0) + 1      # the features and the context operand a pending train_heads backward reads are overwritten
+        self._overwriting(ws)
         main = torch.cuda.current_stream(dev)
         esz_ctx = ws["ctx16"].element_size()
         img_elems = x.shape[1] * x.shape[2] * x.shape[3]
@@ -555,7 +616,7 @@ class Model(nn.Module):
         with self._lock:                      # (workspaces belong to the instance: same lock as forward(); round-5 advisor finding)
             if train_backbone:
                 x = x.float().contiguous()
-                P, ws, stream = self._prepare(x, tap=int(getattr(self, "_backbone_n", 1)))
+                P, ws, stream = self._prepare(x, tap=self._backbone_n)
                 self._run_backbone(P, ws, x)
                 from . import backbone_train
                 return backbone_train.attach(self, P, ws, x.shape[0])
@@ -563,17 +624,18 @@ class Model(nn.Module):
             self._run_backbone(P, ws, x)
             return ws["feat32"].view(x.shape[0], P["N"], P["C"])
 
-    def _prepare(self, x, tap=0):
+    def _require_camera(self):
         if self.camera_embedding is None:
             raise AttributeError("'Model' object has no attribute 'camera' (camera_embedding=None: the reference's forward fails the same "
                                  "way at model.py:262 -> :183)")
+
+    def _prepare(self, x, tap=0):
+        self._require_camera()
         if not x.is_cuda:
             raise _lib.MhmrError("multi_hmr_amd.Model.forward runs only on an MI355X (HIP) tensor; there is no CPU fallback")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.img_size or x.shape[3] != self.img_size:
             raise ValueError(f"x must be [B,3,{self.img_size},{self.img_size}]")
-        P = self._packed
-        if P is None or P["device"] != x.device:
-            P = self._pack(x.device)
+        P = self._packed_for(x.device)
         ws = self._workspace(P, x.shape[0], tap)
         return P, ws, torch.cuda.current_stream(x.device).cuda_stream
 
@@ -599,17 +661,9 @@ class Model(nn.Module):
         n): the forward taps the residual stream in front of the last n blocks, the feature cotangent of
         ``forward_features`` carries the gradient to the features, and one node hands it to ``mhmr_vit_tail_backward``.  The same rule
         for the backward; afterwards an optimiser step and ``repack_backbone()``."""
-        if kwargs.get("train_backbone", False) and not is_training:
-            raise ValueError("train_backbone=True needs is_training=True")
-        if kwargs.get("train_detection", False) and not is_training:
-            raise ValueError("train_detection=True needs is_training=True")
-        if kwargs.get("train_heads", False) and not (is_training and kwargs.get("return_readout", False)):
-            raise ValueError("train_heads=True needs is_training=True and return_readout=True")
+        sw = call_switches(is_training, kwargs)
         with self._lock, torch.autocast("cuda", enabled=False):     # demo.forward_model wraps us in fp16 autocast (demo.py:117)
-            return self._forward(x.float().contiguous(), idx, det_thresh, nms_kernel_size, K, is_training,
-                                 bool(kwargs.get("return_image_index", False)), bool(kwargs.get("return_batched", False)),
-                                 bool(kwargs.get("return_readout", False)), bool(kwargs.get("train_heads", False)),
-                                 bool(kwargs.get("train_detection", False)), bool(kwargs.get("train_backbone", False)))
+            return self._forward(x.float().contiguous(), idx, det_thresh, nms_kernel_size, K, is_training, sw)
 
     supports_image_index = True
     supports_batched = True
@@ -640,9 +694,7 @@ class Model(nn.Module):
     def _prepare_features(self, features):
         """The checks of ``_prepare`` for a feature tensor [B, N, C] or [B N, C] -> (P, ws, stream, B, fp32 contiguous features).  A tensor
         of another float dtype is widened (and must not require grad: its gradient would be that of the rounded copy)."""
-        if self.camera_embedding is None:
-            raise AttributeError("'Model' object has no attribute 'camera' (camera_embedding=None: the reference's forward fails the same "
-                                 "way at model.py:262 -> :183)")
+        self._require_camera()
         if not isinstance(features, torch.Tensor) or not features.is_cuda:
             raise _lib.MhmrError("multi_hmr_amd.Model.forward_features runs only on an MI355X (HIP) tensor; there is no CPU fallback")
         N, Cd = (self.img_size // PATCH) ** 2, self.embed_dim
@@ -656,9 +708,7 @@ class Model(nn.Module):
         B = features.shape[0] if features.dim() == 3 else features.shape[0] // N
         if B < 1:
             raise ValueError(f"features must be a float tensor [B,{N},{Cd}] or [B*{N},{Cd}]")
-        P = self._packed
-        if P is None or P["device"] != features.device:
-            P = self._pack(features.device)
+        P = self._packed_for(features.device)
         ws = self._workspace(P, B)
         return P, ws, torch.cuda.current_stream(features.device).cuda_stream, B, features.detach().float().contiguous()
 
@@ -675,10 +725,7 @@ class Model(nn.Module):
         not ``train_heads`` / ``train_detection`` are set; ``backward()`` then fills ``features.grad`` (straight-through
         past the 16-bit roundings; once differentiable; ``K`` gets nothing).  Parameter gradients follow the rules of ``forward``.  The
         backward reads this call's workspace: it must run before the next ``forward`` / ``forward_features`` of the same batch size."""
-        if kwargs.get("train_detection", False) and not is_training:
-            raise ValueError("train_detection=True needs is_training=True")
-        if kwargs.get("train_heads", False) and not (is_training and kwargs.get("return_readout", False)):
-            raise ValueError("train_heads=True needs is_training=True and return_readout=True")
+        sw = call_switches(is_training, kwargs, from_features=True)
         with self._lock, torch.autocast("cuda", enabled=False):
             P, ws, stream, B, f32 = self._prepare_features(features)
             dev = features.device
@@ -687,37 +734,33 @@ class Model(nn.Module):
             self._features_in(P, ws, f32, B, stream)
             self._front_heads(P, ws, B, K, stream)
             leaf = features if (is_training and features.requires_grad) else None
-            return self._behind_front(P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training,
-                                      bool(kwargs.get("return_image_index", False)), bool(kwargs.get("return_batched", False)),
-                                      bool(kwargs.get("return_readout", False)), bool(kwargs.get("train_heads", False)),
-                                      bool(kwargs.get("train_detection", False)), leaf)
+            return self._behind_front(P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, sw, leaf)
 
     def _features_in(self, P, ws, f32, B, stream):
         """Step 1 of the forward with the features given: ws["feat32"] = features (no copy when they ARE that buffer) and the context
         operand's feature columns = their 16-bit rounding, as the backbone's final norm leaves both."""
-        ws["generation"] = ws.get("generation", 0) + 1      # as _run_backbone: a pending backward's features and context are overwritten
+        self._overwriting(ws)
         _lib.check(_lib.lib().mhmr_features_to_context(f32.data_ptr(), ws["feat32"].data_ptr(), ws["ctx16"].data_ptr(), P["Kc"], B * P["N"],
                                                        P["C"], P["dt_id"], stream), "mhmr_features_to_context")
 
-    def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, with_ids=False, batched=False, with_readout=False,
-                 train_heads=False, train_detection=False, train_backbone=False):
-        P, ws, stream = self._prepare(x, tap=int(getattr(self, "_backbone_n", 1)) if train_backbone else 0)
+    def _forward(self, x, idx, det_thresh, nms_kernel_size, K, is_training, sw):
+        P, ws, stream = self._prepare(x, tap=self._backbone_n if sw.train_backbone else 0)
         dev, B = x.device, x.shape[0]
         K = K.to(device=dev, dtype=torch.float32).contiguous()
         assert K.shape == (B, 3, 3)
 
         self._front(P, ws, x, K, stream)
         features = None
-        if train_backbone:          # the features as a tensor attached to the backbone parameters: the route of forward_features from here on
+        if sw.train_backbone:       # the features as a tensor attached to the backbone parameters: the route of forward_features from here on
             from . import backbone_train
             features = backbone_train.attach(self, P, ws, B)
-        return self._behind_front(P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, with_ids, batched, with_readout,
-                                  train_heads, train_detection, features)
+        return self._behind_front(P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, sw, features)
 
-    def _behind_front(self, P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, with_ids, batched, with_readout,
-                      train_heads, train_detection, features):
-        """Everything behind steps 1-3 (shared by ``forward`` and ``forward_features``).  ``features``: the caller's feature tensor when the
-        outputs are to be attached to autograd with respect to it (training mode, ``requires_grad``), else None."""
+    def _behind_front(self, P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, sw, features):
+        """Everything behind steps 1-3 (shared by ``forward`` and ``forward_features``).  ``sw``: the call's ``Switches``.  ``features``: the
+        caller's feature tensor when the outputs are to be attached to autograd with respect to it (training mode, ``requires_grad``), else
+        None."""
+        with_ids, batched, with_readout, train_heads, train_detection = sw[:5]
         L = _lib.lib()
         G = P["G"]
         scores = ws["scores"].view(B, G, G, 1)
@@ -731,8 +774,8 @@ class Model(nn.Module):
             attach_heads = train_heads or (features is not None and with_readout)
             if train_detection or features is not None:
                 from . import detect_train
-                out["scores"] = detect_train.attach(self, dict(P=P, ws=ws, dev=dev, rows=B * P["N"], generation=ws["generation"],
-                                                               heads_generation=P["heads_generation"], scores=out["scores"]),
+                out["scores"] = detect_train.attach(self, dict(P=P, ws=ws, dev=dev, rows=B * P["N"], scores=out["scores"],
+                                                               taken=self._take(P, ws, "heads_generation")),
                                                     features=features, with_params=train_detection)
             if Pn == 0:
                 if with_readout:
@@ -754,8 +797,8 @@ class Model(nn.Module):
                 out["readout"] = keep["dec"][:, :318 + P["hph"]["nb"] + 13].contiguous()
             if attach_heads:
                 from . import heads_train
-                st = dict(P=P, ws=ws, dev=dev, Pn=Pn, B=B, generation=ws["generation"], heads_generation=P["heads_generation"],
-                          desc=keep["desc"], wsp=keep["wsp"], det=det, gstart=gstart_t, chunks=chunks_t, ngc=ngc, ncc=ncc,
+                st = dict(P=P, ws=ws, dev=dev, Pn=Pn, B=B, taken=self._take(P, ws, "heads_generation"), desc=keep["desc"],
+                          wsp=keep["wsp"], det=det, gstart=gstart_t, chunks=chunks_t, ngc=ngc, ncc=ncc,
                           readout=out["readout"], offset=out["offset"].clone())
                 out["readout"], out["offset"] = heads_train.attach(self, st, features=features, with_params=train_heads)
             return out
@@ -864,16 +907,18 @@ class Model(nn.Module):
                      ("dist_postprocessed", (1,)), ("dist", (1,)), ("v3d", None), ("v2d", None), ("j3d", (127, 3)), ("j2d", (127, 2)),
                      ("transl", (3,)), ("scores", ()))
 
+    def _output_shapes(self, P):
+        """``OUTPUT_SHAPES`` with the trailing shapes that depend on the pack filled in -> [(name, shape)]."""
+        var = {"shape": (P["hph"]["nb"],), "v3d": (P["lbs"]["V"], 3), "v2d": (P["lbs"]["V"], 2)}
+        return [(name, var[name] if shp is None else shp) for name, shp in self.OUTPUT_SHAPES]
+
     def _alloc_outputs(self, P, Pn, dev, flat=None):
         """The output tensors of the heads for Pn person rows (views of them are what forward returns), carved out of ONE allocation
         (``o["_flat"]``, every tensor 256-byte aligned): one allocator call per forward instead of fourteen, and a consumer that has to
         keep the results past the next forward of a recorded graph copies one buffer (graphed.GraphedForward).  ``flat``: build the views
         on an existing buffer of the same layout (such a copy)."""
-        nb, V = P["hph"]["nb"], P["lbs"]["V"]
-        var = {"shape": (nb,), "v3d": (V, 3), "v2d": (V, 2)}
         off, lay = 0, []
-        for name, shp in self.OUTPUT_SHAPES:
-            shp = var[name] if shp is None else shp
+        for name, shp in self._output_shapes(P):
             n = Pn * int(np.prod(shp, dtype=np.int64))
             lay.append((name, shp, off, n))
             off += -(-n // 64) * 64
@@ -900,7 +945,7 @@ class Model(nn.Module):
         d.dim, d.heads, d.mlp, d.depth, d.nb, d.Ktok, d.Ndec = h["dim"], h["heads"], h["mlp"], h["depth"], h["nb"], h["Ktok"], h["Ndec"]
         d.patch, d.nearness = PATCH, int(bool(self.nearness))
         d.fn = float(self.img_size / (2 * np.tan(np.radians(self.fovn) / 2)))
-        for n in ("off1_w", "off1_b", "off2_w", "off2_b", "cq_x", "cq_y", "cv_x", "cv_y", "init_tail", "tok_w", "tok_b", "dec_w", "dec_b"):
+        for n in self.HEAD_TENSORS:
             setattr(d, n, h[n])
         d.layers = C.cast(h["layers"], C.POINTER(_lib.HphLayer))
         for n, t in wsp.items():
@@ -921,13 +966,15 @@ class Model(nn.Module):
                                       chunks_t.data_ptr(), ncc, K.data_ptr(), B, offset.data_ptr(), loc.data_ptr(),
                                       rotmat.data_ptr(), rotvec.data_ptr(), shape.data_ptr(), expression.data_ptr(), dist_pp.data_ptr(),
                                       dist.data_ptr(), stream), "mhmr_hph_forward")
-        lb = P["lbs"]
-        V = lb["V"]
-        v3d, v2d, j3d, j2d, transl = o["v3d"], o["v2d"], o["j3d"], o["j2d"], o["transl"]
-        ws_F, ws_A, ws_xf = f(roundup(Pn, 16), lb["Kb"]), f(roundup(Pn, 16), 768), f(Pn, 24)
-        # pose kernel + vertex kernel (csrc/lbs.hip)
-        args = [C.byref(P["lbs_struct"]), rotvec.data_ptr(), shape.data_ptr(), expression.data_ptr(), loc.data_ptr(), dist.data_ptr(), K.data_ptr(),
-                det[0].data_ptr(), Pn, ws_F.data_ptr(), ws_A.data_ptr(), ws_xf.data_ptr(), v3d.data_ptr(), v2d.data_ptr(), j3d.data_ptr(), j2d.data_ptr(),
-                transl.data_ptr()]
-        _lib.check(L.mhmr_lbs_forward(*args, stream), "mhmr_lbs_forward")
+        self._lbs(P, o, K, det[0], Pn, stream)
         return o
+
+    def _lbs(self, P, o, K, det_b, Pn, stream):
+        """The SMPL-X layer (pose kernel + vertex kernel, csrc/lbs.hip) for Pn person rows: from ``o``'s rotvec, shape, expression, loc and
+        dist to its v3d, v2d, j3d, j2d and transl.  Allocates the three scratch tensors."""
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=K.device)
+        ws_F, ws_A, ws_xf = f(roundup(Pn, 16), P["lbs"]["Kb"]), f(roundup(Pn, 16), 768), f(Pn, 24)
+        ptrs = lambda *names: [o[n].data_ptr() for n in names]
+        _lib.check(_lib.lib().mhmr_lbs_forward(C.byref(P["lbs_struct"]), *ptrs("rotvec", "shape", "expression", "loc", "dist"), K.data_ptr(),
+                                               det_b.data_ptr(), Pn, ws_F.data_ptr(), ws_A.data_ptr(), ws_xf.data_ptr(),
+                                               *ptrs("v3d", "v2d", "j3d", "j2d", "transl"), stream), "mhmr_lbs_forward")

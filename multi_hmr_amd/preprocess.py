@@ -167,63 +167,73 @@ class Preprocessor:
         calls on one Preprocessor must all use the same stream (the staging buffers are reused in stream order).  The plan of every
         source size met stays cached (tables of a few KB and the one-image ``tmp`` of ``__call__``, rows x ow x 3 bytes): an endless
         stream of ever new sizes grows that cache; use a new Preprocessor per source, or clear ``_tables``, there."""
-        B, S = len(images), self.S
+        B = len(images)
         if B == 0 or B > 65535:
             raise ValueError("expected 1 ... 65535 images")
         for img in images:
             if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
                 raise ValueError("expected a uint8 [H, W, 3] RGB image")
-        dev = self.lut.device                              # with its index: self.device may be a bare "cuda"
         with self._batch_lock:
-            plans = [self._plan(int(img.shape[0]), int(img.shape[1])) for img in images]
-            if out is None:
-                out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-            if not (out.is_contiguous() and out.numel() == B * 3 * S * S and out.dtype == torch.float32 and out.device == dev):
-                raise ValueError(f"out must be a contiguous float32 tensor of {B} x 3 x {S} x {S} elements on {dev}")
-            up = lambda n: -(-n // 256) * 256
-            # layout of the staging buffer: [B descriptors][host image 0][host image 1] ...; of the workspace: [tmp 0][tmp 1] ...
-            off, img_off, tmp_off, tmp_bytes = up(B * ctypes.sizeof(_lib.PreImage)), [], [], 0
-            for img, t in zip(images, plans):
-                img_off.append(None if img.is_cuda else off)
-                if not img.is_cuda:
-                    off += up(img.numel())
-                tmp_off.append(tmp_bytes)
-                tmp_bytes += up(t["rows"] * t["ow"] * 3)
-            slot = self._pinned[self._turn]
-            self._turn ^= 1
-            if slot[1] is not None:
-                slot[1].synchronize()                      # the copy out of this buffer two calls ago
-            if slot[0] is None or slot[0].numel() < off:
-                slot[0] = torch.empty(off + off // 4, dtype=torch.uint8, pin_memory=True)
-            if self._staging is None or self._staging.numel() < off:
-                self._staging = torch.empty(off + off // 4, dtype=torch.uint8, device=dev)
-            if self._tmp is None or self._tmp.numel() < tmp_bytes:
-                self._tmp = torch.empty(tmp_bytes + tmp_bytes // 4, dtype=torch.uint8, device=dev)
-            pin, staging = slot[0], self._staging
-            desc, keep = (_lib.PreImage * B)(), []
-            for b, (img, t) in enumerate(zip(images, plans)):
-                d, H, W = desc[b], int(img.shape[0]), int(img.shape[1])
-                if img.is_cuda:
-                    img = img.to(dev).contiguous()
-                    keep.append(img)
-                    d.img = img.data_ptr()
-                else:
-                    pin[img_off[b]:img_off[b] + img.numel()].view(H, W, 3).copy_(img)
-                    d.img = staging.data_ptr() + img_off[b]
-                d.H, d.W, d.ow, d.oh, d.y0, d.rows, d.pad_x, d.pad_y, d.ksh, d.ksv = (H, W, t["ow"], t["oh"], t["y0"], t["rows"], t["px"],
-                                                                                     t["py"], t["ksh"], t["ksv"])
-                d.kh, d.bh, d.kv, d.bv = t["kh"].data_ptr(), t["bh"].data_ptr(), t["kv"].data_ptr(), t["bv"].data_ptr()
-                d.tmp = self._tmp.data_ptr() + tmp_off[b]
-            pin[:ctypes.sizeof(desc)].copy_(torch.frombuffer(desc, dtype=torch.uint8))
-            with torch.cuda.device(dev):
-                staging[:off].copy_(pin[:off], non_blocking=True)
-                if slot[1] is None:
-                    slot[1] = torch.cuda.Event()
-                slot[1].record()
-                st = torch.cuda.current_stream(dev).cuda_stream
-                _lib.check(_lib.lib().mhmr_preprocess_u8_batch(desc, staging.data_ptr(), B, S, self.lut.data_ptr(), out.data_ptr(), st),
-                           "mhmr_preprocess_u8_batch")
-            del keep                                       # device inputs made contiguous here: freed in stream order, after the kernels
+            return self._stage(images, None, out)
+
+    def _stage(self, images, orient, out):
+        """What ``batch`` (``orient`` None: ``PreImage`` descriptors, ``mhmr_preprocess_u8_batch``) and ``batch_oriented`` (``PreImageO``,
+        ``mhmr_preprocess_u8_batch_oriented``) share: plans, staging layout, the pinned buffers used in turn, descriptors, the one copy
+        and the launch.  The caller holds ``_batch_lock`` and has checked ``images`` and ``orient``."""
+        B, S, dev = len(images), self.S, self.lut.device     # (the device with its index: self.device may be a bare "cuda")
+        Desc, entry = (_lib.PreImage, "mhmr_preprocess_u8_batch") if orient is None else (_lib.PreImageO, "mhmr_preprocess_u8_batch_oriented")
+        # the plan is keyed by (H, W) of the ORIENTED image: a rotated source's rows are the stored columns
+        rot = [False] * B if orient is None else [bool(o & _lib.ORIENT_ROT90) for o in orient]
+        plans = [self._plan(*((int(img.shape[1]), int(img.shape[0])) if r else (int(img.shape[0]), int(img.shape[1])))) for img, r in zip(images, rot)]
+        if out is None:
+            out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+        if not (out.is_contiguous() and out.numel() == B * 3 * S * S and out.dtype == torch.float32 and out.device == dev):
+            raise ValueError(f"out must be a contiguous float32 tensor of {B} x 3 x {S} x {S} elements on {dev}")
+        up = lambda n: -(-n // 256) * 256
+        # layout of the staging buffer: [B descriptors][host image 0][host image 1] ...; of the workspace: [tmp 0][tmp 1] ...
+        off, img_off, tmp_off, tmp_bytes = up(B * ctypes.sizeof(Desc)), [], [], 0
+        for img, t in zip(images, plans):
+            img_off.append(None if img.is_cuda else off)
+            if not img.is_cuda:
+                off += up(img.numel())
+            tmp_off.append(tmp_bytes)
+            tmp_bytes += up(t["rows"] * t["ow"] * 3)
+        slot = self._pinned[self._turn]
+        self._turn ^= 1
+        if slot[1] is not None:
+            slot[1].synchronize()                      # the copy out of this buffer two calls ago
+        if slot[0] is None or slot[0].numel() < off:
+            slot[0] = torch.empty(off + off // 4, dtype=torch.uint8, pin_memory=True)
+        if self._staging is None or self._staging.numel() < off:
+            self._staging = torch.empty(off + off // 4, dtype=torch.uint8, device=dev)
+        if self._tmp is None or self._tmp.numel() < tmp_bytes:
+            self._tmp = torch.empty(tmp_bytes + tmp_bytes // 4, dtype=torch.uint8, device=dev)
+        pin, staging = slot[0], self._staging
+        desc, keep = (Desc * B)(), []
+        for b, (img, t) in enumerate(zip(images, plans)):
+            d, H, W = desc[b], int(img.shape[0]), int(img.shape[1])
+            if img.is_cuda:
+                img = img.to(dev).contiguous()
+                keep.append(img)
+                d.img = img.data_ptr()
+            else:
+                pin[img_off[b]:img_off[b] + img.numel()].view(H, W, 3).copy_(img)
+                d.img = staging.data_ptr() + img_off[b]
+            d.H, d.W, d.ow, d.oh, d.y0, d.rows, d.pad_x, d.pad_y, d.ksh, d.ksv = (H, W, t["ow"], t["oh"], t["y0"], t["rows"], t["px"],
+                                                                                 t["py"], t["ksh"], t["ksv"])
+            d.kh, d.bh, d.kv, d.bv = t["kh"].data_ptr(), t["bh"].data_ptr(), t["kv"].data_ptr(), t["bv"].data_ptr()
+            d.tmp = self._tmp.data_ptr() + tmp_off[b]
+            if orient is not None:
+                d.orient = orient[b]
+        pin[:ctypes.sizeof(desc)].copy_(torch.frombuffer(desc, dtype=torch.uint8))
+        with torch.cuda.device(dev):
+            staging[:off].copy_(pin[:off], non_blocking=True)
+            if slot[1] is None:
+                slot[1] = torch.cuda.Event()
+            slot[1].record()
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(getattr(_lib.lib(), entry)(desc, staging.data_ptr(), B, S, self.lut.data_ptr(), out.data_ptr(), st), entry)
+        del keep                                       # device inputs made contiguous here: freed in stream order, after the kernels
         return out.view(B, 3, S, S)
 
     def batch_oriented(self, images, orient, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -232,7 +242,7 @@ class Preprocessor:
         after the rotation.  Image b is bit-identical to ``batch`` on the oriented copy of ``images[b]``, but no such copy is made: one
         ``mhmr_preprocess_u8_batch_oriented`` call reads the stored pixels through the permutation.  Inputs (host, device or mixed),
         staging, stream rules and the plan cache are those of ``batch``; the plan of an image is keyed by its ORIENTED size."""
-        B, S = len(images), self.S
+        B = len(images)
         orient = [int(o) for o in orient]
         if B == 0 or B > 65535 or len(orient) != B:
             raise ValueError("expected 1 ... 65535 images and one orient code per image")
@@ -241,60 +251,8 @@ class Preprocessor:
                 raise ValueError("expected a uint8 [H, W, 3] RGB image")
             if o & ~(_lib.ORIENT_MIRROR | _lib.ORIENT_ROT90):
                 raise ValueError("orient: bit 0 = mirror, bit 1 = rotate by 90 degrees clockwise")
-        dev = self.lut.device
         with self._batch_lock:
-            # (H, W) of the oriented image: a rotated source's rows are the stored columns
-            plans = [self._plan(*((int(img.shape[1]), int(img.shape[0])) if o & _lib.ORIENT_ROT90 else (int(img.shape[0]), int(img.shape[1]))))
-                     for img, o in zip(images, orient)]
-            if out is None:
-                out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-            if not (out.is_contiguous() and out.numel() == B * 3 * S * S and out.dtype == torch.float32 and out.device == dev):
-                raise ValueError(f"out must be a contiguous float32 tensor of {B} x 3 x {S} x {S} elements on {dev}")
-            up = lambda n: -(-n // 256) * 256
-            off, img_off, tmp_off, tmp_bytes = up(B * ctypes.sizeof(_lib.PreImageO)), [], [], 0
-            for img, t in zip(images, plans):
-                img_off.append(None if img.is_cuda else off)
-                if not img.is_cuda:
-                    off += up(img.numel())
-                tmp_off.append(tmp_bytes)
-                tmp_bytes += up(t["rows"] * t["ow"] * 3)
-            slot = self._pinned[self._turn]
-            self._turn ^= 1
-            if slot[1] is not None:
-                slot[1].synchronize()
-            if slot[0] is None or slot[0].numel() < off:
-                slot[0] = torch.empty(off + off // 4, dtype=torch.uint8, pin_memory=True)
-            if self._staging is None or self._staging.numel() < off:
-                self._staging = torch.empty(off + off // 4, dtype=torch.uint8, device=dev)
-            if self._tmp is None or self._tmp.numel() < tmp_bytes:
-                self._tmp = torch.empty(tmp_bytes + tmp_bytes // 4, dtype=torch.uint8, device=dev)
-            pin, staging = slot[0], self._staging
-            desc, keep = (_lib.PreImageO * B)(), []
-            for b, (img, t) in enumerate(zip(images, plans)):
-                d, H, W = desc[b], int(img.shape[0]), int(img.shape[1])
-                if img.is_cuda:
-                    img = img.to(dev).contiguous()
-                    keep.append(img)
-                    d.img = img.data_ptr()
-                else:
-                    pin[img_off[b]:img_off[b] + img.numel()].view(H, W, 3).copy_(img)
-                    d.img = staging.data_ptr() + img_off[b]
-                d.H, d.W, d.ow, d.oh, d.y0, d.rows, d.pad_x, d.pad_y, d.ksh, d.ksv = (H, W, t["ow"], t["oh"], t["y0"], t["rows"], t["px"],
-                                                                                     t["py"], t["ksh"], t["ksv"])
-                d.kh, d.bh, d.kv, d.bv = t["kh"].data_ptr(), t["bh"].data_ptr(), t["kv"].data_ptr(), t["bv"].data_ptr()
-                d.tmp = self._tmp.data_ptr() + tmp_off[b]
-                d.orient = orient[b]
-            pin[:ctypes.sizeof(desc)].copy_(torch.frombuffer(desc, dtype=torch.uint8))
-            with torch.cuda.device(dev):
-                staging[:off].copy_(pin[:off], non_blocking=True)
-                if slot[1] is None:
-                    slot[1] = torch.cuda.Event()
-                slot[1].record()
-                st = torch.cuda.current_stream(dev).cuda_stream
-                _lib.check(_lib.lib().mhmr_preprocess_u8_batch_oriented(desc, staging.data_ptr(), B, S, self.lut.data_ptr(), out.data_ptr(), st),
-                           "mhmr_preprocess_u8_batch_oriented")
-            del keep
-        return out.view(B, 3, S, S)
+            return self._stage(images, orient, out)
 
 
 _PRE = {}

@@ -140,13 +140,11 @@ def _render(images_u8, verts, image_index, K, faces, colors, alpha, Rt, nviews, 
     d.key_out, d.rgb_out = _lib.ptr(key), _lib.ptr(rgb)
     L = _lib.lib()
     if nviews is None:
-        nbytes, what = L.mhmr_render_workspace_bytes(C.byref(d)), "mhmr_render_workspace_bytes"
+        nbytes = _lib.workspace_bytes("mhmr_render_workspace_bytes", C.byref(d))
     else:
-        nbytes, what = L.mhmr_render_views_workspace_bytes(C.byref(d), nviews), "mhmr_render_views_workspace_bytes"
-    if nbytes < 0:
-        _lib.check(int(nbytes), what)
+        nbytes = _lib.workspace_bytes("mhmr_render_views_workspace_bytes", C.byref(d), nviews)
     with torch.cuda.device(dev):
-        ws = _workspace(int(nbytes), dev)
+        ws = _workspace(nbytes, dev)
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
         stream = torch.cuda.current_stream(dev).cuda_stream
         if nviews is None:

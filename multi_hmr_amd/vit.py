@@ -439,5 +439,6 @@ class WorkspaceCache:
         ws["feat32"] = z(B * N, Cd, dtype=torch.float32)
         ws.update(extra(P, B, z))
         ws["parts"], ws["vit_desc"], ws["Tp"], ws["tap_blocks"] = parts, parts[0]["desc"], Tp, tap
+        ws["generation"] = 0           # moved by whatever overwrites the features and the context operand (model.Model._overwriting)
         self._ws[key] = ws
         return ws

@@ -83,6 +83,27 @@ def test_the_output_and_every_tmp_slice_sit_between_sentinels():
     assert off <= tmp.size and (tmp[off:] == 0xA5).all()
 
 
+def test_batch_and_batch_oriented_in_turn_share_the_staging_buffers():
+    """The two methods stage through the same pinned buffers, device copy and tmp workspace, with descriptors of different sizes -- so the
+    image offsets differ from call to call.  Four calls back to back on one Preprocessor, no synchronisation in between: each result is
+    bit-equal to the same call on a Preprocessor of its own."""
+    S = 56
+    host = [torch.from_numpy(do.make_image(H, W, seed=7 + j)) for j, (W, H) in enumerate([(37, 53), (64, 48), (50, 50)])]
+    a, b, c = host
+    calls = [(None, [a, b.cuda(), c]),                       # batch, B = 3, mixed
+             ([2, 1], [a.cuda(), b]),                        # batch_oriented, B = 2, mixed
+             (None, [c]),                                    # batch, B = 1: the pinned buffer of the first call again
+             ([3, 0, 2], [a, b, c.cuda()])]                  # batch_oriented, B = 3, mixed
+
+    def run(pre, orient, imgs):
+        return pre.batch(imgs) if orient is None else pre.batch_oriented(imgs, orient)
+    shared = pp.Preprocessor(S, DEV)
+    got = [run(shared, orient, imgs) for orient, imgs in calls]
+    for j, (orient, imgs) in enumerate(calls):
+        want = run(pp.Preprocessor(S, DEV), orient, imgs)
+        assert got[j].shape == (len(imgs), 3, S, S) and torch.equal(got[j], want), (j, orient)
+
+
 # ------------------------------------------------------------------------------------------------------- end to end
 def _assert_y(got, want):
     assert set(got) == set(want)

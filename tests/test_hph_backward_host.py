@@ -278,6 +278,45 @@ def test_head_parameter_names_are_the_models_head_parameters():
     m.repack_heads()                                  # nothing packed yet: a no-op
 
 
+def test_workspace_bytes_returns_the_count_and_raises_on_an_error_code(L):
+    """_lib.workspace_bytes: the values tests/test_heads_backward_host.py asserts on the raw entry."""
+    assert _lib.workspace_bytes("mhmr_heads_place_workspace_bytes", 10475, 127, 3) == 3 * 12 * 24
+    assert _lib.workspace_bytes("mhmr_heads_place_workspace_bytes", 10475, 127, 0) == 0
+    with pytest.raises(_lib.MhmrError, match="mhmr_heads_place_workspace_bytes failed: bad argument"):
+        _lib.workspace_bytes("mhmr_heads_place_workspace_bytes", 0, 127, 1)
+
+
+def test_call_switches():
+    """model.call_switches: one record of what a forward call's keywords ask for; no device, no model."""
+    from multi_hmr_amd.model import Switches, call_switches
+    off = Switches(False, False, False, False, False, False)
+    assert call_switches(False, {}) == off and call_switches(True, {}, from_features=True) == off
+    assert Switches._fields == ("with_ids", "batched", "with_readout", "train_heads", "train_detection", "train_backbone")
+    every = dict(return_image_index=1, return_batched=True, return_readout=True, train_heads=True, train_detection=True, train_backbone=True)
+    assert call_switches(True, every) == Switches(True, True, True, True, True, True)
+    assert all(type(v) is bool for v in call_switches(True, every))
+    assert call_switches(False, dict(return_batched=True, return_image_index=True)) == off._replace(with_ids=True, batched=True)
+    with pytest.raises(AttributeError):
+        call_switches(True, every).train_heads = False                       # immutable
+    # the three invalid combinations, for both callers where both read the switch
+    for ff in (False, True):
+        with pytest.raises(ValueError, match="^train_detection=True needs is_training=True$"):
+            call_switches(False, dict(train_detection=True), from_features=ff)
+        for kw in (dict(train_heads=True), dict(train_heads=True, return_readout=True)):
+            with pytest.raises(ValueError, match="^train_heads=True needs is_training=True and return_readout=True$"):
+                call_switches(False, kw, from_features=ff)
+        with pytest.raises(ValueError, match="^train_heads=True needs is_training=True and return_readout=True$"):
+            call_switches(True, dict(train_heads=True), from_features=ff)
+    with pytest.raises(ValueError, match="^train_backbone=True needs is_training=True$"):
+        call_switches(False, dict(train_backbone=True))
+    # forward_features has no backbone to train: the keyword is not read there, in either mode
+    assert call_switches(False, dict(train_backbone=True), from_features=True) == off
+    assert call_switches(True, dict(train_backbone=True, train_detection=True), from_features=True) == off._replace(train_detection=True)
+    assert call_switches(True, dict(train_backbone=True)) == off._replace(train_backbone=True)
+    # keywords that are none of ours are ignored, as the reference's *args, **kwargs ignores them
+    assert call_switches(False, dict(verbose=True, return_readout=True, train_everything=True)) == off._replace(with_readout=True)
+
+
 # ------------------------------------------------------------------------------------------------------ the oracle itself
 def _fd_check(f, leaves, grads, seed, tag):
     """Central differences of the fp64 scalar f(leaves) along four seeded directions against <grads, direction>; gate 1e-6 relative."""
