@@ -14,7 +14,8 @@ namespace {
 
 // ------------------------------------------------------------------------------------------------------------
 // Y[m][n] = act( sum_k X[row(m)][k] * W[n][k] + bias[n] ) (+ R[m][n]);  K % 16 == 0 (callers pad with zeros).
-// One wave = 16 (m) x 32 (n); block = 4 waves along n = 16 x 128.
+// One wave = 16 (m) x 32 (n); block = 4 waves along n = 16 x 128.  The sum over k is one MFMA chain per 256 k, the chains added up in
+// two further levels (hph_shared.h): the heads reach this form with K < 256 or thousands of persons, the ViT tape (vit_bwd.hip) with K = 1024 and 4096.
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict__ X, int ldx, const int* __restrict__ row_idx,
                                                          const float* __restrict__ W, int ldw, const float* __restrict__ bias,
@@ -29,17 +30,26 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
     const float* xp = X + (size_t)mrow * ldx + 4 * g;
     const float* wp0 = W + (size_t)min(n0 + l15, N - 1) * ldw + 4 * g;
     const float* wp1 = W + (size_t)min(n0 + 16 + l15, N - 1) * ldw + 4 * g;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    // a blocked chain over k (BlockedSum2 of hph_shared.h): up to K = 256 the single chain bit for bit; the ViT tape runs K = 1024 and 4096
+    BlockedSum2 sum;
+    for (int k2 = 0; k2 < K; k2 += BLOCKED_SUM_L1 * BLOCKED_SUM_L2) {
+        const int k2end = min(K, k2 + BLOCKED_SUM_L1 * BLOCKED_SUM_L2);
+        for (int k1 = k2; k1 < k2end; k1 += BLOCKED_SUM_L1) {
+            const int k1end = min(K, k1 + BLOCKED_SUM_L1);
 #pragma unroll 4
-    for (int k = 0; k < K; k += 16) {
-        const f32x4 xa = *(const f32x4*)(xp + k);
-        const f32x4 w0 = *(const f32x4*)(wp0 + k);
-        const f32x4 w1 = *(const f32x4*)(wp1 + k);
+            for (int k = k1; k < k1end; k += 16) {
+                const f32x4 xa = *(const f32x4*)(xp + k);
+                const f32x4 w0 = *(const f32x4*)(wp0 + k);
+                const f32x4 w1 = *(const f32x4*)(wp1 + k);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], w0[e], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], w1[e], acc1, 0, 0, 0);
+                for (int e = 0; e < 4; ++e) {
+                    sum.acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], w0[e], sum.acc0, 0, 0, 0);
+                    sum.acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], w1[e], sum.acc1, 0, 0, 0);
+                }
+            }
+            sum.flush1();
         }
+        sum.flush2();
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -50,7 +60,7 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
         for (int r = 0; r < 4; ++r) {
             const int m = m0 + 4 * g + r;
             if (m >= M) continue;
-            float v = (t == 0 ? acc0[r] : acc1[r]) + bv;
+            float v = (t == 0 ? sum.top0[r] : sum.top1[r]) + bv;
             if (act == MHMR_ACT_RELU) v = fmaxf(v, 0.f);
             else if (act == MHMR_ACT_GELU) v = gelu_erf(v);
             if (R) v += R[(size_t)m * ldr + n];
@@ -429,6 +439,7 @@ __global__ void loc_kernel(const float* __restrict__ offset, const int* __restri
 int mhmr_launch_linear_f32(const float* X, int ldx, const int* row_idx, const float* W, int ldw, const float* bias,
                            const float* R, int ldr, float* Y, int ldy, int M, int N, int K, int act, hipStream_t s) {
     if (M <= 0 || N <= 0 || K <= 0 || K % 16 || ldx % 4 || ldw % 4) return MHMR_ERR_BAD_SHAPE;
+    if (M > 16 * 65535) return MHMR_ERR_BAD_SHAPE;                               // the row tiles of 16 are gridDim.y of both forms
     if (K >= 256 && (long long)((N + 127) / 128) * ((M + 15) / 16) < 1024)       // few tiles, long k: split k over the waves
         hipLaunchKernelGGL(linear_f32_splitk_kernel, dim3((N + 31) / 32, (M + 15) / 16), dim3(256), 0, s, X, ldx, row_idx, W, ldw,
                            bias, R, ldr, Y, ldy, M, N, K, act);

@@ -8,7 +8,9 @@
 //
 //   linear, input side    dX[m][k] = sum_n dZ[row(m)][n] W[n][k] (+ dR[m][k]),  dZ = dY * act'(Z)       (Z = TAPED pre-activation);
 //                         the n range split over the four waves of a workgroup, partial sums added in wave order
-//   linear, weight side   dW[n][k] = sum_m dZ[m][n] X[m][k]  (MFMA chain over m, zero-padded to a multiple of 4),  db[n] = fp64 sum
+//   linear, weight side   dW[n][k] = sum_m dZ[m][n] X[m][k]  (MFMA chain over m, zero-padded to a multiple of 4, blocked: one chain per
+//                         256 rows, added up in two further levels -- the rows are persons here and B Tp token rows in vit_bwd.hip),
+//                         db[n] = fp64 sum
 //   LayerNorm             dx one wave per row (+ dR: the residual stream's cotangent); d gamma, d beta: fp64, two fixed stages
 //   self-attention        (q) lane = query: lse, D = dO . O, dq;  (kv) lane = key: dK, dV over the group's queries in index order
 //   cross-attention       (a) lse and D per (query, head), (b) dq with the forward's lane / wave split of the keys, (c) dkv with
@@ -93,8 +95,11 @@ __global__ __launch_bounds__(256) void linear_bwd_input_kernel(const float* __re
     }
 }
 
-// Linear backward, weight side.  One wave = 16 (n) x 32 (k); block = 4 waves along k.  The chain runs over the persons in index order,
-// four per MFMA (lane group g takes person m + g; persons >= M contribute an exact zero).
+// Linear backward, weight side.  One wave = 16 (n) x 32 (k); block = 4 waves along k.  The sum runs over the rows m (persons in the
+// heads, B Tp token rows in the backbone blocks) in index order, four per MFMA (lane group g takes row m + g; rows >= M contribute an
+// exact zero), as a blocked chain (BlockedSum2 of hph_shared.h): one MFMA chain per 256 rows, flushed into a second accumulator, and that into a third
+// every 4096 rows.  Up to 256 rows this is the single chain, bit for bit; a single chain over all rows is good to a few hundred rows only
+// (measured against fp32 CPU torch: 1.9x its relative L2 error at 640 rows, 4.5x at 4 160, 12x at 133 120).
 __global__ __launch_bounds__(256) void linear_bwd_weight_kernel(const float* __restrict__ dY, int lddy, const float* __restrict__ Z, int ldz,
                                                                 const float* __restrict__ X, int ldx, float* __restrict__ dW, int lddw,
                                                                 int M, int N, int K, int act) {
@@ -104,16 +109,24 @@ __global__ __launch_bounds__(256) void linear_bwd_weight_kernel(const float* __r
     if (k0 >= K) return;
     const int na = min(n0 + l15, N - 1);
     const int kc0 = min(k0 + l15, K - 1), kc1 = min(k0 + 16 + l15, K - 1);
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    BlockedSum2 sum;
+    for (int m2 = 0; m2 < M; m2 += BLOCKED_SUM_L1 * BLOCKED_SUM_L2) {
+        const int m2end = min(M, m2 + BLOCKED_SUM_L1 * BLOCKED_SUM_L2);
+        for (int m1 = m2; m1 < m2end; m1 += BLOCKED_SUM_L1) {
+            const int m1end = min(M, m1 + BLOCKED_SUM_L1);
 #pragma unroll 4
-    for (int m = 0; m < M; m += 4) {
-        const int mm = m + g, mc = min(mm, M - 1);
-        float a = dY[(size_t)mc * lddy + na];
-        if (Z) a *= dact(Z[(size_t)mc * ldz + na], act);
-        if (mm >= M) a = 0.f;
-        const float* xp = X + (size_t)mc * ldx;
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xp[kc0], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xp[kc1], acc1, 0, 0, 0);
+            for (int m = m1; m < m1end; m += 4) {
+                const int mm = m + g, mc = min(mm, M - 1);
+                float a = dY[(size_t)mc * lddy + na];
+                if (Z) a *= dact(Z[(size_t)mc * ldz + na], act);
+                if (mm >= M) a = 0.f;
+                const float* xp = X + (size_t)mc * ldx;
+                sum.acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xp[kc0], sum.acc0, 0, 0, 0);
+                sum.acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xp[kc1], sum.acc1, 0, 0, 0);
+            }
+            sum.flush1();
+        }
+        sum.flush2();
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -122,7 +135,7 @@ __global__ __launch_bounds__(256) void linear_bwd_weight_kernel(const float* __r
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = n0 + 4 * g + r;
-            if (n < N) dW[(size_t)n * lddw + k] = t == 0 ? acc0[r] : acc1[r];
+            if (n < N) dW[(size_t)n * lddw + k] = t == 0 ? sum.top0[r] : sum.top1[r];
         }
     }
 }

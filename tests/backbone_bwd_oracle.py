@@ -1,5 +1,6 @@
 """Oracle of the backbone backward: oracle/dinov2_ref's own Block / LayerNorm modules in a chosen dtype under
-torch autograd, a closed-form attention backward for the kernel-level test, and the per-tensor measure and gate of the tests.
+torch autograd, a closed-form attention backward for the kernel-level test, one linear's forward and backward in a chosen dtype for the
+long-reduction tests, and the per-tensor measure and gate of the tests.
 
 Layouts are the library's: token rows of an image are [T real rows | padding] of ``Tp`` rows, the class token last among the real rows;
 ``qkv`` is [B*Tp, 3C] = (Q | K | V) un-scaled with head h at columns h*64."""
@@ -103,6 +104,29 @@ def block_backward(blk, x_in, g_out, B, T, Tp, dtype=torch.float64):
     out[:, :T] = y.detach()
     res["g_in"], res["out"] = g_in.reshape(B * Tp, C), out.reshape(B * Tp, C)
     return res
+
+
+# ------------------------------------------------------------------------------------------------------ one linear
+def linear_forward(X, W, bias, R, dtype=torch.float64):
+    """Y = X W^T + bias + R in ``dtype`` (the expression of mhmr_linear_f32 without an activation)."""
+    return torch.nn.functional.linear(X.to(dtype), W.to(dtype), bias.to(dtype)) + R.to(dtype)
+
+
+def linear_backward(dY, Z, X, W, dR, act, dtype=torch.float64):
+    """dZ = dY * act'(Z) with Z TAKEN AS GIVEN (the taped pre-activation; ``act`` is "none" or "gelu", erf form), through autograd in
+    ``dtype`` -> dict: dW = dZ^T X and db = column sums of dZ (where X is given), dX = dZ W + dR (where W is given)."""
+    dZ = dY.to(dtype)
+    if act == "gelu":
+        z = Z.to(dtype).requires_grad_()
+        (dZ,) = torch.autograd.grad((torch.nn.functional.gelu(z) * dY.to(dtype)).sum(), z)
+    else:
+        assert act == "none"
+    out = {}
+    if X is not None:
+        out["dW"], out["db"] = dZ.T @ X.to(dtype), dZ.sum(0)
+    if W is not None:
+        out["dX"] = dZ @ W.to(dtype) + dR.to(dtype)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------ measure and gate

@@ -72,6 +72,19 @@ def test_linear_backward_validation(L):
         assert wgt(**bad) == BAD_ARG, bad
 
 
+def test_linear_forward_refuses_more_row_tiles_than_a_grid_holds(L):
+    """mhmr_linear_f32's row tiles of 16 are gridDim.y of both of its forms: a launch limit, refused before the launch like its backward
+    siblings' (every case here returns before any launch, so the pointers are never read)."""
+    call = lambda **o: L.mhmr_linear_f32(*[{**dict(X=PTR, ldx=64, row_idx=None, W=PTR, ldw=64, bias=None, R=None, ldr=0, Y=PTR, ldy=32, M=5, N=32,
+                                                   K=64, act=_lib.ACT_NONE, stream=None), **o}[k]
+                                           for k in ("X", "ldx", "row_idx", "W", "ldw", "bias", "R", "ldr", "Y", "ldy", "M", "N", "K", "act", "stream")])
+    for K in (64, 256, 4096):                          # the plain form and the split-k form
+        assert call(M=16 * 65535 + 1, K=K, ldx=K, ldw=K) == BAD_SHAPE, K
+        assert call(M=0x7fffffff, K=K, ldx=K, ldw=K) == BAD_SHAPE, K
+    for bad in (dict(M=0), dict(N=0), dict(K=0), dict(K=40), dict(ldx=66), dict(ldw=66)):
+        assert call(**bad) == BAD_SHAPE, bad
+
+
 def test_layernorm_backward_validation(L):
     call = lambda **o: L.mhmr_layernorm_f32_backward(*[{**dict(x=PTR, w=PTR, dy=PTR, dR=None, dx=PTR, dw=PTR, db=PTR, rows=5, C=128, eps=1e-5,
                                                                ws=PTR, nbytes=1 << 20, stream=None), **o}[k]
