@@ -1198,8 +1198,8 @@ int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream)
 
 /* The backbone tail: the backward of the final LayerNorm -- patch rows only: g_feat [B*N, C] is the cotangent of feat32, the class
  * row and the padding rows of the stream cotangent are zeros -- then mhmr_vit_block_backward for the last n blocks, last block first,
- * each at its tapped input.  The gradient stops at the input of block L - n (g_stream); there is no patch- or position-embedding
- * gradient.  blocks: HOST array of n descriptors in block order (L - n first) of which the fourteen master tensors and the fourteen
+ * each at its tapped input.  The gradient stops at the input of block L - n (g_stream); with n == L that is the token embedding's
+ * output, which mhmr_vit_embed_backward (below) differentiates.  blocks: HOST array of n descriptors in block order (L - n first) of which the fourteen master tensors and the fourteen
  * gradient buffers are read; their shapes, x_in, g_out, g_in and workspace fields are ignored.  tap: [n][B*Tp, C], slot i = the stream
  * entering block L - n + i (mhmr_vit_desc.tap with tap_first = L - n); resid: the stream the final norm read.
  * n >= 1, N == T - 1, and the shape rules of the block (MHMR_ERR_BAD_SHAPE); NULL pointers, a short workspace: MHMR_ERR_BAD_ARG. */
@@ -1219,6 +1219,35 @@ typedef struct {
 } mhmr_vit_tail_backward_desc;
 long long mhmr_vit_tail_backward_workspace_bytes(int B, int Tp, int C);
 int mhmr_vit_tail_backward(const mhmr_vit_tail_backward_desc* d, void* stream);
+
+/* The token embedding: the derivative of the fp32 function
+ *     tokens[b] = [ patchify(x[b]) W^T + bias + pos_G[1:],  cls + pos_G[0] ],   pos_G = interpolate(pos_embed)
+ * at the fp32 master parameters and the fp32 image, against g_stream, the cotangent of the stream entering block 0 (what
+ * mhmr_vit_tail_backward writes with n == L).  The forward's 16-bit roundings of the patches and of W are straight-through.
+ * S = 14 G; N = G*G patch rows of image b at rows b*Tp + n (n = gy*G + gx), its class row at b*Tp + N; the position table has
+ * 1 + M*M rows.  Only the patch rows enter g_patch_w, g_patch_b and g_pos[1:], only the class rows enter g_cls and g_pos[0]
+ * (the same number); rows > N of an image are never read.  interp: DEVICE [G, M] fp64, the bicubic resampling matrix
+ * (pos_G[1 + y*G + x] = sum_a sum_q interp[y][a] interp[x][q] pos[1 + a*M + q]; the identity for G == M).
+ * g_patch_w is an fp32 MFMA chain (v_mfma_f32_16x16x4_f32) over the B*N patch rows in index order, blocked 256 / 4096; every
+ * other sum is fp64 in a fixed index order, rounded once.  No atomics, every element of every output is written, two calls
+ * give the same bits; no allocation, no synchronisation, all validation before the first launch.
+ * MHMR_ERR_BAD_ARG: a NULL pointer, a negative count, a workspace that is short or not 16-byte aligned.  MHMR_ERR_BAD_SHAPE:
+ * S != 14 G, Tp % 64, Tp < G*G + 1, C % 64, C > 2048, B == 0, G == 0, M < 1, or the launch limits (G <= 1024, M <= 4096,
+ * B * Tp <= 16 * 65535). */
+typedef struct {
+    int B, S, G, M, Tp, C;
+    const float* x;         /* [B, 3, S, S] fp32, the forward's input                                  */
+    const float* g_stream;  /* [B*Tp, C] cotangent of the stream entering block 0                      */
+    const double* interp;   /* [G, M] the bicubic resampling matrix                                    */
+    float* g_patch_w;       /* [C, 588], k = c*196 + py*14 + px (torch's conv weight, flattened)       */
+    float* g_patch_b;       /* [C]                                                                     */
+    float* g_cls;           /* [C]                                                                     */
+    float* g_pos;           /* [1 + M*M, C]                                                            */
+    void* workspace;
+    long long workspace_bytes; /* >= mhmr_vit_embed_backward_workspace_bytes(B, G, M, C) */
+} mhmr_vit_embed_backward_desc;
+long long mhmr_vit_embed_backward_workspace_bytes(int B, int G, int M, int C);
+int mhmr_vit_embed_backward(const mhmr_vit_embed_backward_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Measurement: hipEvent brackets around every launch of one kernel family (0 = GEMM, 1 = attention, 2 = LBS

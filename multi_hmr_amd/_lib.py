@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "vit_embed_bwd.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -275,6 +275,14 @@ class VitTailBackwardDesc(C.Structure):
                                                                                    "workspace")] + [("workspace_bytes", C.c_longlong)])
 
 
+class VitEmbedBackwardDesc(C.Structure):
+    """include/mhmr.h mhmr_vit_embed_backward_desc: the image, the cotangent of the stream entering block 0, the resampling matrix and one
+    gradient buffer for each of patch_embed.proj.weight / .bias, cls_token and pos_embed."""
+    _fields_ = ([(n, _i) for n in ("B", "S", "G", "M", "Tp", "C")] +
+                [(n, _vp) for n in ("x", "g_stream", "interp", "g_patch_w", "g_patch_b", "g_cls", "g_pos", "workspace")] +
+                [("workspace_bytes", C.c_longlong)])
+
+
 ADAM_CHUNK = 2048                   # include/mhmr.h MHMR_ADAM_CHUNK
 ADAM_PACK_NONE, ADAM_PACK_F32, ADAM_PACK_F16, ADAM_PACK_BF16 = range(4)
 
@@ -370,6 +378,8 @@ _SIGS = {
     "mhmr_vit_block_backward": ([C.POINTER(VitBlockBackwardDesc), _vp], _i),
     "mhmr_vit_tail_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
     "mhmr_vit_tail_backward": ([C.POINTER(VitTailBackwardDesc), _vp], _i),
+    "mhmr_vit_embed_backward_workspace_bytes": ([_i, _i, _i, _i], C.c_longlong),
+    "mhmr_vit_embed_backward": ([C.POINTER(VitEmbedBackwardDesc), _vp], _i),
     "mhmr_prof_enable": ([_i], _i),
     "mhmr_prof_collect": ([C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)], _i),
 }

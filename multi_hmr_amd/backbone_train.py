@@ -30,6 +30,16 @@ def backbone_parameter_names(depth: int, n: int = 1) -> list:
     return names
 
 
+#: the four parameters of the token embedding, in the order ``Model.embedding_parameters`` returns and ``embed_backward`` answers
+EMBED_FIELDS = dict(g_patch_w="patch_embed.proj.weight", g_patch_b="patch_embed.proj.bias", g_pos="pos_embed", g_cls="cls_token")
+
+
+def embedding_parameter_names() -> list:
+    """``named_parameters`` keys of the token embedding: patch convolution weight and bias, position table, class token.  They receive a
+    gradient only when every block is trained (``train_backbone_(depth)``): DESIGN.md section 29."""
+    return [ENCODER + n for n in EMBED_FIELDS.values()]
+
+
 def _f32(t):
     if not t.is_cuda:
         raise _lib.MhmrError("multi_hmr_amd.backbone_train runs only on an MI355X (HIP) tensor; there is no CPU fallback")
@@ -128,10 +138,37 @@ def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H,
     return g_stream, g_norm_w, g_norm_b, grads
 
 
-def model_tail_backward(model, P, ws, B, g_feat, n):
+def embed_backward(x, g_stream, B, G, M, Tp, stream=None):
+    """``mhmr_vit_embed_backward`` on device tensors: ``x [B, 3, 14 G, 14 G]`` the forward's input, ``g_stream [B*Tp, C]`` the cotangent of the
+    stream entering block 0 (``tail_backward`` over every block), ``M`` the edge of the stored position table
+    -> {g_patch_w [C, 588], g_patch_b [C], g_pos [1 + M*M, C], g_cls [C]}."""
+    import numpy as np
+    from . import packing
+    L = _lib.lib()
+    x, g_stream = _f32(x), _f32(g_stream)
+    dev, Cd = g_stream.device, g_stream.shape[1]
+    assert tuple(x.shape) == (B, 3, 14 * G, 14 * G) and g_stream.shape[0] == B * Tp
+    interp = torch.from_numpy(np.ascontiguousarray(packing.pos_embed_matrix(M, G))).to(dev)
+    out = dict(g_patch_w=torch.empty(Cd, 588, dtype=torch.float32, device=dev), g_patch_b=torch.empty(Cd, dtype=torch.float32, device=dev),
+               g_pos=torch.empty(1 + M * M, Cd, dtype=torch.float32, device=dev), g_cls=torch.empty(Cd, dtype=torch.float32, device=dev))
+    nbytes = _lib.workspace_bytes("mhmr_vit_embed_backward_workspace_bytes", B, G, M, Cd)
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    d = _lib.VitEmbedBackwardDesc()
+    d.B, d.S, d.G, d.M, d.Tp, d.C = B, 14 * G, G, M, Tp, Cd
+    d.x, d.g_stream, d.interp, d.workspace, d.workspace_bytes = x.data_ptr(), g_stream.data_ptr(), interp.data_ptr(), wsb.data_ptr(), nbytes
+    for f, t in out.items():
+        setattr(d, f, t.data_ptr())
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(L.mhmr_vit_embed_backward(C.byref(d), stream), "mhmr_vit_embed_backward")
+    return out
+
+
+def model_tail_backward(model, P, ws, B, g_feat, n, x=None):
     """The tail backward of ``model`` on the workspace of its last ``train_backbone`` forward of batch size B: the fp32 master weights
     are the ``nn.Parameter``s themselves; one call per image block of the workspace (``Model._nsplit``), the parameter gradients of the
-    blocks added in block order.  -> {parameter name: gradient} for ``backbone_parameter_names(depth, n)``."""
+    blocks added in block order.  -> {parameter name: gradient} for ``backbone_parameter_names(depth, n)``.
+    ``x`` (the forward's fp32 input, ``n == depth`` only): every image block's ``g_stream`` also goes through ``embed_backward`` with that
+    block's images, and the dict gains the gradients of ``embedding_parameter_names()`` (shaped [C, 588], [C], [1 + M*M, C], [C])."""
     enc = model.backbone.encoder
     depth, N, Cd, H = len(enc.blocks), P["N"], P["C"], P["H"]
     if ws.get("tap_blocks") != n:
@@ -140,17 +177,25 @@ def model_tail_backward(model, P, ws, B, g_feat, n):
     norm_w, norm_b = _f32(enc.norm.weight), _f32(enc.norm.bias)
     blocks = [block_tensors(enc.blocks[l], dev) for l in range(depth - n, depth)]
     g_feat = _f32(g_feat).reshape(B * N, Cd)
+    if x is not None and n != depth:
+        raise _lib.MhmrError(f"Model: the embedding gradient needs every block's backward ({depth}), this one runs {n}")
+    names = backbone_parameter_names(depth, n) + (embedding_parameter_names() if x is not None else [])
+    M = int(round((enc.pos_embed.shape[1] - 1) ** 0.5))
     total = None
     for part in ws["parts"]:
         Bh, i0, bufs = part["B"], part["img0"], part["bufs"]
-        _, gw, gb, grads = tail_backward(norm_w, norm_b, blocks, bufs["tap"], bufs["resid"], g_feat[i0 * N:(i0 + Bh) * N], Bh, N, ws["Tp"], H)
+        g_stream, gw, gb, grads = tail_backward(norm_w, norm_b, blocks, bufs["tap"], bufs["resid"], g_feat[i0 * N:(i0 + Bh) * N], Bh, N, ws["Tp"], H)
         flat = [gw, gb] + [g[f] for g in grads for f in _lib.VitBlockBackwardDesc.PARAMS]
+        if x is not None:
+            ge = embed_backward(x[i0:i0 + Bh], g_stream, Bh, P["G"], M, ws["Tp"])
+            flat += [ge[f] for f in EMBED_FIELDS]
         total = flat if total is None else [a + b for a, b in zip(total, flat)]
-    return dict(zip(backbone_parameter_names(depth, n), total))
+    return dict(zip(names, total))
 
 
 class _TailFunction(torch.autograd.Function):
-    """(the parameters of backbone_parameter_names) -> features [B, N, C]: the values are the ones the forward has already computed."""
+    """(the parameters of backbone_parameter_names, then -- when the embedding is trained -- of embedding_parameter_names) -> features
+    [B, N, C]: the values are the ones the forward has already computed."""
 
     @staticmethod
     def forward(ctx, model, st, *params):
@@ -164,22 +209,39 @@ class _TailFunction(torch.autograd.Function):
         P, ws = st["P"], st["ws"]
         model._require_current(st["taken"])
         need = ctx.needs_input_grad[2:]
+        embed = any(need[len(st["named"]) - len(EMBED_FIELDS):]) if st["x"] is not None else False
         with model._lock, torch.cuda.device(st["dev"]):
-            grads = model_tail_backward(model, P, ws, st["B"], g_feat, st["n"])
+            grads = model_tail_backward(model, P, ws, st["B"], g_feat, st["n"], st["x"] if embed else None)
+        need = [want and k in grads for (k, _), want in zip(st["named"], need)]
         return (None, None) + tuple(grads[k].view_as(p) if want else None for (k, p), want in zip(st["named"], need))
 
 
-def attach(model, P, ws, B):
+def embeddings_on(model) -> bool:
+    """Some embedding parameter of ``model`` requires grad.  ``ValueError`` when ``train_backbone_``'s n then is not the depth: the gradient
+    reaches the embedding only through every block."""
+    if not any(p.requires_grad for p in model.embedding_parameters()):
+        return False
+    depth = len(model.backbone.encoder.blocks)
+    if model._backbone_n != depth:
+        raise ValueError(f"embedding parameters require grad, but train_backbone_({model._backbone_n}) stops the backward in front of block "
+                         f"{depth - model._backbone_n}: call train_backbone_({depth}) (or train_embeddings_(False))")
+    return True
+
+
+def attach(model, P, ws, B, x=None):
     """-> the features of the forward that has just run on ``ws`` (a clone, [B, N, C]) attached to autograd with respect to
-    ``model.backbone_parameters(n)``: the node that hands the feature cotangent to ``mhmr_vit_tail_backward``."""
+    ``model.backbone_parameters(n)``: the node that hands the feature cotangent to ``mhmr_vit_tail_backward``.  ``x``: the forward's
+    contiguous fp32 input when the embedding is trained (``embeddings_on``) -- the node then also takes ``model.embedding_parameters()`` and
+    keeps a reference to ``x``, which the caller must not write into before ``backward()``."""
     n = model._backbone_n
     params = dict(model.named_parameters())
-    named = [(k, params[k]) for k in backbone_parameter_names(len(model.backbone.encoder.blocks), n)]
-    st = dict(P=P, ws=ws, B=B, n=n, dev=ws["feat32"].device, taken=model._take(P, ws, "backbone_generation"),
+    names = backbone_parameter_names(len(model.backbone.encoder.blocks), n) + (embedding_parameter_names() if x is not None else [])
+    named = [(k, params[k]) for k in names]
+    st = dict(P=P, ws=ws, B=B, n=n, dev=ws["feat32"].device, taken=model._take(P, ws, "backbone_generation"), x=x,
               named=named, features=ws["feat32"].view(B, P["N"], P["C"]).clone())
     with torch.enable_grad():
         return _TailFunction.apply(model, st, *[p for _, p in named])
 
 
-__all__ = ["BLOCK_FIELDS", "backbone_parameter_names", "attention_tape", "attention_backward", "block_tensors", "block_backward", "tail_backward",
-           "model_tail_backward", "attach"]
+__all__ = ["BLOCK_FIELDS", "EMBED_FIELDS", "backbone_parameter_names", "embedding_parameter_names", "attention_tape", "attention_backward",
+           "block_tensors", "block_backward", "tail_backward", "embed_backward", "model_tail_backward", "embeddings_on", "attach"]

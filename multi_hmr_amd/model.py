@@ -479,12 +479,27 @@ class Model(nn.Module):
         self._backbone_n = int(n)
         return self
 
+    def embedding_parameters(self):
+        """The four parameters of the token embedding (``backbone_train.embedding_parameter_names``): patch convolution weight and bias,
+        position table, class token.  They stay ``requires_grad=False`` until ``train_embeddings_()``."""
+        from .backbone_train import embedding_parameter_names
+        params = dict(self.named_parameters())
+        return [params[k] for k in embedding_parameter_names()]
+
+    def train_embeddings_(self, flag=True):
+        """Set ``requires_grad`` of ``embedding_parameters()`` and of nothing else; returns self.  Their gradient passes through every
+        block: a ``train_backbone=True`` forward raises ``ValueError`` unless ``train_backbone_(depth)`` is set."""
+        for p in self.embedding_parameters():
+            p.requires_grad_(bool(flag))
+        return self
+
     def repack_backbone(self):
         """Re-pack the final norm and the last ``n`` blocks (``train_backbone_``'s n) into the buffers the descriptors already point to --
         after an optimiser step on ``backbone_parameters(n)``.  Fold, column sums, low halves and fp8 rows of a block are derived again
         from its parameters by the code that packed them (``vit.pack_block``), so the next forward equals ``repack()`` + forward bit for
-        bit (the precision a pack resolved from ``'auto'`` is kept).  The head pack and the workspaces stay.  A pending ``backward`` must
-        run first."""
+        bit (the precision a pack resolved from ``'auto'`` is kept).  When embedding parameters require grad, the packed patch weight and
+        bias, the resampled position table and class row are refreshed the same way (``vit.pack_embeddings``).  The head pack and the
+        workspaces stay.  A pending ``backward`` must run first."""
         with self._lock:
             P = self._packed
             if P is None:
@@ -503,6 +518,10 @@ class Model(nn.Module):
                         setattr(v["blocks"][l], name, val)
                 v["norm_t"]["norm_w"].copy_(_f32(enc.norm.weight, P["device"]))
                 v["norm_t"]["norm_b"].copy_(_f32(enc.norm.bias, P["device"]))
+                if any(p.requires_grad for p in self.embedding_parameters()):
+                    for name, t in vit.pack_embeddings(P, enc).items():
+                        assert t.shape == v["embed_t"][name].shape and t.dtype == v["embed_t"][name].dtype, name
+                        v["embed_t"][name].copy_(t)
             P["backbone_generation"] += 1
 
     def _packed_for(self, device):
@@ -612,14 +631,17 @@ class Model(nn.Module):
         """[B,3,S,S] -> [B,N,C] fp32 patch features (reference blocks/dinov2.py:16-26), as a view of the workspace.
         ``train_backbone=True``: a ``.clone()`` of them instead, attached to autograd with respect to ``backbone_parameters(n)``
         (``train_backbone_``'s n): the backbone tail on its own.  Its backward reads this call's workspace (the tapped streams), so it must
-        run before the next forward of the same batch size."""
+        run before the next forward of the same batch size.  With ``train_embeddings_()`` also with respect to
+        ``embedding_parameters()``: the node keeps a reference to the contiguous fp32 ``x``, which must not be written into before
+        ``backward()``."""
         with self._lock:                      # (workspaces belong to the instance: same lock as forward(); round-5 advisor finding)
             if train_backbone:
+                from . import backbone_train
+                embed = backbone_train.embeddings_on(self)          # (ValueError before any GPU work when n < depth)
                 x = x.float().contiguous()
                 P, ws, stream = self._prepare(x, tap=self._backbone_n)
                 self._run_backbone(P, ws, x)
-                from . import backbone_train
-                return backbone_train.attach(self, P, ws, x.shape[0])
+                return backbone_train.attach(self, P, ws, x.shape[0], x if embed else None)
             P, ws, stream = self._prepare(x)
             self._run_backbone(P, ws, x)
             return ws["feat32"].view(x.shape[0], P["N"], P["C"])
@@ -660,8 +682,13 @@ class Model(nn.Module):
         for key and bit for bit, with its outputs attached to autograd with respect to ``backbone_parameters(n)`` (``train_backbone_``'s
         n): the forward taps the residual stream in front of the last n blocks, the feature cotangent of
         ``forward_features`` carries the gradient to the features, and one node hands it to ``mhmr_vit_tail_backward``.  The same rule
-        for the backward; afterwards an optimiser step and ``repack_backbone()``."""
+        for the backward; afterwards an optimiser step and ``repack_backbone()``.  With ``train_embeddings_()`` (DESIGN.md section 29;
+        needs ``train_backbone_(depth)``, ``ValueError`` otherwise) the node also covers ``embedding_parameters()`` and keeps a reference
+        to the contiguous fp32 ``x`` -- ``x`` itself when it already is that: do not write into ``x`` before ``backward()``."""
         sw = call_switches(is_training, kwargs)
+        if sw.train_backbone:
+            from . import backbone_train
+            backbone_train.embeddings_on(self)                      # ValueError before any GPU work: embeddings need train_backbone_(depth)
         with self._lock, torch.autocast("cuda", enabled=False):     # demo.forward_model wraps us in fp16 autocast (demo.py:117)
             return self._forward(x.float().contiguous(), idx, det_thresh, nms_kernel_size, K, is_training, sw)
 
@@ -753,7 +780,7 @@ class Model(nn.Module):
         features = None
         if sw.train_backbone:       # the features as a tensor attached to the backbone parameters: the route of forward_features from here on
             from . import backbone_train
-            features = backbone_train.attach(self, P, ws, B)
+            features = backbone_train.attach(self, P, ws, B, x if backbone_train.embeddings_on(self) else None)
         return self._behind_front(P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, sw, features)
 
     def _behind_front(self, P, ws, dev, B, stream, idx, det_thresh, nms_kernel_size, K, is_training, sw, features):

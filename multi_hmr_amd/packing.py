@@ -27,6 +27,27 @@ def _cubic_weights(t: np.ndarray, A: float = -0.75) -> np.ndarray:
     return np.stack([outer(t + 1), inner(t), inner(1 - t), outer(2 - t)], axis=-1)
 
 
+def _cubic_taps(M: int, G: int, offset: float = 0.1):
+    """-> (weights [G, 4] fp64, clipped source indices [G, 4]) of the resampling of M cells to G along one axis."""
+    inv = 1.0 / float(G + offset) * M                  # 1 / scale_factor
+    src = (np.arange(G, dtype=np.float64) + 0.5) * inv - 0.5
+    fl = np.floor(src)
+    return _cubic_weights(src - fl), np.clip(fl[:, None].astype(np.int64) + np.arange(-1, 3)[None, :], 0, M - 1)
+
+
+def pos_embed_matrix(M: int, G: int, offset: float = 0.1) -> np.ndarray:
+    """The dense [G, M] fp64 matrix R of ``interpolate_pos_embed`` along one axis: with ``grid = pos_embed[0, 1:].reshape(M, M, C)`` the
+    resampled table is ``einsum("ya,xb,abc->yxc", R, R, grid)``, and the gradient of the table is the same product with R transposed
+    (``mhmr_vit_embed_backward``'s ``interp``).  Same weights and clipped indices as ``interpolate_pos_embed``; taps clipped onto one
+    border cell add.  ``G == M``: the identity, because the table is returned untouched there (the formula with the offset is not)."""
+    if G == M:
+        return np.eye(M, dtype=np.float64)
+    w, idx = _cubic_taps(M, G, offset)
+    R = np.zeros((G, M), dtype=np.float64)
+    np.add.at(R, (np.arange(G)[:, None].repeat(4, 1), idx), w)
+    return R
+
+
 def interpolate_pos_embed(pos_embed: np.ndarray, G: int, offset: float = 0.1) -> np.ndarray:
     """DINOv2 ``interpolate_pos_encoding`` for a G x G grid: the M x M patch table is
     resampled bicubically (A=-0.75, align_corners=False, no antialias) with the source coordinate computed from
@@ -39,14 +60,7 @@ def interpolate_pos_embed(pos_embed: np.ndarray, G: int, offset: float = 0.1) ->
         return pe.astype(np.float32)
     C = pe.shape[1]
     grid = pe[1:].reshape(M, M, C)
-    scale = np.float32(float(G + offset) / M)          # torch keeps the scale as a C++ double made from a python float
-    inv = 1.0 / float(G + offset) * M                  # 1 / scale_factor
-    o = np.arange(G, dtype=np.float64)
-    src = (o + 0.5) * inv - 0.5
-    fl = np.floor(src)
-    t = src - fl
-    w = _cubic_weights(t)                               # [G,4]
-    idx = np.clip(fl[:, None].astype(np.int64) + np.arange(-1, 3)[None, :], 0, M - 1)   # [G,4]
+    w, idx = _cubic_taps(M, G, offset)                  # [G,4] each (torch keeps the scale as a C++ double made from a python float)
     rows = np.einsum("ya,yaxc->yxc", w, grid[idx])      # interpolate along y: [G, M, C]
     out = np.einsum("xa,yxac->yxc", w, rows[:, idx])    # then along x: [G, G, C]
     return np.concatenate([pe[:1], out.reshape(G * G, C)], axis=0).astype(np.float32)

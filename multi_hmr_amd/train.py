@@ -91,7 +91,7 @@ class Trainer:
         detection = any(p.requires_grad for p in model.detection_parameters())
         # backbone parameters in the optimiser's groups (any torch.optim optimiser; HeadsAdam covers the heads and the detector only)
         in_opt = {id(p) for g in getattr(opt, "param_groups", ()) for p in g["params"]}
-        backbone = any(p.requires_grad and id(p) in in_opt for p in model.backbone_parameters(model._backbone_n))
+        backbone = any(p.requires_grad and id(p) in in_opt for p in model.backbone_parameters(model._backbone_n) + model.embedding_parameters())
         if not (heads or detection or backbone):
             raise _lib.MhmrError("Trainer: nothing to train -- call model.train_heads_(True) and / or model.train_detection_(True) first")
         kw = {}

@@ -200,10 +200,6 @@ def pack_encoder(enc, img_size: int, precision: str, device, wlo: str | None = N
                       f"attention keep the 1e-3 contract on such weights at about 4x the time of plain f16; Model(precision='f16') forces "
                       f"the fast path (tools/checkpoint_report.py and tools/parity_table.py say what that costs on these weights).",
                       RuntimeWarning, stacklevel=3)
-    pos = torch.from_numpy(packing.interpolate_pos_embed(enc.pos_embed.detach().float().cpu().numpy(), G)).to(device)
-    cls_pos0 = f32(enc.cls_token.reshape(-1)) + pos[0]
-    pw = torch.zeros(Cd, P["Kp"], dtype=torch.float32, device=device)
-    pw[:, :588] = f32(enc.patch_embed.proj.weight).reshape(Cd, 588)
     blocks = (_lib.VitBlock * L)()
     if x3:
         # every linear as three products over operand pairs; fp32 LayerNorm / GELU / attention (csrc/capi.hip vit_forward_x3)
@@ -231,11 +227,27 @@ def pack_encoder(enc, img_size: int, precision: str, device, wlo: str | None = N
         for n, v in scalars.items():
             setattr(blocks[i], n, v)
     norm_t = dict(norm_w=f32(enc.norm.weight), norm_b=f32(enc.norm.bias))
-    P["vit"] = dict(blocks=blocks, patch_w=k(triple(pw, tdt) if x3 else pw.to(tdt).contiguous()), patch_b=k(f32(enc.patch_embed.proj.bias)),
-                    cls_pos0=k(cls_pos0.contiguous()), pos=k(pos.contiguous()), norm_w=k(norm_t["norm_w"]), norm_b=k(norm_t["norm_b"]),
-                    block_t=block_t, norm_t=norm_t)
+    embed_t = pack_embeddings(P, enc)
+    P["vit"] = dict(blocks=blocks, patch_w=k(embed_t["patch_w"]), patch_b=k(embed_t["patch_b"]), cls_pos0=k(embed_t["cls_pos0"]),
+                    pos=k(embed_t["pos"]), norm_w=k(norm_t["norm_w"]), norm_b=k(norm_t["norm_b"]), block_t=block_t, norm_t=norm_t,
+                    embed_t=embed_t)
     P["keep"] = keep
     return P
+
+
+def pack_embeddings(P: dict, enc) -> dict:
+    """The packed tensors of the token embedding under the pack's choices (``P``: precision, grid) -> {mhmr_vit_desc pointer field:
+    tensor}: ``patch_w`` (the flattened convolution weight zero-padded to Kp columns, in the 16-bit operand type, or the operand triple
+    under f16x3), ``patch_b``, ``pos`` (the table resampled to the G x G grid on the host) and ``cls_pos0`` (class token + its position
+    row).  ``pack_encoder`` and ``Model.repack_backbone`` both come through here, so the two cannot drift apart."""
+    device, tdt, Cd = P["device"], P["tdt"], P["C"]
+    f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+    pos = torch.from_numpy(packing.interpolate_pos_embed(enc.pos_embed.detach().float().cpu().numpy(), P["G"])).to(device)
+    cls_pos0 = f32(enc.cls_token.reshape(-1)) + pos[0]
+    pw = torch.zeros(Cd, P["Kp"], dtype=torch.float32, device=device)
+    pw[:, :588] = f32(enc.patch_embed.proj.weight).reshape(Cd, 588)
+    return dict(patch_w=triple(pw, tdt) if P.get("x3") else pw.to(tdt).contiguous(), patch_b=f32(enc.patch_embed.proj.bias),
+                cls_pos0=cls_pos0.contiguous(), pos=pos.contiguous())
 
 
 def pack_block(P: dict, b, i: int):

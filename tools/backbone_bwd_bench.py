@@ -9,7 +9,10 @@ of alternating repetitions after warm-up.  Per configuration -- ViT-L 896^2 with
 The attention lines carry the fraction of the 155 TFLOP/s fp32 matrix rate that their useful products reach (tape 4 T^2 64 per head and
 image, backward 14 T^2 64: seven products, of which the kernels compute nine -- S and dP twice in the query pass).
 One JSON line per measurement, printed and appended to --out (default profiles/backbone_bwd_bench.txt).
-  python tools/backbone_bwd_bench.py [--config all|vitl_896_8|vitl_896_32|vits_672_16] [--reps 3] [--warmup 1] [--skip-model]"""
+--embed: instead, one line per configuration for the backward of the token embedding
+  embed_bwd       mhmr_vit_embed_backward through backbone_train.embed_backward, stored table 37 x 37
+appended to --embed-out (default profiles/embed_bwd_bench.txt).
+  python tools/backbone_bwd_bench.py [--config all|vitl_896_8|vitl_896_32|vits_672_16] [--reps 3] [--warmup 1] [--skip-model] [--embed]"""
 import argparse
 import json
 import os
@@ -79,6 +82,22 @@ def kernels(name, backbone, S, B, a):
     return lines
 
 
+def embed(name, backbone, S, B, a):
+    """mhmr_vit_embed_backward on a random image batch and stream cotangent of the configuration's shape."""
+    Cd, G = VIT_CFG[backbone]["embed_dim"], S // 14
+    Tp = (G * G + 1 + 63) // 64 * 64
+    g = torch.Generator(device=DEV).manual_seed(4)
+    x, gs = torch.randn(B, 3, S, S, generator=g, device=DEV) + 0.5, torch.randn(B * Tp, Cd, generator=g, device=DEV)
+    ms = timed({"embed_bwd": lambda: bt.embed_backward(x, gs, B, G, 37, Tp)}, a)
+    med = sorted(ms["embed_bwd"])[len(ms["embed_bwd"]) // 2]
+    flop = 2.0 * B * G * G * Cd * 588
+    return [report("embed_backward", ms, dict(config=name, backbone=backbone, size=S, images=B, G=G, M=37, Tp=Tp, C=Cd, patch_weight_gflop=round(flop / 1e9, 1),
+                                              workspace_bytes=int(_lib.lib().mhmr_vit_embed_backward_workspace_bytes(B, G, 37, Cd)),
+                                              fraction_of_fp32_mfma_peak=round(flop / FP32_MFMA_FLOPS / (med * 1e-3), 4),
+                                              note="one call: g_patch_w (fp32 MFMA chain, image gathered), g_patch_b, g_cls, g_pos (fp64); the wrapper's "
+                                                   "allocations and the upload of the resampling matrix are inside the bracket"))]
+
+
 def model_level(name, backbone, S, B, a):
     smplx_data, mean_params = synthetic.make_smplx_data(0), synthetic.make_mean_params(0)
     m = Model(backbone=backbone, img_size=S, smplx_data=smplx_data, mean_params=mean_params, precision="f16")
@@ -106,6 +125,13 @@ def model_level(name, backbone, S, B, a):
 def main(a):
     names = list(CONFIGS) if a.config == "all" else [a.config]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.embed:                                              # the embedding backward alone, into a file of its own
+        with open(a.embed_out, "a") as fh:
+            fh.write("# tools/backbone_bwd_bench.py --embed: mhmr_vit_embed_backward through backbone_train.embed_backward\n")
+            for name in names:
+                for line in embed(name, *CONFIGS[name], a):
+                    fh.write(json.dumps(line) + "\n")
+        return
     with open(a.out, "a") as fh:
         fh.write("# tools/backbone_bwd_bench.py: attention tape / backward, block backward and a train_backbone step next to the forward\n")
         for name in names:
@@ -123,6 +149,8 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "backbone_bwd_bench.txt"))
+    ap.add_argument("--embed", action="store_true", help="time the embedding backward (section 29) instead, appended to --embed-out")
+    ap.add_argument("--embed-out", default=os.path.join(ROOT, "profiles", "embed_bwd_bench.txt"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("backbone_bwd_bench measures on the GPU; there is none here")
