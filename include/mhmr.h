@@ -1191,9 +1191,11 @@ typedef struct {
     float* g_fc2_b;
     float* g_ls2;
     void* workspace;
-    long long workspace_bytes; /* >= mhmr_vit_block_backward_workspace_bytes(B, Tp, C) */
+    long long workspace_bytes; /* >= mhmr_vit_block_backward_workspace_bytes(B, Tp, C); with linear_precision 1: ..._bytes_p(B, Tp, C, 1) */
+    int linear_precision;      /* MHMR_BWD_F32 (0, a zeroed field): the exact fp32 linears; MHMR_BWD_BF16 (1): bf16 operands (below) */
 } mhmr_vit_block_backward_desc;
 long long mhmr_vit_block_backward_workspace_bytes(int B, int Tp, int C);
+long long mhmr_vit_block_backward_workspace_bytes_p(int B, int Tp, int C, int precision);
 int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream);
 
 /* The backbone tail: the backward of the final LayerNorm -- patch rows only: g_feat [B*N, C] is the cotangent of feat32, the class
@@ -1215,10 +1217,46 @@ typedef struct {
     float* g_norm_b;
     float* g_stream; /* [B*Tp, C] cotangent of the stream entering block L - n; rows >= T are zeros */
     void* workspace;
-    long long workspace_bytes; /* >= mhmr_vit_tail_backward_workspace_bytes(B, Tp, C) */
+    long long workspace_bytes; /* >= mhmr_vit_tail_backward_workspace_bytes(B, Tp, C); with linear_precision 1: ..._bytes_p(B, Tp, C, 1) */
+    int linear_precision;      /* MHMR_BWD_*: handed to every block (the blocks' own field is ignored, like their shapes) */
 } mhmr_vit_tail_backward_desc;
 long long mhmr_vit_tail_backward_workspace_bytes(int B, int Tp, int C);
+long long mhmr_vit_tail_backward_workspace_bytes_p(int B, int Tp, int C, int precision);
 int mhmr_vit_tail_backward(const mhmr_vit_tail_backward_desc* d, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------------
+ * Mixed-precision backbone training: dense linears with bf16 operands and fp32 accumulation on
+ * v_mfma_f32_16x16x32_bf16 -- what torch autocast makes of an nn.Linear, in both directions.  r() is round-to-nearest-even
+ * fp32 -> bf16 (torch.Tensor.bfloat16()); every tensor here is fp32, row-major, W [N, K] in torch layout:
+ *   mhmr_linear_bf16:                  Y[m][n]  = sum_k r(X[m][k]) r(W[n][k]) + bias[n]           (bias may be NULL)
+ *   mhmr_linear_bf16_backward_input:   dX[m][k] = sum_n r(dY[m][n]) r(W[n][k]) (+ dR[m][k])       (dR may be NULL; added in fp32)
+ *   mhmr_linear_bf16_backward_weight:  dW[n][k] = sum_m r(dY[m][n]) r(X[m][k]);  db[n] = sum_m dY[m][n] in fp64 from the
+ *                                      UNROUNDED dY, two fixed stages.  dW or db may be NULL, not both.
+ * There is no activation argument: a GELU derivative is applied in fp32 in front of these products (the block does so).
+ * A product of two bf16 numbers is exact in fp32; the fp32 accumulation runs in chains of 256 summed indices that are added
+ * into a second accumulator, and the weight side's sum over M is cut into slices of 4096 rows whose partial products (in the
+ * workspace) are added in slice order in fp64 and rounded once.  The shape of every sum is fixed by (M, N, K) alone: no
+ * floating-point atomics, two calls give the same bits, rows of exact zeros appended to dY change no bit of dW.  Every
+ * element of every output is written; no allocation, no synchronisation; everything is validated before the first launch.
+ * Shapes: M, N, K multiples of 64 and at least 64, M <= 16 * 65535; every leading dimension at least its row length and a
+ * multiple of 4 (MHMR_ERR_BAD_SHAPE otherwise).  MHMR_ERR_BAD_ARG: a negative count, a NULL pointer that would be read or
+ * written, a pointer that is not 16-byte aligned (db excepted), a workspace below mhmr_linear_bf16_workspace_bytes(M, N, K)
+ * -- one size for all three products.
+ * In mhmr_vit_block_backward / mhmr_vit_tail_backward, linear_precision = MHMR_BWD_BF16 sends the four linears of the tape and
+ * their eight backward products through these kernels (dh <- dh * gelu'(z1) by an fp32 kernel in front of fc1's two).  The
+ * LayerNorms, the attention tape and backward, LayerScale, GELU, the row mask and every fp64 column sum are the fp32 mode's,
+ * and so are its invariants: rows >= T of g_in / g_stream are exact zeros, finite values in rows >= T of x_in / g_out move no
+ * bit, an image's g_in does not depend on the other images.  Any other value of linear_precision: MHMR_ERR_BAD_ARG.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define MHMR_BWD_F32 0
+#define MHMR_BWD_BF16 1
+long long mhmr_linear_bf16_workspace_bytes(int M, int N, int K);
+int mhmr_linear_bf16(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy, int M, int N, int K,
+                     void* workspace, long long workspace_bytes, void* stream);
+int mhmr_linear_bf16_backward_input(const float* dY, int lddy, const float* W, int ldw, const float* dR, int lddr, float* dX,
+                                    int lddx, int M, int N, int K, void* workspace, long long workspace_bytes, void* stream);
+int mhmr_linear_bf16_backward_weight(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw, float* db, int M,
+                                     int N, int K, void* workspace, long long workspace_bytes, void* stream);
 
 /* The token embedding: the derivative of the fp32 function
  *     tokens[b] = [ patchify(x[b]) W^T + bias + pos_G[1:],  cls + pos_G[0] ],   pos_G = interpolate(pos_embed)

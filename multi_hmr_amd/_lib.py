@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "vit_embed_bwd.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -265,14 +265,26 @@ class VitBlockBackwardDesc(C.Structure):
     of its output, and one gradient buffer per tensor."""
     PARAMS = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")
     _fields_ = ([(n, _i) for n in ("B", "T", "Tp", "C", "H")] + [(n, _vp) for n in PARAMS] + [(n, _vp) for n in ("x_in", "g_out", "g_in")] +
-                [("g_" + n, _vp) for n in PARAMS] + [("workspace", _vp), ("workspace_bytes", C.c_longlong)])
+                [("g_" + n, _vp) for n in PARAMS] + [("workspace", _vp), ("workspace_bytes", C.c_longlong), ("linear_precision", _i)])
 
 
 class VitTailBackwardDesc(C.Structure):
     """include/mhmr.h mhmr_vit_tail_backward_desc: final norm + the last n blocks, at the tapped streams."""
     _fields_ = ([(n, _i) for n in ("B", "N", "T", "Tp", "C", "H", "n")] + [("norm_w", _vp), ("norm_b", _vp),
                 ("blocks", C.POINTER(VitBlockBackwardDesc))] + [(n, _vp) for n in ("tap", "resid", "g_feat", "g_norm_w", "g_norm_b", "g_stream",
-                                                                                   "workspace")] + [("workspace_bytes", C.c_longlong)])
+                                                                                   "workspace")] + [("workspace_bytes", C.c_longlong),
+                                                                                                     ("linear_precision", _i)])
+
+
+BWD_F32, BWD_BF16 = 0, 1            # include/mhmr.h MHMR_BWD_*: linear_precision of the two descriptors above
+BWD_PRECISIONS = {"f32": BWD_F32, "bf16": BWD_BF16}
+
+
+def bwd_precision(name) -> int:
+    """MHMR_BWD_* of a precision name of the backbone backward ("f32" or "bf16"); ``ValueError`` for anything else."""
+    if name not in BWD_PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(BWD_PRECISIONS)}, not {name!r}")
+    return BWD_PRECISIONS[name]
 
 
 class VitEmbedBackwardDesc(C.Structure):
@@ -375,9 +387,15 @@ _SIGS = {
     "mhmr_attention_f32_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
     "mhmr_attention_f32_backward": ([_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
     "mhmr_vit_block_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_vit_block_backward_workspace_bytes_p": ([_i, _i, _i, _i], C.c_longlong),
     "mhmr_vit_block_backward": ([C.POINTER(VitBlockBackwardDesc), _vp], _i),
     "mhmr_vit_tail_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_vit_tail_backward_workspace_bytes_p": ([_i, _i, _i, _i], C.c_longlong),
     "mhmr_vit_tail_backward": ([C.POINTER(VitTailBackwardDesc), _vp], _i),
+    "mhmr_linear_bf16_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_linear_bf16": ([_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
+    "mhmr_linear_bf16_backward_input": ([_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
+    "mhmr_linear_bf16_backward_weight": ([_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
     "mhmr_vit_embed_backward_workspace_bytes": ([_i, _i, _i, _i], C.c_longlong),
     "mhmr_vit_embed_backward": ([C.POINTER(VitEmbedBackwardDesc), _vp], _i),
     "mhmr_prof_enable": ([_i], _i),

@@ -2,7 +2,8 @@
 image, in fp32 at the fp32 master weights, evaluated at the residual stream the inference forward produced.
 
 The functions here run the kernels of csrc/vit_bwd.hip on device tensors and allocate their outputs and workspaces.  There is no CPU
-path.  Token rows follow the forward's layout: ``Tp`` rows per image, patch rows first, the class token at row ``N = T - 1``, padding
+path.  ``precision="bf16"`` gives the linears of a block bf16 operands with fp32 accumulation (csrc/linear_bf16.hip),
+in the recomputed tape and in both backward products; attention, LayerNorm and the column sums stay exact, and ``"f32"`` is the default.  Token rows follow the forward's layout: ``Tp`` rows per image, patch rows first, the class token at row ``N = T - 1``, padding
 behind it."""
 from __future__ import annotations
 
@@ -95,28 +96,74 @@ def fill_block_desc(d, params: dict, grads: dict, B, T, Tp, Cd, H):
     return d
 
 
-def block_backward(params: dict, x_in, g_out, B, T, Tp, H, stream=None):
+def linear_bf16(X, W, bias=None, stream=None):
+    """``mhmr_linear_bf16``: Y [M, N] = r(X [M, K]) r(W [N, K])^T + bias, bf16 operands (round to nearest even), fp32 accumulation."""
+    X, W = _f32(X), _f32(W)
+    bias = None if bias is None else _f32(bias)
+    (M, K), N = X.shape, W.shape[0]
+    Y = torch.empty(M, N, dtype=torch.float32, device=X.device)
+    nbytes = _lib.workspace_bytes("mhmr_linear_bf16_workspace_bytes", M, N, K)
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    stream = torch.cuda.current_stream(X.device).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().mhmr_linear_bf16(X.data_ptr(), K, W.data_ptr(), K, _lib.ptr(bias), Y.data_ptr(), N, M, N, K, wsb.data_ptr(), nbytes, stream),
+               "mhmr_linear_bf16")
+    return Y
+
+
+def linear_bf16_backward_input(dY, W, dR=None, stream=None):
+    """``mhmr_linear_bf16_backward_input``: dX [M, K] = r(dY [M, N]) r(W [N, K]) (+ dR, added in fp32)."""
+    dY, W = _f32(dY), _f32(W)
+    dR = None if dR is None else _f32(dR)
+    (M, N), K = dY.shape, W.shape[1]
+    dX = torch.empty(M, K, dtype=torch.float32, device=dY.device)
+    nbytes = _lib.workspace_bytes("mhmr_linear_bf16_workspace_bytes", M, N, K)
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dY.device)
+    stream = torch.cuda.current_stream(dY.device).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().mhmr_linear_bf16_backward_input(dY.data_ptr(), N, W.data_ptr(), K, _lib.ptr(dR), K, dX.data_ptr(), K, M, N, K, wsb.data_ptr(),
+                                                          nbytes, stream), "mhmr_linear_bf16_backward_input")
+    return dX
+
+
+def linear_bf16_backward_weight(dY, X, stream=None):
+    """``mhmr_linear_bf16_backward_weight``: (dW [N, K] = r(dY [M, N])^T r(X [M, K]), db [N] = the fp64 column sums of the unrounded dY)."""
+    dY, X = _f32(dY), _f32(X)
+    (M, N), K = dY.shape, X.shape[1]
+    dW = torch.empty(N, K, dtype=torch.float32, device=dY.device)
+    db = torch.empty(N, dtype=torch.float32, device=dY.device)
+    nbytes = _lib.workspace_bytes("mhmr_linear_bf16_workspace_bytes", M, N, K)
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dY.device)
+    stream = torch.cuda.current_stream(dY.device).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().mhmr_linear_bf16_backward_weight(dY.data_ptr(), N, X.data_ptr(), K, dW.data_ptr(), K, db.data_ptr(), M, N, K, wsb.data_ptr(),
+                                                           nbytes, stream), "mhmr_linear_bf16_backward_weight")
+    return dW, db
+
+
+def block_backward(params: dict, x_in, g_out, B, T, Tp, H, stream=None, precision="f32"):
     """``mhmr_vit_block_backward`` on device tensors: ``params`` = {descriptor field: fp32 tensor} (``block_tensors``), x_in and g_out
-    [B*Tp, C] -> (g_in [B*Tp, C], {field: gradient of the parameter's shape})."""
+    [B*Tp, C] -> (g_in [B*Tp, C], {field: gradient of the parameter's shape}).  ``precision``: "f32" (the exact linears) or "bf16"
+    (bf16 operands, fp32 accumulation)."""
     L = _lib.lib()
+    prec = _lib.bwd_precision(precision)
     x_in, g_out = _f32(x_in), _f32(g_out)
     dev, Cd = x_in.device, x_in.shape[1]
     grads = {f: torch.empty_like(params[f]) for f in _lib.VitBlockBackwardDesc.PARAMS}
     g_in = torch.empty_like(x_in)
-    nbytes = _lib.workspace_bytes("mhmr_vit_block_backward_workspace_bytes", B, Tp, Cd)
+    nbytes = _lib.workspace_bytes("mhmr_vit_block_backward_workspace_bytes_p", B, Tp, Cd, prec)
     wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     d = fill_block_desc(_lib.VitBlockBackwardDesc(), params, grads, B, T, Tp, Cd, H)
+    d.linear_precision = prec
     d.x_in, d.g_out, d.g_in, d.workspace, d.workspace_bytes = x_in.data_ptr(), g_out.data_ptr(), g_in.data_ptr(), wsb.data_ptr(), nbytes
     stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
     _lib.check(L.mhmr_vit_block_backward(C.byref(d), stream), "mhmr_vit_block_backward")
     return g_in, grads
 
 
-def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H, stream=None):
+def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H, stream=None, precision="f32"):
     """``mhmr_vit_tail_backward`` on device tensors: final norm + the blocks of ``blocks`` ([{descriptor field: fp32 tensor}], first block
     first) at the tapped streams ``tap [n, B*Tp, C]``; ``resid [B*Tp, C]`` the stream the final norm read; ``g_feat [B*N, C]``
-    -> (g_stream [B*Tp, C], g_norm_w, g_norm_b, [{field: gradient}] per block)."""
+    -> (g_stream [B*Tp, C], g_norm_w, g_norm_b, [{field: gradient}] per block).  ``precision``: as in ``block_backward``, for every block."""
     L = _lib.lib()
+    prec = _lib.bwd_precision(precision)
     n, dev, Cd = len(blocks), resid.device, resid.shape[-1]
     g_feat = _f32(g_feat).reshape(B * N, Cd)
     assert tap.dtype == resid.dtype == torch.float32 and tap.is_contiguous() and resid.is_contiguous() and tap.numel() == n * B * Tp * Cd
@@ -126,9 +173,10 @@ def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H,
         fill_block_desc(descs[i], blocks[i], grads[i], B, N + 1, Tp, Cd, H)
     g_norm_w, g_norm_b = torch.empty_like(norm_w), torch.empty_like(norm_b)
     g_stream = torch.empty(B * Tp, Cd, dtype=torch.float32, device=dev)
-    nbytes = _lib.workspace_bytes("mhmr_vit_tail_backward_workspace_bytes", B, Tp, Cd)
+    nbytes = _lib.workspace_bytes("mhmr_vit_tail_backward_workspace_bytes_p", B, Tp, Cd, prec)
     wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     d = _lib.VitTailBackwardDesc()
+    d.linear_precision = prec
     d.B, d.N, d.T, d.Tp, d.C, d.H, d.n = B, N, N + 1, Tp, Cd, H, n
     d.norm_w, d.norm_b, d.blocks = norm_w.data_ptr(), norm_b.data_ptr(), C.cast(descs, C.POINTER(_lib.VitBlockBackwardDesc))
     d.tap, d.resid, d.g_feat = tap.data_ptr(), resid.data_ptr(), g_feat.data_ptr()
@@ -184,7 +232,8 @@ def model_tail_backward(model, P, ws, B, g_feat, n, x=None):
     total = None
     for part in ws["parts"]:
         Bh, i0, bufs = part["B"], part["img0"], part["bufs"]
-        g_stream, gw, gb, grads = tail_backward(norm_w, norm_b, blocks, bufs["tap"], bufs["resid"], g_feat[i0 * N:(i0 + Bh) * N], Bh, N, ws["Tp"], H)
+        g_stream, gw, gb, grads = tail_backward(norm_w, norm_b, blocks, bufs["tap"], bufs["resid"], g_feat[i0 * N:(i0 + Bh) * N], Bh, N, ws["Tp"], H,
+                                                precision=model._backbone_precision)
         flat = [gw, gb] + [g[f] for g in grads for f in _lib.VitBlockBackwardDesc.PARAMS]
         if x is not None:
             ge = embed_backward(x[i0:i0 + Bh], g_stream, Bh, P["G"], M, ws["Tp"])
@@ -244,4 +293,4 @@ def attach(model, P, ws, B, x=None):
 
 
 __all__ = ["BLOCK_FIELDS", "EMBED_FIELDS", "backbone_parameter_names", "embedding_parameter_names", "attention_tape", "attention_backward",
-           "block_tensors", "block_backward", "tail_backward", "embed_backward", "model_tail_backward", "embeddings_on", "attach"]
+           "block_tensors", "linear_bf16", "linear_bf16_backward_input", "linear_bf16_backward_weight", "block_backward", "tail_backward", "embed_backward", "model_tail_backward", "embeddings_on", "attach"]

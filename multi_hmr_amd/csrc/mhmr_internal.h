@@ -196,6 +196,17 @@ int mhmr_launch_cls_linear(const ClsArgs& a, int epi, int dtype, hipStream_t s);
 int mhmr_launch_linear_f32(const float* X, int ldx, const int* row_idx, const float* W, int ldw, const float* bias, const float* R, int ldr,
                            float* Y, int ldy, int M, int N, int K, int act, hipStream_t s);
 int mhmr_launch_layernorm_f32(const float* in, const float* w, const float* b, float* out, int rows, int C, float eps, hipStream_t s);
+// ---- linear_bf16.hip (bf16 operands, fp32 accumulation; arguments validated by the caller: M, N, K multiples of 64, leading dimensions
+// multiples of 4, 16-byte aligned pointers; ws holds mhmr_linear_bf16_bytes(M, N, K), which grows with each of M, N and K)
+long long mhmr_linear_bf16_bytes(long long M, int N, int K);
+int mhmr_launch_linear_bf16(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy, int M, int N, int K, void* ws,
+                            hipStream_t s);
+int mhmr_launch_linear_bf16_bwd_input(const float* dY, int lddy, const float* W, int ldw, const float* dR, int lddr, float* dX, int lddx, int M, int N,
+                                      int K, void* ws, hipStream_t s);
+int mhmr_launch_linear_bf16_bwd_weight(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw, float* db, int M, int N, int K, void* ws,
+                                       hipStream_t s);
+
+// ---- hph.hip, continued
 // The shape rules of the decoder stack and of the whole head that forward and backward share (each entry point adds its own).
 bool mhmr_hph_stack_shape_ok(int dim, int heads, int mlp, int Kc);
 bool mhmr_hph_head_shape_ok(const mhmr_hph_desc* d);

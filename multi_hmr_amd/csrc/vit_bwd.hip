@@ -319,6 +319,15 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(const float* __restrict_
     out[i] = (int)(row % (size_t)Tp) < T ? in[i] : 0.f;
 }
 
+// mixed-precision mode: dh <- dh * gelu'(z) in fp32, in place, in front of the plain bf16 products (the erf form's
+// derivative, the expression of hph_bwd.hip's dact)
+__global__ __launch_bounds__(256) void gelu_bwd_inplace_kernel(float* __restrict__ dh, const float* __restrict__ z, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float v = z[i];
+    dh[i] *= 0.5f * (1.0f + erff(v * 0.70710678118654752440f)) + v * 0.39894228040143267794f * expf(-0.5f * v * v);
+}
+
 __global__ __launch_bounds__(256) void gelu_f32_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = gelu_erf(in[i]);
@@ -396,9 +405,11 @@ int block_shape_rc(int B, int T, int Tp, int C, int H) {
 // the block's workspace: the tape, the cotangents, the statistics and the scratch of the kernels it calls
 struct BlockLayout {
     int nsl;
-    long long xn1, qkv, att, y1, x1, xn2, z1, h, y2, g0, dy, dh, dxn, g1, datt, lse, attn, ln, part, total;
+    long long xn1, qkv, att, y1, x1, xn2, z1, h, y2, g0, dy, dh, dxn, g1, datt, lse, attn, ln, part, lin, total;
 };
-BlockLayout block_layout(int B, int Tp, int C) {
+// precision MHMR_BWD_BF16 appends the workspace of the widest bf16 linear (fc1: [M, 4C] x [4C, C]), which serves all four
+// linears in their three products, one after the other
+BlockLayout block_layout(int B, int Tp, int C, int precision = MHMR_BWD_F32) {
     BlockLayout L;
     WsCursor ws;
     const long long M = (long long)B * Tp, row = M * C * (long long)sizeof(float);
@@ -411,19 +422,22 @@ BlockLayout block_layout(int B, int Tp, int C) {
     L.attn = ws.take(attn_bwd_bytes(B, Tp, C / 64));
     L.ln = ws.take(mhmr_layernorm_f32_backward_workspace_bytes((int)M, C));
     L.part = ws.take((long long)L.nsl * C * 2 * (long long)sizeof(double));
+    L.lin = ws.at;
+    if (precision == MHMR_BWD_BF16) L.lin = ws.take(mhmr_linear_bf16_bytes(M, 4 * C, C));
     L.total = ws.at;
     return L;
 }
+inline bool precision_ok(int p) { return p == MHMR_BWD_F32 || p == MHMR_BWD_BF16; }
 
 // the tail's workspace: the scattered cotangent of the final norm, the second of the two stream cotangents, LayerNorm scratch, one block
 struct TailLayout { long long dy, gy, ln, block, total; };
-TailLayout tail_layout(int B, int Tp, int C) {
+TailLayout tail_layout(int B, int Tp, int C, int precision = MHMR_BWD_F32) {
     TailLayout L;
     WsCursor ws;
     const long long M = (long long)B * Tp, row = M * C * (long long)sizeof(float);
     L.dy = ws.take(row); L.gy = ws.take(row);
     L.ln = ws.take(mhmr_layernorm_f32_backward_workspace_bytes((int)M, C));
-    L.block = ws.take(block_layout(B, Tp, C).total);
+    L.block = ws.take(block_layout(B, Tp, C, precision).total);
     L.total = ws.at;
     return L;
 }
@@ -436,6 +450,10 @@ bool block_tensors_given(const mhmr_vit_block_backward_desc* d) {
     for (const void* q : p)
         if (!q) return false;
     return aligned16(d->qkv_w) && aligned16(d->proj_w) && aligned16(d->fc1_w) && aligned16(d->fc2_w);
+}
+// the bf16 linears read their bias as 16-byte vectors
+bool block_biases_aligned(const mhmr_vit_block_backward_desc* d) {
+    return aligned16(d->qkv_b) && aligned16(d->proj_b) && aligned16(d->fc1_b) && aligned16(d->fc2_b);
 }
 
 // d ls = sum_rows g y, d bias = ls sum_rows g (fp64, two fixed stages), dy = g ls
@@ -484,12 +502,22 @@ long long mhmr_vit_block_backward_workspace_bytes(int B, int Tp, int C) {
     return block_layout(B, Tp, C).total;
 }
 
+long long mhmr_vit_block_backward_workspace_bytes_p(int B, int Tp, int C, int precision) {
+    if (B < 0 || Tp < 0 || C < 0 || !precision_ok(precision)) return MHMR_ERR_BAD_ARG;
+    if (C == 0 || C % 64) return MHMR_ERR_BAD_SHAPE;
+    TRY(block_shape_rc(B, Tp, Tp, C, C / 64));
+    return block_layout(B, Tp, C, precision).total;
+}
+
 int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream) {
     if (!d) return MHMR_ERR_BAD_ARG;
     const int B = d->B, T = d->T, Tp = d->Tp, C = d->C, H = d->H;
     TRY(block_shape_rc(B, T, Tp, C, H));
+    if (!precision_ok(d->linear_precision)) return MHMR_ERR_BAD_ARG;
+    const bool bf = d->linear_precision == MHMR_BWD_BF16;
     if (!block_tensors_given(d) || !d->x_in || !d->g_out || !d->g_in || !aligned16(d->x_in)) return MHMR_ERR_BAD_ARG;
-    const BlockLayout L = block_layout(B, Tp, C);
+    if (bf && !block_biases_aligned(d)) return MHMR_ERR_BAD_ARG;
+    const BlockLayout L = block_layout(B, Tp, C, d->linear_precision);
     if (!d->workspace || !aligned16(d->workspace) || d->workspace_bytes < L.total || d->g_in == d->g_out) return MHMR_ERR_BAD_ARG;
 
     hipStream_t s = (hipStream_t)stream;
@@ -505,34 +533,55 @@ int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream)
     const long long lnbytes = mhmr_layernorm_f32_backward_workspace_bytes(M, C);
     double* part = (double*)(ws + L.part);
     const float eps = 1e-6f;
+    // the three products of a linear without activation, in the descriptor's precision: Y [M, N] = X W^T + bias, dW [N, K] (+ db), dX [M, K]
+    void* lin = ws + L.lin;
+    auto fwd = [&](const float* X, const float* W, const float* bias, float* Y, int N, int K) {
+        return bf ? mhmr_launch_linear_bf16(X, K, W, K, bias, Y, N, M, N, K, lin, s)
+                  : mhmr_launch_linear_f32(X, K, nullptr, W, K, bias, nullptr, 0, Y, N, M, N, K, MHMR_ACT_NONE, s);
+    };
+    auto bwd_w = [&](const float* dY, const float* X, float* dW, float* db, int N, int K) {
+        return bf ? mhmr_launch_linear_bf16_bwd_weight(dY, N, X, K, dW, K, db, M, N, K, lin, s)
+                  : mhmr_linear_f32_backward_weight(dY, N, nullptr, 0, X, K, dW, K, db, M, N, K, MHMR_ACT_NONE, s);
+    };
+    auto bwd_x = [&](const float* dY, const float* W, float* dX, int N, int K) {
+        return bf ? mhmr_launch_linear_bf16_bwd_input(dY, N, W, K, nullptr, 0, dX, K, M, N, K, lin, s)
+                  : mhmr_linear_f32_backward_input(dY, N, nullptr, nullptr, 0, W, K, nullptr, 0, dX, K, M, N, K, MHMR_ACT_NONE, s);
+    };
 
     // ---- the tape: the block's forward in fp32, from x_in
     TRY(mhmr_launch_layernorm_f32(d->x_in, d->ln1_w, d->ln1_b, xn1, M, C, eps, s));
-    TRY(mhmr_launch_linear_f32(xn1, C, nullptr, d->qkv_w, C, d->qkv_b, nullptr, 0, qkv, 3 * C, M, 3 * C, C, MHMR_ACT_NONE, s));
+    TRY(fwd(xn1, d->qkv_w, d->qkv_b, qkv, 3 * C, C));
     TRY(launch_attn_tape(qkv, att, lse, B, T, Tp, C, H, s));
-    TRY(mhmr_launch_linear_f32(att, C, nullptr, d->proj_w, C, d->proj_b, nullptr, 0, y1, C, M, C, C, MHMR_ACT_NONE, s));
+    TRY(fwd(att, d->proj_w, d->proj_b, y1, C, C));
     hipLaunchKernelGGL(layerscale_resid_kernel, dim3(blocks256(n)), dim3(256), 0, s, d->x_in, (const float*)y1, d->ls1, x1, n, C);
     TRY(mhmr_launch_layernorm_f32(x1, d->ln2_w, d->ln2_b, xn2, M, C, eps, s));
-    TRY(mhmr_launch_linear_f32(xn2, C, nullptr, d->fc1_w, C, d->fc1_b, nullptr, 0, z1, 4 * C, M, 4 * C, C, MHMR_ACT_NONE, s));
+    TRY(fwd(xn2, d->fc1_w, d->fc1_b, z1, 4 * C, C));
     hipLaunchKernelGGL(gelu_f32_kernel, dim3(blocks256(4 * n)), dim3(256), 0, s, (const float*)z1, h, 4 * n);
-    TRY(mhmr_launch_linear_f32(h, 4 * C, nullptr, d->fc2_w, 4 * C, d->fc2_b, nullptr, 0, y2, C, M, C, 4 * C, MHMR_ACT_NONE, s));
+    TRY(fwd(h, d->fc2_w, d->fc2_b, y2, C, 4 * C));
 
     // ---- the MLP branch: x2 = x1 + ls2 * fc2(gelu(fc1(norm2(x1))))
     hipLaunchKernelGGL(mask_rows_kernel, dim3(blocks256(n)), dim3(256), 0, s, d->g_out, g0, n, C, T, Tp);
     TRY(launch_layerscale_bwd(g0, y2, d->ls2, dy, d->g_ls2, d->g_fc2_b, M, C, L.nsl, part, s));
-    TRY(mhmr_linear_f32_backward_weight(dy, C, nullptr, 0, h, 4 * C, d->g_fc2_w, 4 * C, nullptr, M, C, 4 * C, MHMR_ACT_NONE, s));
-    TRY(mhmr_linear_f32_backward_input(dy, C, nullptr, nullptr, 0, d->fc2_w, 4 * C, nullptr, 0, dh, 4 * C, M, C, 4 * C, MHMR_ACT_NONE, s));
-    TRY(mhmr_linear_f32_backward_weight(dh, 4 * C, z1, 4 * C, xn2, C, d->g_fc1_w, C, d->g_fc1_b, M, 4 * C, C, MHMR_ACT_GELU, s));
-    TRY(mhmr_linear_f32_backward_input(dh, 4 * C, nullptr, z1, 4 * C, d->fc1_w, C, nullptr, 0, dxn, C, M, 4 * C, C, MHMR_ACT_GELU, s));
+    TRY(bwd_w(dy, h, d->g_fc2_w, nullptr, C, 4 * C));
+    TRY(bwd_x(dy, d->fc2_w, dh, C, 4 * C));
+    if (bf) {
+        // the GELU derivative in fp32 in front of plain products: the rounded operand does not depend on where erf is evaluated
+        hipLaunchKernelGGL(gelu_bwd_inplace_kernel, dim3(blocks256(4 * n)), dim3(256), 0, s, dh, (const float*)z1, 4 * n);
+        TRY(bwd_w(dh, xn2, d->g_fc1_w, d->g_fc1_b, 4 * C, C));
+        TRY(bwd_x(dh, d->fc1_w, dxn, 4 * C, C));
+    } else {
+        TRY(mhmr_linear_f32_backward_weight(dh, 4 * C, z1, 4 * C, xn2, C, d->g_fc1_w, C, d->g_fc1_b, M, 4 * C, C, MHMR_ACT_GELU, s));
+        TRY(mhmr_linear_f32_backward_input(dh, 4 * C, nullptr, z1, 4 * C, d->fc1_w, C, nullptr, 0, dxn, C, M, 4 * C, C, MHMR_ACT_GELU, s));
+    }
     TRY(mhmr_layernorm_f32_backward(x1, d->ln2_w, dxn, g0, g1, d->g_ln2_w, d->g_ln2_b, M, C, eps, lnws, lnbytes, s));
 
     // ---- the attention branch: x1 = x + ls1 * proj(MHSA(norm1(x)))
     TRY(launch_layerscale_bwd(g1, y1, d->ls1, dy, d->g_ls1, d->g_proj_b, M, C, L.nsl, part, s));
-    TRY(mhmr_linear_f32_backward_weight(dy, C, nullptr, 0, att, C, d->g_proj_w, C, nullptr, M, C, C, MHMR_ACT_NONE, s));
-    TRY(mhmr_linear_f32_backward_input(dy, C, nullptr, nullptr, 0, d->proj_w, C, nullptr, 0, datt, C, M, C, C, MHMR_ACT_NONE, s));
+    TRY(bwd_w(dy, att, d->g_proj_w, nullptr, C, C));
+    TRY(bwd_x(dy, d->proj_w, datt, C, C));
     TRY(launch_attn_bwd(qkv, att, lse, datt, C, dqkv, B, T, Tp, C, H, Dws, s));
-    TRY(mhmr_linear_f32_backward_weight(dqkv, 3 * C, nullptr, 0, xn1, C, d->g_qkv_w, C, d->g_qkv_b, M, 3 * C, C, MHMR_ACT_NONE, s));
-    TRY(mhmr_linear_f32_backward_input(dqkv, 3 * C, nullptr, nullptr, 0, d->qkv_w, C, nullptr, 0, dxn, C, M, 3 * C, C, MHMR_ACT_NONE, s));
+    TRY(bwd_w(dqkv, xn1, d->g_qkv_w, d->g_qkv_b, 3 * C, C));
+    TRY(bwd_x(dqkv, d->qkv_w, dxn, 3 * C, C));
     TRY(mhmr_layernorm_f32_backward(d->x_in, d->ln1_w, dxn, g1, d->g_in, d->g_ln1_w, d->g_ln1_b, M, C, eps, lnws, lnbytes, s));
     MHMR_CHECK_LAUNCH();
     return 0;
@@ -545,19 +594,28 @@ long long mhmr_vit_tail_backward_workspace_bytes(int B, int Tp, int C) {
     return tail_layout(B, Tp, C).total;
 }
 
+long long mhmr_vit_tail_backward_workspace_bytes_p(int B, int Tp, int C, int precision) {
+    if (B < 0 || Tp < 0 || C < 0 || !precision_ok(precision)) return MHMR_ERR_BAD_ARG;
+    if (C == 0 || C % 64) return MHMR_ERR_BAD_SHAPE;
+    TRY(block_shape_rc(B, Tp, Tp, C, C / 64));
+    return tail_layout(B, Tp, C, precision).total;
+}
+
 int mhmr_vit_tail_backward(const mhmr_vit_tail_backward_desc* d, void* stream) {
     if (!d) return MHMR_ERR_BAD_ARG;
     const int B = d->B, T = d->T, Tp = d->Tp, C = d->C, H = d->H, n = d->n;
     if (d->N < 0 || n < 0) return MHMR_ERR_BAD_ARG;
     TRY(block_shape_rc(B, T, Tp, C, H));
     if (n == 0 || d->N != T - 1) return MHMR_ERR_BAD_SHAPE;
+    if (!precision_ok(d->linear_precision)) return MHMR_ERR_BAD_ARG;
     if (!d->norm_w || !d->norm_b || !d->blocks || !d->tap || !d->resid || !d->g_feat || !d->g_norm_w || !d->g_norm_b || !d->g_stream)
         return MHMR_ERR_BAD_ARG;
-    const TailLayout L = tail_layout(B, Tp, C);
+    const TailLayout L = tail_layout(B, Tp, C, d->linear_precision);
     if (!d->workspace || !aligned16(d->workspace) || d->workspace_bytes < L.total || !aligned16(d->tap) || !aligned16(d->g_stream))
         return MHMR_ERR_BAD_ARG;
     for (int i = 0; i < n; ++i)
-        if (!block_tensors_given(&d->blocks[i])) return MHMR_ERR_BAD_ARG;
+        if (!block_tensors_given(&d->blocks[i]) || (d->linear_precision == MHMR_BWD_BF16 && !block_biases_aligned(&d->blocks[i])))
+            return MHMR_ERR_BAD_ARG;
 
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d->workspace;
@@ -572,6 +630,7 @@ int mhmr_vit_tail_backward(const mhmr_vit_tail_backward_desc* d, void* stream) {
     for (int k = 0; k < n; ++k) {
         mhmr_vit_block_backward_desc b = d->blocks[n - 1 - k];
         b.B = B; b.T = T; b.Tp = Tp; b.C = C; b.H = H;
+        b.linear_precision = d->linear_precision;      // the tail's own value: the blocks' field is ignored, like their shapes
         b.x_in = d->tap + (size_t)(n - 1 - k) * rows;
         b.g_out = cur(k);
         b.g_in = cur(k + 1);

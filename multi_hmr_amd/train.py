@@ -3,10 +3,13 @@ reference's ``train.py`` ``Trainer``, for what this package trains (DESIGN.md se
 
 Two differences from the reference, both on purpose:
 
-* it trains the heads (``x_attention_head``, ``mlp_offset``) and the detector (``mlp_classif``) on a FROZEN backbone -- the backbone has
-  no backward here -- so the optimiser holds ``model.heads_parameters()`` (+ ``model.detection_parameters()``), not ``model.parameters()``;
-* the master weights are fp32 and there is no autocast / AMP: the 16-bit operands of the forward are the model's packed copies, which the
-  optimiser step rewrites (``HeadsAdam``) or ``repack_heads()`` refreshes (any other ``torch.optim`` optimiser).
+* by default it trains the heads (``x_attention_head``, ``mlp_offset``) and the detector (``mlp_classif``) on a FROZEN backbone, so the
+  optimiser holds ``model.heads_parameters()`` (+ ``model.detection_parameters()``), not ``model.parameters()``; ``--train_backbone N``
+  adds the final norm and the last N encoder blocks (and, with N = the depth, the token embedding) under ``torch.optim.Adam``;
+* the master weights are fp32 and there is no autocast: the 16-bit operands of the forward are the model's packed copies, which the
+  optimiser step rewrites (``HeadsAdam``) or ``repack_heads()`` / ``repack_backbone()`` refresh (any other ``torch.optim`` optimiser).
+  ``--amp 1`` (the reference's default) gives the linears of the backbone BACKWARD bf16 operands with fp32 accumulation (DESIGN.md
+  section 30); the heads' backward and every forward are what they are without it.
 
 The step has one legal order -- forward, ``decode_readout``, loss, ``backward()``, optimiser step, re-pack -- because ``backward()`` reads
 the forward's workspace and the packed weights; ``train_step`` / ``train_step_features`` are that order.  ``data`` is any iterable of
@@ -235,7 +238,7 @@ def build_parser():
     ``max_epochs = max_iter // n_iter`` as the reference does).  The loss weights are ``Loss.add_specific_args``."""
     from argparse import ArgumentParser
     from .loss import Loss
-    p = ArgumentParser(description="Train the heads and the detector of a Multi-HMR checkpoint on a frozen backbone")
+    p = ArgumentParser(description="Train the heads and the detector of a Multi-HMR checkpoint, on a frozen backbone or with its last blocks")
     p.add_argument("--train_data", type=str, default="BEDLAM", choices=["BEDLAM"])
     p.add_argument("--train_split", type=str, default="training")
     p.add_argument("--train_n", type=int, default=-1)
@@ -246,7 +249,11 @@ def build_parser():
     p.add_argument("--val_subsample", type=int, nargs="*", default=None)
     p.add_argument("--save_dir", type=str, default="logs")
     p.add_argument("--name", type=str, default="trainval")
-    p.add_argument("--pretrained", type=str, required=True, help="checkpoint name under models/multiHMR (demo.load_model): the backbone is not trained here")
+    p.add_argument("--pretrained", type=str, required=True, help="checkpoint name under models/multiHMR (demo.load_model); its backbone stays frozen unless --train_backbone is given")
+    p.add_argument("--train_backbone", type=int, default=0,
+                   help="train the final norm and the last N encoder blocks as well (0: frozen backbone; N = the depth also trains the token embedding)")
+    p.add_argument("--amp", type=int, default=1, choices=[0, 1],
+                   help="with --train_backbone: 1 = bf16 operands, fp32 accumulation in the backbone backward's linears, 0 = exact fp32")
     p.add_argument("--batch_size", type=int, default=2)
     p.add_argument("--num_workers", "-j", type=int, default=8)
     p.add_argument("--img_size", type=int, default=None, help="default: the checkpoint's")
@@ -268,9 +275,24 @@ def build_parser():
     return Loss.add_specific_args(p)
 
 
+def make_optimizer(model, args):
+    """The optimiser of the command line.  ``--train_backbone 0``: ``HeadsAdam`` over the heads (and the detector).  ``--train_backbone N``:
+    ``train_backbone_(N, precision="bf16" if --amp else "f32")``, ``train_embeddings_()`` when N is the encoder's depth, and ``torch.optim.Adam``
+    over heads, detector, backbone and embedding parameters (the ``Trainer`` re-packs after each step)."""
+    n, detection = int(getattr(args, "train_backbone", 0) or 0), bool(args.train_detection)
+    if n <= 0:
+        return HeadsAdam(model, lr=args.learning_rate, detection=detection)
+    model.train_backbone_(n, precision="bf16" if int(getattr(args, "amp", 1)) else "f32")
+    params = model.heads_parameters() + (model.detection_parameters() if detection else []) + model.backbone_parameters(n)
+    if n == len(model.backbone.encoder.blocks):
+        model.train_embeddings_()
+        params += model.embedding_parameters()
+    return torch.optim.Adam(params, lr=args.learning_rate)
+
+
 def main(argv=None):
-    """``python -m multi_hmr_amd.train --pretrained NAME ...``: ``load_model`` -> ``train_heads_`` / ``train_detection_`` -> ``HeadsAdam`` ->
-    ``Trainer.fit`` over a ``TrainLoader`` of the training set, with one loader per validation set."""
+    """``python -m multi_hmr_amd.train --pretrained NAME ...``: ``load_model`` -> ``train_heads_`` / ``train_detection_`` -> ``make_optimizer``
+    -> ``Trainer.fit`` over a ``TrainLoader`` of the training set, with one loader per validation set."""
     from . import data
     from .bodymodel import BodyModel
     from .demo import load_model
@@ -283,7 +305,7 @@ def main(argv=None):
     model = load_model(args.pretrained, device=device, **({} if args.img_size is None else {"img_size": args.img_size}))
     args.img_size = S = int(model.img_size)
     model = model.eval().train_heads_(True).train_detection_(bool(args.train_detection))
-    optimizer = HeadsAdam(model, lr=args.learning_rate, detection=bool(args.train_detection))
+    optimizer = make_optimizer(model, args)
     body = lambda *parts: os.path.join(args.smplx_dir, *parts)
     smpl = {g: (BodyModel(body("smpl", f"SMPL_{g.upper()}.pkl"), "smpl", num_betas=10) if os.path.isfile(body("smpl", f"SMPL_{g.upper()}.pkl")) else None)
             for g in ("male", "female")}
@@ -308,7 +330,7 @@ def main(argv=None):
     return trainer
 
 
-__all__ = ["AverageMeter", "Trainer", "build_parser", "main"]
+__all__ = ["AverageMeter", "Trainer", "build_parser", "make_optimizer", "main"]
 
 
 if __name__ == "__main__":

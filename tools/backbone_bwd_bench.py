@@ -12,7 +12,12 @@ One JSON line per measurement, printed and appended to --out (default profiles/b
 --embed: instead, one line per configuration for the backward of the token embedding
   embed_bwd       mhmr_vit_embed_backward through backbone_train.embed_backward, stored table 37 x 37
 appended to --embed-out (default profiles/embed_bwd_bench.txt).
-  python tools/backbone_bwd_bench.py [--config all|vitl_896_8|vitl_896_32|vits_672_16] [--reps 3] [--warmup 1] [--skip-model] [--embed]"""
+--precision bf16 (default f32 = the lines above, unchanged): block_bwd is timed in BOTH forms, alternating inside
+every repetition (block_bwd = f32, block_bwd_bf16), a line `linears_bf16` times the twelve products of a block (four linears x forward,
+input side, weight side, conversions included) on the bf16 entries with their rate against the dense bf16 peak, and the model's
+train_step runs with train_backbone_(1, precision="bf16").  Default --out is then profiles/backbone_bwd_bench_bf16.txt.
+  python tools/backbone_bwd_bench.py [--config all|vitl_896_8|vitl_896_32|vits_672_16] [--reps 3] [--warmup 1] [--skip-model] [--embed]
+                                     [--precision f32|bf16]"""
 import argparse
 import json
 import os
@@ -31,6 +36,7 @@ from multi_hmr_amd.constants import VIT_CFG  # noqa: E402
 from eval_bench import DEV, report  # noqa: E402
 
 FP32_MFMA_FLOPS = 155e12
+BF16_MFMA_FLOPS = 2.5e15            # dense bf16 matrix peak of the MI355X
 CONFIGS = {"vitl_896_8": ("dinov2_vitl14", 896, 8), "vitl_896_32": ("dinov2_vitl14", 896, 32), "vits_672_16": ("dinov2_vits14", 672, 16)}
 
 
@@ -73,13 +79,53 @@ def kernels(name, backbone, S, B, a):
                   proj_b=0.1 * rn(Cd), ls1=0.5 + 0.1 * rn(Cd), ln2_w=1 + 0.1 * rn(Cd), ln2_b=0.1 * rn(Cd), fc1_w=rn(4 * Cd, Cd) * Cd ** -0.5,
                   fc1_b=0.1 * rn(4 * Cd), fc2_w=rn(Cd, 4 * Cd) * (4 * Cd) ** -0.5, fc2_b=0.1 * rn(Cd), ls2=0.5 + 0.1 * rn(Cd))
     x_in, g_out = rn(M, Cd), rn(M, Cd)
-    ms = timed({"block_bwd": lambda: bt.block_backward(params, x_in, g_out, B, T, Tp, H)}, a)
+    forms = {"block_bwd": lambda: bt.block_backward(params, x_in, g_out, B, T, Tp, H)}
+    if a.precision == "bf16":
+        forms["block_bwd_bf16"] = lambda: bt.block_backward(params, x_in, g_out, B, T, Tp, H, precision="bf16")
+    ms = timed(forms, a)
     lin = 3 * 2.0 * M * 12 * Cd * Cd                       # tape, input side and weight side of the four linears
+    if a.precision == "bf16":
+        lines.append(linears_bf16(shape, params, M, Cd, lin, a))
+        lines.append(report("block_backward_bf16", ms, dict(shape, workspace_bytes=int(_lib.lib().mhmr_vit_block_backward_workspace_bytes_p(B, Tp, Cd, 1)),
+                                                            workspace_bytes_f32=int(_lib.lib().mhmr_vit_block_backward_workspace_bytes(B, Tp, Cd)),
+                                                            linear_gflop=round(lin / 1e9, 1), attention_gflop=round(18 * unit / 1e9, 1),
+                                                            median_ratio_f32_over_bf16=round(med(ms["block_bwd"]) / med(ms["block_bwd_bf16"]), 2),
+                                                            note="tape + backward in both forms, alternating; attention, LayerNorm and the column "
+                                                                 "sums are the fp32 kernels in both")))
+        return lines
     lines.append(report("block_backward", ms, dict(shape, workspace_bytes=int(_lib.lib().mhmr_vit_block_backward_workspace_bytes(B, Tp, Cd)),
                                                    linear_gflop=round(lin / 1e9, 1), attention_gflop=round(18 * unit / 1e9, 1),
                                                    fraction_of_fp32_mfma_peak=round((lin + 18 * unit) / FP32_MFMA_FLOPS / (med(ms["block_bwd"]) * 1e-3), 4),
                                                    note="tape + backward; the linears run on the person head's fp32 kernels (16-row tiles)")))
     return lines
+
+
+def linears_bf16(shape, params, M, Cd, lin_flop, a):
+    """The twelve products of a block on the bf16 entries (conversions included), preallocated operands and workspace."""
+    L = _lib.lib()
+    g = torch.Generator(device=DEV).manual_seed(6)
+    act = torch.randn(M, 4 * Cd, generator=g, device=DEV)       # every activation / cotangent is a view of these two
+    cot = torch.randn(M, 4 * Cd, generator=g, device=DEV)
+    out = torch.empty(M, 4 * Cd, device=DEV)
+    dW, db = torch.empty(4 * Cd * Cd, device=DEV), torch.empty(4 * Cd, device=DEV)
+    nbytes = int(L.mhmr_linear_bf16_workspace_bytes(M, 4 * Cd, Cd))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    s = lambda: torch.cuda.current_stream().cuda_stream
+    shapes = [("qkv_w", 3 * Cd, Cd), ("proj_w", Cd, Cd), ("fc1_w", 4 * Cd, Cd), ("fc2_w", Cd, 4 * Cd)]
+
+    def run():
+        for f, N, K in shapes:
+            W = params[f]
+            _lib.check(L.mhmr_linear_bf16(act.data_ptr(), 4 * Cd, W.data_ptr(), K, None, out.data_ptr(), 4 * Cd, M, N, K, ws.data_ptr(), nbytes, s()), f)
+            _lib.check(L.mhmr_linear_bf16_backward_input(cot.data_ptr(), 4 * Cd, W.data_ptr(), K, None, 0, out.data_ptr(), 4 * Cd, M, N, K, ws.data_ptr(),
+                                                         nbytes, s()), f)
+            _lib.check(L.mhmr_linear_bf16_backward_weight(cot.data_ptr(), 4 * Cd, act.data_ptr(), 4 * Cd, dW.data_ptr(), K, db.data_ptr(), M, N, K,
+                                                          ws.data_ptr(), nbytes, s()), f)
+    ms = timed({"linears_bf16": run}, a)
+    t = sorted(ms["linears_bf16"])[len(ms["linears_bf16"]) // 2] * 1e-3
+    return report("linears_bf16", ms, dict(shape, linear_gflop=round(lin_flop / 1e9, 1), tflops=round(lin_flop / t / 1e12, 1),
+                                           fraction_of_bf16_mfma_peak=round(lin_flop / BF16_MFMA_FLOPS / t, 4), workspace_bytes=nbytes,
+                                           note="4 linears x (forward, input side, weight side + bias sums), fp32 -> bf16 conversions included"))
 
 
 def embed(name, backbone, S, B, a):
@@ -102,7 +148,7 @@ def model_level(name, backbone, S, B, a):
     smplx_data, mean_params = synthetic.make_smplx_data(0), synthetic.make_mean_params(0)
     m = Model(backbone=backbone, img_size=S, smplx_data=smplx_data, mean_params=mean_params, precision="f16")
     m.load_state_dict(synthetic.make_state_dict(backbone, S, seed=0, mean_params=mean_params), strict=True)
-    m = m.to(DEV).eval().train_backbone_(1)
+    m = m.to(DEV).eval().train_backbone_(1, precision=a.precision)
     G = S // 14
     x = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(0)).to(DEV)
     K = synthetic.get_camera_K(S, B).to(DEV)
@@ -117,6 +163,7 @@ def model_level(name, backbone, S, B, a):
     ms = timed({"forward": lambda: m(x, idx=idx, K=K, is_training=True), "train_step": step}, a)
     med = lambda v: sorted(v)[len(v) // 2]
     return [report("model", ms, dict(config=name, backbone=backbone, size=S, images=B, dtype=m.packed_precision, trainable_blocks=1,
+                                     **({"backward_precision": a.precision} if a.precision != "f32" else {}),
                                      image_blocks=m._nsplit(B), median_ratio_train_step_over_forward=round(med(ms["train_step"]) / med(ms["forward"]), 2),
                                      note="train_step = the forward with the tap + backward of a random-cotangent scalar on the scores (detector's "
                                           "feature cotangent, final norm, one block); no optimiser step, no re-pack"))]
@@ -148,10 +195,13 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--skip-model", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "backbone_bwd_bench.txt"))
+    ap.add_argument("--precision", default="f32", choices=["f32", "bf16"], help="bf16: also time the bf16-operand form (section 30)")
+    ap.add_argument("--out", default=None, help="default profiles/backbone_bwd_bench.txt (profiles/backbone_bwd_bench_bf16.txt with --precision bf16)")
     ap.add_argument("--embed", action="store_true", help="time the embedding backward (section 29) instead, appended to --embed-out")
     ap.add_argument("--embed-out", default=os.path.join(ROOT, "profiles", "embed_bwd_bench.txt"))
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "backbone_bwd_bench_bf16.txt" if a.precision == "bf16" else "backbone_bwd_bench.txt")
     if not torch.cuda.is_available():
         raise SystemExit("backbone_bwd_bench measures on the GPU; there is none here")
     main(a)
