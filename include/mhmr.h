@@ -927,8 +927,9 @@ int mhmr_rotvec_to_rotmat(const float* rotvec, int n, float* rotmat, void* strea
  *   sampled at (c + 0.5, r + 0.5); faces with a vertex at Z < znear are dropped; back faces
  *   (dot((b-a) x (c-a), a) >= 0) culled if cull_back; coverage: edge functions > 0, or == 0 on a top-left edge;
  *   the winner of a pixel is the smallest key (float_bits(Z) << 32) | (p F + f), Z perspective-correct, kept
- *   only if znear <= Z <= zfar; glTF metallic-roughness shading with one directional light along the view
- *   axis plus ambient; the reference's 3x3 mask smoothing; the fp32 alpha blend, every operation rounded.
+ *   only if znear <= (float)Z <= zfar (the fp32 depth of the key against the fp32 fields below); glTF
+ *   metallic-roughness shading with one directional light along the view axis plus ambient; the reference's 3x3
+ *   mask smoothing; the fp32 alpha blend, every operation rounded.
  * Geometry (transform, projection, edge functions, depth) is fp64; shading and the blend are fp32.
  * verts: person p's vertex v at verts[p * vstride + 3 v + axis] (vstride >= 3 V: the v3d block is read in place).
  * adj_off [V + 1] / adj: for every vertex the (3 face + corner) entries of its incident faces, ascending

@@ -263,8 +263,9 @@ __device__ inline void raster_pixel(const RenderArgs& a, const Tri& t, unsigned 
     double e[3], w[3];
     if (!tri_cover(t, x + 0.5, y + 0.5, e)) return;
     const double Z = tri_depth(t, e, w);
-    if (!(Z >= a.znear && Z <= a.zfar)) return;
-    const unsigned long long k = ((unsigned long long)__float_as_uint((float)Z) << 32) | id;
+    const float zf = (float)Z;                                          // the depth the key holds is the depth that is clipped:
+    if (!(zf >= a.znear && zf <= a.zfar)) return;                       // a face lying on a clip plane keeps all its pixels
+    const unsigned long long k = ((unsigned long long)__float_as_uint(zf) << 32) | id;
     unsigned long long* dst = key_img + (size_t)y * a.W + x;
     if (k < *dst) atomicMin(dst, k);                                    // the plain read only skips atomics that cannot win
 }

@@ -7,8 +7,8 @@ Render contract (one sample per pixel; this text defines the output, and the CPU
 1. Camera: per image K [3, 3] (fx = K00, fy = K11, cx = K02, cy = K12, skew ignored) and optional R [3, 3], t [3]; a vertex
    moves to camera coordinates as X = R x + t (OpenCV: X right, Y down, Z forward), u = fx X / Z + cx, v = fy Y / Z + cy.
    Pixel (row r, col c) is sampled at (c + 0.5, r + 0.5).
-2. Clipping: znear = 0.05, zfar = 100.  A face with any vertex at Z < znear is dropped, not clipped (a deviation from GL);
-   a fragment is kept only if znear <= Z <= zfar.
+2. Clipping: znear = fl32(0.05), zfar = 100.  A face with any vertex at Z < znear is dropped, not clipped (a deviation from GL);
+   a fragment is kept only if znear <= fl32(Z) <= zfar, the depth its key holds: a face lying on a clip plane keeps every pixel.
 3. Culling (cull_back=True): face (a, b, c) is culled when dot((b - a) x (c - a), a) >= 0 in camera coordinates.
 4. Coverage: a pixel centre is inside if all three edge functions are > 0, or = 0 on a top-left edge; edges shared by two
    faces are evaluated with their endpoints in one fixed order, so such a pixel is covered exactly once.  Zero-area faces

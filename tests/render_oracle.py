@@ -8,7 +8,7 @@ from __future__ import annotations
 import numpy as np
 
 KEY_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
-ZNEAR, ZFAR = 0.05, 100.0
+ZNEAR, ZFAR = float(np.float32(0.05)), 100.0                       # the clip planes are the descriptor's fp32 fields
 
 
 def camera_vertices(x, R=None, t=None):
@@ -140,9 +140,11 @@ def raster(X, faces, K, H, W, id_base=0, keys=None, znear=ZNEAR, zfar=ZFAR, cull
         cov = np.all((e > 0) | ((e == 0) & t["tl"][fi]), axis=1)
         fi, x, y, e = fi[cov], x[cov], y[cov], e[cov]
         Z, _ = depth(t, fi, e)
+        with np.errstate(over="ignore", invalid="ignore"):
+            Z = Z.astype(np.float32)                               # the depth the key holds is the depth that is clipped
         ok = (Z >= znear) & (Z <= zfar)
         fi, x, y, Z = fi[ok], x[ok], y[ok], Z[ok]
-        key = (Z.astype(np.float32).view(np.uint32).astype(np.uint64) << np.uint64(32)) | (t["idx"][fi] + id_base).astype(np.uint64)
+        key = (Z.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (t["idx"][fi] + id_base).astype(np.uint64)
         np.minimum.at(flat, y * W + x, key)
         start = stop
     return keys

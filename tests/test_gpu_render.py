@@ -65,6 +65,8 @@ def check_against_oracle(images, verts, image_index, K, faces, colors, alpha=0.8
         dk = key[b]
         bad = np.argwhere(dk != okeys)
         covered = int((okeys != KEY_NONE).sum())
+        print(f"FORGIVEN image {b}: {len(bad)} of {covered} covered pixels differ from the oracle "
+              f"({images.shape[1]}x{images.shape[2]}, P={len(ps)}, F={F})")
         assert len(bad) <= max(0.001 * covered, 0), (b, len(bad), covered)
         for y, x in bad:
             ok = False
