@@ -1259,6 +1259,51 @@ int mhmr_linear_bf16_backward_input(const float* dY, int lddy, const float* W, i
 int mhmr_linear_bf16_backward_weight(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw, float* db, int M,
                                      int N, int K, void* workspace, long long workspace_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Attention with bf16 operands for mixed-precision training: the tape and the backward of the
+ * self-attention on v_mfma_f32_16x16x32_bf16.  Every tensor is fp32 in the layouts of mhmr_attention_f32_tape / _backward;
+ * r() is round-to-nearest-even fp32 -> bf16.  Per (image, head), over the T real rows:
+ *     S_ij  = MHMR_ATTN_QSCALE * sum_d r(Q_i[d]) r(K_j[d])     fp32 accumulation, S is NOT rounded
+ *     lse_i = log2 sum_j exp2(S_ij)                            P_ij = exp2(S_ij - lse_i): normalised by the final lse
+ *     O_i   = sum_j r(P_ij) r(V_j)                             -> out32 (fp32, not rounded)
+ *     D_i   = sum_d dO_i[d] O_i[d]                             fp32, the UNROUNDED dO and the tape's out32, fixed order
+ *     dP_ij = sum_d r(dO_i[d]) r(V_j[d])                       dS_ij = P_ij (dP_ij - D_i)
+ *     dV_j  = sum_i r(P_ij) r(dO_i)     dQ_i = 0.125 sum_j r(dS_ij) r(K_j)     dK_j = 0.125 sum_i r(dS_ij) r(Q_i)
+ * The rounded probability is the normalised one -- a function of the inputs, not of a tile order: the tape sweeps the keys
+ * twice (S and the log-sum, then S again, r(exp2(S - lse)) and the product with V), and the backward recomputes S with the
+ * same products and uses the tape's lse.  Against torch autocast, which rounds q k^T to 16 bits in front of the softmax, S
+ * stays fp32: a deviation on the accurate side.  D is the row sum of dO . O, so out32 IS read by this backward.
+ *   mhmr_attention_bf16_workspace_bytes: one size for both entries (the bf16 copies of qkv and dO, as they lie and
+ *       transposed, and D [B, H, Tp]).
+ *   mhmr_attention_bf16_tape:     qkv [B*Tp, 3C] -> out32 [B*Tp, C], lse [B, H, Tp].
+ *   mhmr_attention_bf16_backward: qkv, out32, lse, dO [B*Tp, lddo] -> dqkv [B*Tp, 3C].  Converts on its own: it does not need
+ *       the tape to have run on the same workspace.
+ * Invariants (those of the fp32 pair): keys and queries at rows >= T are masked; whatever finite values (finite as bf16) qkv,
+ * dO and out32 hold at rows >= T moves no bit of a real row; rows >= T of out32, lse and dqkv are exact zeros; every element
+ * of every output is written; no floating-point atomics; the order of every fp32 accumulation (ascending tiles of 64 keys or
+ * queries) is fixed by (T, Tp) alone, so two calls give the same bits and an image does not depend on the others; no
+ * allocation, no synchronisation, all validation before the first launch.
+ * Shapes and errors: those of the fp32 pair, and B * Tp at most 64 * 65535; a workspace below
+ * mhmr_attention_bf16_workspace_bytes(B, Tp, C, H) or not 16-byte aligned: MHMR_ERR_BAD_ARG.
+ *
+ * In the block and the tail the switch is an argument of appended entries (the descriptors are closed):
+ * mhmr_vit_block_backward(d, s) == mhmr_vit_block_backward_a(d, MHMR_ATTN_F32, s), likewise the tail, which hands its value to
+ * every block; with MHMR_ATTN_BF16 the attention tape and backward of the block are the two entries above and the workspace must
+ * hold ..._workspace_bytes_pa(B, Tp, C, linear_precision, MHMR_ATTN_BF16); ..._pa(.., p, MHMR_ATTN_F32) == ..._p(.., p).  The two
+ * switches are independent.  Any other attention_precision: MHMR_ERR_BAD_ARG.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define MHMR_ATTN_F32 0
+#define MHMR_ATTN_BF16 1
+long long mhmr_attention_bf16_workspace_bytes(int B, int Tp, int C, int H);
+int mhmr_attention_bf16_tape(const float* qkv, float* out32, float* lse, int B, int T, int Tp, int C, int H, void* workspace,
+                             long long workspace_bytes, void* stream);
+int mhmr_attention_bf16_backward(const float* qkv, const float* out32, const float* lse, const float* dO, int lddo, float* dqkv,
+                                 int B, int T, int Tp, int C, int H, void* workspace, long long workspace_bytes, void* stream);
+long long mhmr_vit_block_backward_workspace_bytes_pa(int B, int Tp, int C, int linear_precision, int attention_precision);
+long long mhmr_vit_tail_backward_workspace_bytes_pa(int B, int Tp, int C, int linear_precision, int attention_precision);
+int mhmr_vit_block_backward_a(const mhmr_vit_block_backward_desc* d, int attention_precision, void* stream);
+int mhmr_vit_tail_backward_a(const mhmr_vit_tail_backward_desc* d, int attention_precision, void* stream);
+
 /* The token embedding: the derivative of the fp32 function
  *     tokens[b] = [ patchify(x[b]) W^T + bias + pos_G[1:],  cls + pos_G[0] ],   pos_G = interpolate(pos_embed)
  * at the fp32 master parameters and the fp32 image, against g_stream, the cotangent of the stream entering block 0 (what

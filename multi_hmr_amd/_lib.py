@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -46,8 +46,9 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  scene.hip: the same fp64 geometry.
 #: loss.hip: every element of the training loss is the reference's fp32 subtraction(s), rounded one by one (its sign is the gradient).
 #: optim.hip: the Adam update is torch's sequence of fp32 operations, each rounded on its own.
+#: attention_bf16.hip: the logit S = fl(QSCALE * acc) is rounded before exp2(S - lse) in all three kernels, as the contract states it.
 EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
-               "optim.hip": ["-ffp-contract=off"]}
+               "optim.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -287,6 +288,17 @@ def bwd_precision(name) -> int:
     return BWD_PRECISIONS[name]
 
 
+ATTN_F32, ATTN_BF16 = 0, 1          # include/mhmr.h MHMR_ATTN_*: attention_precision of the ..._a / ..._pa entries
+ATTN_PRECISIONS = {"f32": ATTN_F32, "bf16": ATTN_BF16}
+
+
+def attn_precision(name) -> int:
+    """MHMR_ATTN_* of an attention precision name of the backbone backward ("f32" or "bf16"); ``ValueError`` for anything else."""
+    if name not in ATTN_PRECISIONS:
+        raise ValueError(f"attention must be one of {sorted(ATTN_PRECISIONS)}, not {name!r}")
+    return ATTN_PRECISIONS[name]
+
+
 class VitEmbedBackwardDesc(C.Structure):
     """include/mhmr.h mhmr_vit_embed_backward_desc: the image, the cotangent of the stream entering block 0, the resampling matrix and one
     gradient buffer for each of patch_embed.proj.weight / .bias, cls_token and pos_embed."""
@@ -396,6 +408,13 @@ _SIGS = {
     "mhmr_linear_bf16": ([_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
     "mhmr_linear_bf16_backward_input": ([_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
     "mhmr_linear_bf16_backward_weight": ([_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
+    "mhmr_attention_bf16_workspace_bytes": ([_i, _i, _i, _i], C.c_longlong),
+    "mhmr_attention_bf16_tape": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
+    "mhmr_attention_bf16_backward": ([_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),
+    "mhmr_vit_block_backward_workspace_bytes_pa": ([_i, _i, _i, _i, _i], C.c_longlong),
+    "mhmr_vit_tail_backward_workspace_bytes_pa": ([_i, _i, _i, _i, _i], C.c_longlong),
+    "mhmr_vit_block_backward_a": ([C.POINTER(VitBlockBackwardDesc), _i, _vp], _i),
+    "mhmr_vit_tail_backward_a": ([C.POINTER(VitTailBackwardDesc), _i, _vp], _i),
     "mhmr_vit_embed_backward_workspace_bytes": ([_i, _i, _i, _i], C.c_longlong),
     "mhmr_vit_embed_backward": ([C.POINTER(VitEmbedBackwardDesc), _vp], _i),
     "mhmr_prof_enable": ([_i], _i),

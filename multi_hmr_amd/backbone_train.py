@@ -3,7 +3,9 @@ image, in fp32 at the fp32 master weights, evaluated at the residual stream the 
 
 The functions here run the kernels of csrc/vit_bwd.hip on device tensors and allocate their outputs and workspaces.  There is no CPU
 path.  ``precision="bf16"`` gives the linears of a block bf16 operands with fp32 accumulation (csrc/linear_bf16.hip),
-in the recomputed tape and in both backward products; attention, LayerNorm and the column sums stay exact, and ``"f32"`` is the default.  Token rows follow the forward's layout: ``Tp`` rows per image, patch rows first, the class token at row ``N = T - 1``, padding
+in the recomputed tape and in both backward products; attention, LayerNorm and the column sums stay exact, and ``"f32"`` is the default.
+``attention="bf16"`` is the independent switch of the attention tape and backward: bf16 operands, fp32 accumulation,
+fp32 logits (csrc/attention_bf16.hip; ``attention_bf16_tape`` / ``attention_bf16_backward`` run the pair on its own).  Token rows follow the forward's layout: ``Tp`` rows per image, patch rows first, the class token at row ``N = T - 1``, padding
 behind it."""
 from __future__ import annotations
 
@@ -76,6 +78,37 @@ def attention_backward(qkv, out32, lse, dO, B, T, Tp, H, stream=None, dqkv=None)
     return dqkv
 
 
+def attention_bf16_tape(qkv, B, T, Tp, H, stream=None):
+    """``mhmr_attention_bf16_tape``: qkv [B*Tp, 3C] fp32 -> (out32 [B*Tp, C], lse [B, H, Tp]) with bf16 operands."""
+    qkv = _f32(qkv)
+    dev, Cd = qkv.device, qkv.shape[1] // 3
+    out32 = torch.empty(B * Tp, Cd, dtype=torch.float32, device=dev)
+    lse = torch.empty(B, H, Tp, dtype=torch.float32, device=dev)
+    nbytes = _lib.workspace_bytes("mhmr_attention_bf16_workspace_bytes", B, Tp, Cd, H)
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(_lib.lib().mhmr_attention_bf16_tape(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), B, T, Tp, Cd, H, wsb.data_ptr(), nbytes, stream),
+               "mhmr_attention_bf16_tape")
+    return out32, lse
+
+
+def attention_bf16_backward(qkv, out32, lse, dO, B, T, Tp, H, stream=None, dqkv=None):
+    """``mhmr_attention_bf16_backward``: -> dqkv [B*Tp, 3C] with respect to the un-scaled Q, K and V; ``out32`` and ``lse`` are the tape's."""
+    L = _lib.lib()
+    qkv, out32, lse = _f32(qkv), _f32(out32), _f32(lse)
+    dev, Cd = qkv.device, qkv.shape[1] // 3
+    if dO.dtype != torch.float32 or dO.stride(-1) != 1:
+        dO = _f32(dO)
+    if dqkv is None:
+        dqkv = torch.empty(B * Tp, 3 * Cd, dtype=torch.float32, device=dev)
+    nbytes = _lib.workspace_bytes("mhmr_attention_bf16_workspace_bytes", B, Tp, Cd, H)
+    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(L.mhmr_attention_bf16_backward(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), dO.data_ptr(), dO.stride(0), dqkv.data_ptr(), B,
+                                              T, Tp, Cd, H, wsb.data_ptr(), nbytes, stream), "mhmr_attention_bf16_backward")
+    return dqkv
+
+
 def block_tensors(block, device=None) -> dict:
     """{descriptor field: fp32 contiguous tensor} of a block module with DINOv2's parameter names (the nn.Parameters themselves when they
     already are fp32, contiguous and on the device)."""
@@ -138,32 +171,33 @@ def linear_bf16_backward_weight(dY, X, stream=None):
     return dW, db
 
 
-def block_backward(params: dict, x_in, g_out, B, T, Tp, H, stream=None, precision="f32"):
+def block_backward(params: dict, x_in, g_out, B, T, Tp, H, stream=None, precision="f32", attention="f32"):
     """``mhmr_vit_block_backward`` on device tensors: ``params`` = {descriptor field: fp32 tensor} (``block_tensors``), x_in and g_out
     [B*Tp, C] -> (g_in [B*Tp, C], {field: gradient of the parameter's shape}).  ``precision``: "f32" (the exact linears) or "bf16"
-    (bf16 operands, fp32 accumulation)."""
+    (bf16 operands, fp32 accumulation).  ``attention``: the same two names for the attention tape and backward
+    (DESIGN.md section 31)."""
     L = _lib.lib()
-    prec = _lib.bwd_precision(precision)
+    prec, att = _lib.bwd_precision(precision), _lib.attn_precision(attention)
     x_in, g_out = _f32(x_in), _f32(g_out)
     dev, Cd = x_in.device, x_in.shape[1]
     grads = {f: torch.empty_like(params[f]) for f in _lib.VitBlockBackwardDesc.PARAMS}
     g_in = torch.empty_like(x_in)
-    nbytes = _lib.workspace_bytes("mhmr_vit_block_backward_workspace_bytes_p", B, Tp, Cd, prec)
+    nbytes = _lib.workspace_bytes("mhmr_vit_block_backward_workspace_bytes_pa", B, Tp, Cd, prec, att)
     wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     d = fill_block_desc(_lib.VitBlockBackwardDesc(), params, grads, B, T, Tp, Cd, H)
     d.linear_precision = prec
     d.x_in, d.g_out, d.g_in, d.workspace, d.workspace_bytes = x_in.data_ptr(), g_out.data_ptr(), g_in.data_ptr(), wsb.data_ptr(), nbytes
     stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(L.mhmr_vit_block_backward(C.byref(d), stream), "mhmr_vit_block_backward")
+    _lib.check(L.mhmr_vit_block_backward_a(C.byref(d), att, stream), "mhmr_vit_block_backward_a")
     return g_in, grads
 
 
-def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H, stream=None, precision="f32"):
+def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H, stream=None, precision="f32", attention="f32"):
     """``mhmr_vit_tail_backward`` on device tensors: final norm + the blocks of ``blocks`` ([{descriptor field: fp32 tensor}], first block
     first) at the tapped streams ``tap [n, B*Tp, C]``; ``resid [B*Tp, C]`` the stream the final norm read; ``g_feat [B*N, C]``
-    -> (g_stream [B*Tp, C], g_norm_w, g_norm_b, [{field: gradient}] per block).  ``precision``: as in ``block_backward``, for every block."""
+    -> (g_stream [B*Tp, C], g_norm_w, g_norm_b, [{field: gradient}] per block).  ``precision``, ``attention``: as in ``block_backward``, for every block."""
     L = _lib.lib()
-    prec = _lib.bwd_precision(precision)
+    prec, att = _lib.bwd_precision(precision), _lib.attn_precision(attention)
     n, dev, Cd = len(blocks), resid.device, resid.shape[-1]
     g_feat = _f32(g_feat).reshape(B * N, Cd)
     assert tap.dtype == resid.dtype == torch.float32 and tap.is_contiguous() and resid.is_contiguous() and tap.numel() == n * B * Tp * Cd
@@ -173,7 +207,7 @@ def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H,
         fill_block_desc(descs[i], blocks[i], grads[i], B, N + 1, Tp, Cd, H)
     g_norm_w, g_norm_b = torch.empty_like(norm_w), torch.empty_like(norm_b)
     g_stream = torch.empty(B * Tp, Cd, dtype=torch.float32, device=dev)
-    nbytes = _lib.workspace_bytes("mhmr_vit_tail_backward_workspace_bytes_p", B, Tp, Cd, prec)
+    nbytes = _lib.workspace_bytes("mhmr_vit_tail_backward_workspace_bytes_pa", B, Tp, Cd, prec, att)
     wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     d = _lib.VitTailBackwardDesc()
     d.linear_precision = prec
@@ -182,7 +216,7 @@ def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H,
     d.tap, d.resid, d.g_feat = tap.data_ptr(), resid.data_ptr(), g_feat.data_ptr()
     d.g_norm_w, d.g_norm_b, d.g_stream, d.workspace, d.workspace_bytes = g_norm_w.data_ptr(), g_norm_b.data_ptr(), g_stream.data_ptr(), wsb.data_ptr(), nbytes
     stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(L.mhmr_vit_tail_backward(C.byref(d), stream), "mhmr_vit_tail_backward")
+    _lib.check(L.mhmr_vit_tail_backward_a(C.byref(d), att, stream), "mhmr_vit_tail_backward_a")
     return g_stream, g_norm_w, g_norm_b, grads
 
 
@@ -233,7 +267,7 @@ def model_tail_backward(model, P, ws, B, g_feat, n, x=None):
     for part in ws["parts"]:
         Bh, i0, bufs = part["B"], part["img0"], part["bufs"]
         g_stream, gw, gb, grads = tail_backward(norm_w, norm_b, blocks, bufs["tap"], bufs["resid"], g_feat[i0 * N:(i0 + Bh) * N], Bh, N, ws["Tp"], H,
-                                                precision=model._backbone_precision)
+                                                precision=model._backbone_precision, attention=model._backbone_attention)
         flat = [gw, gb] + [g[f] for g in grads for f in _lib.VitBlockBackwardDesc.PARAMS]
         if x is not None:
             ge = embed_backward(x[i0:i0 + Bh], g_stream, Bh, P["G"], M, ws["Tp"])
@@ -292,5 +326,5 @@ def attach(model, P, ws, B, x=None):
         return _TailFunction.apply(model, st, *[p for _, p in named])
 
 
-__all__ = ["BLOCK_FIELDS", "EMBED_FIELDS", "backbone_parameter_names", "embedding_parameter_names", "attention_tape", "attention_backward",
+__all__ = ["BLOCK_FIELDS", "EMBED_FIELDS", "backbone_parameter_names", "embedding_parameter_names", "attention_tape", "attention_backward", "attention_bf16_tape", "attention_bf16_backward",
            "block_tensors", "linear_bf16", "linear_bf16_backward_input", "linear_bf16_backward_weight", "block_backward", "tail_backward", "embed_backward", "model_tail_backward", "embeddings_on", "attach"]

@@ -213,13 +213,17 @@ int shape_rc(long long M, int N, int K) {
 }
 inline bool ld_ok(int ld, int row) { return ld >= row && ld % 4 == 0; }
 
-void launch_to_bf16(const float* in, int ld, __bf16* out, int rows, int cols, bool transposed, hipStream_t s) {
+}  // namespace
+
+void mhmr_launch_to_bf16(const float* in, int ld, __bf16* out, int rows, int cols, bool transposed, hipStream_t s) {
     if (transposed) hipLaunchKernelGGL(to_bf16_t_kernel, dim3(cols / 64, rows / 64), dim3(256), 0, s, in, ld, out, rows);
     else {
         const size_t n4 = (size_t)rows * (cols / 4);
         hipLaunchKernelGGL(to_bf16_kernel, dim3(blocks256(n4)), dim3(256), 0, s, in, ld, out, cols, n4, cols / 4);
     }
 }
+
+namespace {
 
 // ready bf16 operands: out[z][i][j] = sum over slice z of P[i][s] Q[j][s] (+ bias[j]) (+ R[i][j]); nsl == 1: the whole sum
 void launch_nt(const __bf16* P, int ldp, const __bf16* Q, int ldq, float* out, int ldo, int I, int J, int S, int nsl, int sslice,
@@ -238,8 +242,8 @@ int mhmr_launch_linear_bf16(const float* X, int ldx, const float* W, int ldw, co
     const LinLayout L = lin_layout(M, N, K);
     char* ws = (char*)ws_;
     __bf16 *xb = (__bf16*)(ws + L.opa), *wb = (__bf16*)(ws + L.opb);
-    launch_to_bf16(X, ldx, xb, M, K, false, s);
-    launch_to_bf16(W, ldw, wb, N, K, false, s);
+    mhmr_launch_to_bf16(X, ldx, xb, M, K, false, s);
+    mhmr_launch_to_bf16(W, ldw, wb, N, K, false, s);
     launch_nt(xb, K, wb, K, Y, ldy, M, N, K, 1, K, bias, nullptr, 0, s);
     MHMR_CHECK_LAUNCH();
     return 0;
@@ -250,8 +254,8 @@ int mhmr_launch_linear_bf16_bwd_input(const float* dY, int lddy, const float* W,
     const LinLayout L = lin_layout(M, N, K);
     char* ws = (char*)ws_;
     __bf16 *gb = (__bf16*)(ws + L.opa), *wt = (__bf16*)(ws + L.opb);
-    launch_to_bf16(dY, lddy, gb, M, N, false, s);
-    launch_to_bf16(W, ldw, wt, N, K, true, s);                               // W^T [K, N]
+    mhmr_launch_to_bf16(dY, lddy, gb, M, N, false, s);
+    mhmr_launch_to_bf16(W, ldw, wt, N, K, true, s);                          // W^T [K, N]
     launch_nt(gb, N, wt, N, dX, lddx, M, K, N, 1, N, nullptr, dR, lddr, s);
     MHMR_CHECK_LAUNCH();
     return 0;
@@ -265,8 +269,8 @@ int mhmr_launch_linear_bf16_bwd_weight(const float* dY, int lddy, const float* X
         __bf16 *gt = (__bf16*)(ws + L.opa), *xt = (__bf16*)(ws + L.opb);
         float* part = (float*)(ws + L.part);
         const int nsl = weight_slices(M);
-        launch_to_bf16(dY, lddy, gt, M, N, true, s);                         // dY^T [N, M]
-        launch_to_bf16(X, ldx, xt, M, K, true, s);                           // X^T  [K, M]
+        mhmr_launch_to_bf16(dY, lddy, gt, M, N, true, s);                    // dY^T [N, M]
+        mhmr_launch_to_bf16(X, ldx, xt, M, K, true, s);                      // X^T  [K, M]
         launch_nt(gt, M, xt, M, part, K, N, K, M, nsl, WSLICE, nullptr, nullptr, 0, s);
         hipLaunchKernelGGL(slices_finish_kernel, dim3(blocks256((size_t)N * K)), dim3(256), 0, s, (const float*)part, dW, lddw, nsl, N, K);
     }

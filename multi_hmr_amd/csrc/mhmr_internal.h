@@ -199,12 +199,21 @@ int mhmr_launch_layernorm_f32(const float* in, const float* w, const float* b, f
 // ---- linear_bf16.hip (bf16 operands, fp32 accumulation; arguments validated by the caller: M, N, K multiples of 64, leading dimensions
 // multiples of 4, 16-byte aligned pointers; ws holds mhmr_linear_bf16_bytes(M, N, K), which grows with each of M, N and K)
 long long mhmr_linear_bf16_bytes(long long M, int N, int K);
+// the bf16 copy of an fp32 matrix [rows, cols] (multiples of 64; ld % 4 == 0): as it lies, out [rows, cols], or transposed, out [cols, rows]
+void mhmr_launch_to_bf16(const float* in, int ld, __bf16* out, int rows, int cols, bool transposed, hipStream_t s);
 int mhmr_launch_linear_bf16(const float* X, int ldx, const float* W, int ldw, const float* bias, float* Y, int ldy, int M, int N, int K, void* ws,
                             hipStream_t s);
 int mhmr_launch_linear_bf16_bwd_input(const float* dY, int lddy, const float* W, int ldw, const float* dR, int lddr, float* dX, int lddx, int M, int N,
                                       int K, void* ws, hipStream_t s);
 int mhmr_launch_linear_bf16_bwd_weight(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw, float* db, int M, int N, int K, void* ws,
                                        hipStream_t s);
+
+// ---- attention_bf16.hip (the attention tape and backward with bf16 operands; arguments validated by the caller as the extern "C" entries
+// do; ws holds mhmr_attention_bf16_bytes(B, Tp, C).  qkv_ready: the tape has run on this workspace with this qkv, its bf16 copy is kept)
+long long mhmr_attention_bf16_bytes(int B, int Tp, int C);
+int mhmr_launch_attention_bf16_tape(const float* qkv, float* out32, float* lse, int B, int T, int Tp, int C, int H, void* ws, hipStream_t s);
+int mhmr_launch_attention_bf16_bwd(const float* qkv, const float* out32, const float* lse, const float* dO, int lddo, float* dqkv, int B, int T,
+                                   int Tp, int C, int H, void* ws, bool qkv_ready, hipStream_t s);
 
 // ---- hph.hip, continued
 // The shape rules of the decoder stack and of the whole head that forward and backward share (each entry point adds its own).

@@ -22,6 +22,8 @@
 // A column of an MFMA result depends on that column of B alone, so a row >= T inside a tile (any finite values) reaches no real row: its
 // own p and dS are replaced by zeros where it is the summed index, and its own result is stored as zeros.  dQ and dK carry the factor
 // head_dim^-0.5 = 1/8, exact.
+// attention_precision = MHMR_ATTN_BF16 of the `_a` entries replaces this pair, inside the block, by the bf16-operand
+// pair of attention_bf16.hip; MHMR_ATTN_F32, and the entries without the argument, issue exactly the launches described here.
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
 #include "row_sums.h"
@@ -405,11 +407,13 @@ int block_shape_rc(int B, int T, int Tp, int C, int H) {
 // the block's workspace: the tape, the cotangents, the statistics and the scratch of the kernels it calls
 struct BlockLayout {
     int nsl;
-    long long xn1, qkv, att, y1, x1, xn2, z1, h, y2, g0, dy, dh, dxn, g1, datt, lse, attn, ln, part, lin, total;
+    long long xn1, qkv, att, y1, x1, xn2, z1, h, y2, g0, dy, dh, dxn, g1, datt, lse, attn, ln, part, lin, attn16, total;
 };
 // precision MHMR_BWD_BF16 appends the workspace of the widest bf16 linear (fc1: [M, 4C] x [4C, C]), which serves all four
 // linears in their three products, one after the other
-BlockLayout block_layout(int B, int Tp, int C, int precision = MHMR_BWD_F32) {
+// attention MHMR_ATTN_BF16 appends, behind that, the workspace of the bf16 attention pair (attention_bf16.hip): the tape's bf16 copy of
+// qkv stays there for the backward
+BlockLayout block_layout(int B, int Tp, int C, int precision = MHMR_BWD_F32, int attention = MHMR_ATTN_F32) {
     BlockLayout L;
     WsCursor ws;
     const long long M = (long long)B * Tp, row = M * C * (long long)sizeof(float);
@@ -424,20 +428,23 @@ BlockLayout block_layout(int B, int Tp, int C, int precision = MHMR_BWD_F32) {
     L.part = ws.take((long long)L.nsl * C * 2 * (long long)sizeof(double));
     L.lin = ws.at;
     if (precision == MHMR_BWD_BF16) L.lin = ws.take(mhmr_linear_bf16_bytes(M, 4 * C, C));
+    L.attn16 = ws.at;
+    if (attention == MHMR_ATTN_BF16) L.attn16 = ws.take(mhmr_attention_bf16_bytes(B, Tp, C));
     L.total = ws.at;
     return L;
 }
 inline bool precision_ok(int p) { return p == MHMR_BWD_F32 || p == MHMR_BWD_BF16; }
+inline bool attention_ok(int a) { return a == MHMR_ATTN_F32 || a == MHMR_ATTN_BF16; }
 
 // the tail's workspace: the scattered cotangent of the final norm, the second of the two stream cotangents, LayerNorm scratch, one block
 struct TailLayout { long long dy, gy, ln, block, total; };
-TailLayout tail_layout(int B, int Tp, int C, int precision = MHMR_BWD_F32) {
+TailLayout tail_layout(int B, int Tp, int C, int precision = MHMR_BWD_F32, int attention = MHMR_ATTN_F32) {
     TailLayout L;
     WsCursor ws;
     const long long M = (long long)B * Tp, row = M * C * (long long)sizeof(float);
     L.dy = ws.take(row); L.gy = ws.take(row);
     L.ln = ws.take(mhmr_layernorm_f32_backward_workspace_bytes((int)M, C));
-    L.block = ws.take(block_layout(B, Tp, C, precision).total);
+    L.block = ws.take(block_layout(B, Tp, C, precision, attention).total);
     L.total = ws.at;
     return L;
 }
@@ -509,15 +516,25 @@ long long mhmr_vit_block_backward_workspace_bytes_p(int B, int Tp, int C, int pr
     return block_layout(B, Tp, C, precision).total;
 }
 
-int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream) {
+long long mhmr_vit_block_backward_workspace_bytes_pa(int B, int Tp, int C, int linear_precision, int attention_precision) {
+    if (B < 0 || Tp < 0 || C < 0 || !precision_ok(linear_precision) || !attention_ok(attention_precision)) return MHMR_ERR_BAD_ARG;
+    if (C == 0 || C % 64) return MHMR_ERR_BAD_SHAPE;
+    TRY(block_shape_rc(B, Tp, Tp, C, C / 64));
+    return block_layout(B, Tp, C, linear_precision, attention_precision).total;
+}
+
+int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream) { return mhmr_vit_block_backward_a(d, MHMR_ATTN_F32, stream); }
+
+int mhmr_vit_block_backward_a(const mhmr_vit_block_backward_desc* d, int attention_precision, void* stream) {
     if (!d) return MHMR_ERR_BAD_ARG;
     const int B = d->B, T = d->T, Tp = d->Tp, C = d->C, H = d->H;
     TRY(block_shape_rc(B, T, Tp, C, H));
-    if (!precision_ok(d->linear_precision)) return MHMR_ERR_BAD_ARG;
+    if (!precision_ok(d->linear_precision) || !attention_ok(attention_precision)) return MHMR_ERR_BAD_ARG;
+    const bool abf = attention_precision == MHMR_ATTN_BF16;
     const bool bf = d->linear_precision == MHMR_BWD_BF16;
     if (!block_tensors_given(d) || !d->x_in || !d->g_out || !d->g_in || !aligned16(d->x_in)) return MHMR_ERR_BAD_ARG;
     if (bf && !block_biases_aligned(d)) return MHMR_ERR_BAD_ARG;
-    const BlockLayout L = block_layout(B, Tp, C, d->linear_precision);
+    const BlockLayout L = block_layout(B, Tp, C, d->linear_precision, attention_precision);
     if (!d->workspace || !aligned16(d->workspace) || d->workspace_bytes < L.total || d->g_in == d->g_out) return MHMR_ERR_BAD_ARG;
 
     hipStream_t s = (hipStream_t)stream;
@@ -551,7 +568,8 @@ int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream)
     // ---- the tape: the block's forward in fp32, from x_in
     TRY(mhmr_launch_layernorm_f32(d->x_in, d->ln1_w, d->ln1_b, xn1, M, C, eps, s));
     TRY(fwd(xn1, d->qkv_w, d->qkv_b, qkv, 3 * C, C));
-    TRY(launch_attn_tape(qkv, att, lse, B, T, Tp, C, H, s));
+    if (abf) TRY(mhmr_launch_attention_bf16_tape(qkv, att, lse, B, T, Tp, C, H, ws + L.attn16, s));
+    else TRY(launch_attn_tape(qkv, att, lse, B, T, Tp, C, H, s));
     TRY(fwd(att, d->proj_w, d->proj_b, y1, C, C));
     hipLaunchKernelGGL(layerscale_resid_kernel, dim3(blocks256(n)), dim3(256), 0, s, d->x_in, (const float*)y1, d->ls1, x1, n, C);
     TRY(mhmr_launch_layernorm_f32(x1, d->ln2_w, d->ln2_b, xn2, M, C, eps, s));
@@ -579,7 +597,8 @@ int mhmr_vit_block_backward(const mhmr_vit_block_backward_desc* d, void* stream)
     TRY(launch_layerscale_bwd(g1, y1, d->ls1, dy, d->g_ls1, d->g_proj_b, M, C, L.nsl, part, s));
     TRY(bwd_w(dy, att, d->g_proj_w, nullptr, C, C));
     TRY(bwd_x(dy, d->proj_w, datt, C, C));
-    TRY(launch_attn_bwd(qkv, att, lse, datt, C, dqkv, B, T, Tp, C, H, Dws, s));
+    if (abf) TRY(mhmr_launch_attention_bf16_bwd(qkv, att, lse, datt, C, dqkv, B, T, Tp, C, H, ws + L.attn16, true, s));
+    else TRY(launch_attn_bwd(qkv, att, lse, datt, C, dqkv, B, T, Tp, C, H, Dws, s));
     TRY(bwd_w(dqkv, xn1, d->g_qkv_w, d->g_qkv_b, 3 * C, C));
     TRY(bwd_x(dqkv, d->qkv_w, dxn, 3 * C, C));
     TRY(mhmr_layernorm_f32_backward(d->x_in, d->ln1_w, dxn, g1, d->g_in, d->g_ln1_w, d->g_ln1_b, M, C, eps, lnws, lnbytes, s));
@@ -601,16 +620,25 @@ long long mhmr_vit_tail_backward_workspace_bytes_p(int B, int Tp, int C, int pre
     return tail_layout(B, Tp, C, precision).total;
 }
 
-int mhmr_vit_tail_backward(const mhmr_vit_tail_backward_desc* d, void* stream) {
+long long mhmr_vit_tail_backward_workspace_bytes_pa(int B, int Tp, int C, int linear_precision, int attention_precision) {
+    if (B < 0 || Tp < 0 || C < 0 || !precision_ok(linear_precision) || !attention_ok(attention_precision)) return MHMR_ERR_BAD_ARG;
+    if (C == 0 || C % 64) return MHMR_ERR_BAD_SHAPE;
+    TRY(block_shape_rc(B, Tp, Tp, C, C / 64));
+    return tail_layout(B, Tp, C, linear_precision, attention_precision).total;
+}
+
+int mhmr_vit_tail_backward(const mhmr_vit_tail_backward_desc* d, void* stream) { return mhmr_vit_tail_backward_a(d, MHMR_ATTN_F32, stream); }
+
+int mhmr_vit_tail_backward_a(const mhmr_vit_tail_backward_desc* d, int attention_precision, void* stream) {
     if (!d) return MHMR_ERR_BAD_ARG;
     const int B = d->B, T = d->T, Tp = d->Tp, C = d->C, H = d->H, n = d->n;
     if (d->N < 0 || n < 0) return MHMR_ERR_BAD_ARG;
     TRY(block_shape_rc(B, T, Tp, C, H));
     if (n == 0 || d->N != T - 1) return MHMR_ERR_BAD_SHAPE;
-    if (!precision_ok(d->linear_precision)) return MHMR_ERR_BAD_ARG;
+    if (!precision_ok(d->linear_precision) || !attention_ok(attention_precision)) return MHMR_ERR_BAD_ARG;
     if (!d->norm_w || !d->norm_b || !d->blocks || !d->tap || !d->resid || !d->g_feat || !d->g_norm_w || !d->g_norm_b || !d->g_stream)
         return MHMR_ERR_BAD_ARG;
-    const TailLayout L = tail_layout(B, Tp, C, d->linear_precision);
+    const TailLayout L = tail_layout(B, Tp, C, d->linear_precision, attention_precision);
     if (!d->workspace || !aligned16(d->workspace) || d->workspace_bytes < L.total || !aligned16(d->tap) || !aligned16(d->g_stream))
         return MHMR_ERR_BAD_ARG;
     for (int i = 0; i < n; ++i)
@@ -636,7 +664,7 @@ int mhmr_vit_tail_backward(const mhmr_vit_tail_backward_desc* d, void* stream) {
         b.g_in = cur(k + 1);
         b.workspace = ws + L.block;
         b.workspace_bytes = L.total - L.block;
-        TRY(mhmr_vit_block_backward(&b, s));
+        TRY(mhmr_vit_block_backward_a(&b, attention_precision, s));
     }
     MHMR_CHECK_LAUNCH();
     return 0;

@@ -260,6 +260,7 @@ class Model(nn.Module):
     """A ViT backbone followed by the HPH head and the SMPL-X layer, on hand-written gfx950 kernels."""
     _backbone_n = 1         # blocks a train_backbone forward taps (train_backbone_)
     _backbone_precision = "f32"     # the linears of the backbone backward: "f32" exact, "bf16" bf16 operands (train_backbone_)
+    _backbone_attention = "f32"     # its attention tape and backward: "f32" exact, "bf16" bf16 operands (train_backbone_)
 
     def __init__(self, backbone="dinov2_vitb14", pretrained_backbone=False, img_size=896, camera_embedding="geometric",
                  camera_embedding_num_bands=16, camera_embedding_max_resolution=64, nearness=True, xat_depth=2,
@@ -472,19 +473,24 @@ class Model(nn.Module):
         params = dict(self.named_parameters())
         return [params[k] for k in backbone_parameter_names(len(self.backbone.encoder.blocks), n)]
 
-    def train_backbone_(self, n=1, flag=True, precision=None):
+    def train_backbone_(self, n=1, flag=True, precision=None, attention=None):
         """Set ``requires_grad`` of ``backbone_parameters(n)`` (``1 <= n <= depth``) and remember ``n``: a ``train_backbone=True`` forward
         taps the residual stream in front of the last ``n`` blocks and its backward stops there.  ``precision``: the linears of that
         backward -- ``"f32"`` (the initial setting; exact fp32) or ``"bf16"`` (bf16 operands, fp32 accumulation: what the reference's
-        ``--amp 1`` makes of them); ``None`` keeps the current setting, anything else raises ``ValueError``.  The
-        forward does not depend on it.  Returns self."""
+        ``--amp 1`` makes of them); ``None`` keeps the current setting, anything else raises ``ValueError``.
+        ``attention``: the attention tape and backward of that backward, with the same three cases -- ``"bf16"`` gives every product of
+        the attention bf16 operands.  A ``ValueError`` changes nothing.  The forward depends on neither.  Returns self."""
         if precision is not None:
             _lib.bwd_precision(precision)
+        if attention is not None:
+            _lib.attn_precision(attention)
         for p in self.backbone_parameters(n):
             p.requires_grad_(bool(flag))
         self._backbone_n = int(n)
         if precision is not None:
             self._backbone_precision = precision
+        if attention is not None:
+            self._backbone_attention = attention
         return self
 
     def embedding_parameters(self):

@@ -9,7 +9,8 @@ Two differences from the reference, both on purpose:
 * the master weights are fp32 and there is no autocast: the 16-bit operands of the forward are the model's packed copies, which the
   optimiser step rewrites (``HeadsAdam``) or ``repack_heads()`` / ``repack_backbone()`` refresh (any other ``torch.optim`` optimiser).
   ``--amp 1`` (the reference's default) gives the linears of the backbone BACKWARD bf16 operands with fp32 accumulation (DESIGN.md
-  section 30); the heads' backward and every forward are what they are without it.
+  section 30), ``--amp_attention 1`` (default 0) its attention tape and backward as well (section 31); the heads' backward and every
+  forward are what they are without them.
 
 The step has one legal order -- forward, ``decode_readout``, loss, ``backward()``, optimiser step, re-pack -- because ``backward()`` reads
 the forward's workspace and the packed weights; ``train_step`` / ``train_step_features`` are that order.  ``data`` is any iterable of
@@ -254,6 +255,8 @@ def build_parser():
                    help="train the final norm and the last N encoder blocks as well (0: frozen backbone; N = the depth also trains the token embedding)")
     p.add_argument("--amp", type=int, default=1, choices=[0, 1],
                    help="with --train_backbone: 1 = bf16 operands, fp32 accumulation in the backbone backward's linears, 0 = exact fp32")
+    p.add_argument("--amp_attention", type=int, default=0, choices=[0, 1],
+                   help="with --train_backbone: 1 = bf16 operands in the backbone backward's attention tape and backward as well, 0 = exact fp32")
     p.add_argument("--batch_size", type=int, default=2)
     p.add_argument("--num_workers", "-j", type=int, default=8)
     p.add_argument("--img_size", type=int, default=None, help="default: the checkpoint's")
@@ -277,12 +280,13 @@ def build_parser():
 
 def make_optimizer(model, args):
     """The optimiser of the command line.  ``--train_backbone 0``: ``HeadsAdam`` over the heads (and the detector).  ``--train_backbone N``:
-    ``train_backbone_(N, precision="bf16" if --amp else "f32")``, ``train_embeddings_()`` when N is the encoder's depth, and ``torch.optim.Adam``
+    ``train_backbone_(N, precision="bf16" if --amp else "f32", attention="bf16" if --amp_attention else "f32")``, ``train_embeddings_()`` when N is the encoder's depth, and ``torch.optim.Adam``
     over heads, detector, backbone and embedding parameters (the ``Trainer`` re-packs after each step)."""
     n, detection = int(getattr(args, "train_backbone", 0) or 0), bool(args.train_detection)
     if n <= 0:
         return HeadsAdam(model, lr=args.learning_rate, detection=detection)
-    model.train_backbone_(n, precision="bf16" if int(getattr(args, "amp", 1)) else "f32")
+    model.train_backbone_(n, precision="bf16" if int(getattr(args, "amp", 1)) else "f32",
+                          attention="bf16" if int(getattr(args, "amp_attention", 0)) else "f32")
     params = model.heads_parameters() + (model.detection_parameters() if detection else []) + model.backbone_parameters(n)
     if n == len(model.backbone.encoder.blocks):
         model.train_embeddings_()

@@ -16,8 +16,14 @@ appended to --embed-out (default profiles/embed_bwd_bench.txt).
 every repetition (block_bwd = f32, block_bwd_bf16), a line `linears_bf16` times the twelve products of a block (four linears x forward,
 input side, weight side, conversions included) on the bf16 entries with their rate against the dense bf16 peak, and the model's
 train_step runs with train_backbone_(1, precision="bf16").  Default --out is then profiles/backbone_bwd_bench_bf16.txt.
+--attention bf16 (default f32 = the lines above, unchanged): per configuration a line `attention_bf16` with the
+tape and the attention backward in BOTH forms (mhmr_attention_f32_* and mhmr_attention_bf16_*, alternating inside every repetition, the
+wrappers' workspace allocation inside the bracket) and a line `block_backward_bf16_attention` with the block in three forms, alternating:
+block_bwd (f32), block_bwd_bf16 (bf16 linears) and block_bwd_bf16_attention (bf16 linears and bf16 attention), with the three workspace
+sizes; the model's train_step runs with train_backbone_(1, precision=--precision, attention="bf16").  Default --out is then
+profiles/backbone_bwd_bench_bf16_attention.txt.
   python tools/backbone_bwd_bench.py [--config all|vitl_896_8|vitl_896_32|vits_672_16] [--reps 3] [--warmup 1] [--skip-model] [--embed]
-                                     [--precision f32|bf16]"""
+                                     [--precision f32|bf16] [--attention f32|bf16]"""
 import argparse
 import json
 import os
@@ -65,6 +71,8 @@ def kernels(name, backbone, S, B, a):
     shape = dict(config=name, backbone=backbone, size=S, images=B, T=T, Tp=Tp, C=Cd, H=H)
     qkv, dO = rn(M, 3 * Cd), rn(M, Cd)
     qkv[:, :Cd] *= 2.0
+    if a.attention == "bf16":
+        return attention_bf16_lines(shape, qkv, dO, rn, a)
     out32, lse = bt.attention_tape(qkv, B, T, Tp, H)
     dqkv = torch.empty(M, 3 * Cd, device=DEV)
     ms = timed({"tape": lambda: bt.attention_tape(qkv, B, T, Tp, H),
@@ -97,6 +105,49 @@ def kernels(name, backbone, S, B, a):
                                                    linear_gflop=round(lin / 1e9, 1), attention_gflop=round(18 * unit / 1e9, 1),
                                                    fraction_of_fp32_mfma_peak=round((lin + 18 * unit) / FP32_MFMA_FLOPS / (med(ms["block_bwd"]) * 1e-3), 4),
                                                    note="tape + backward; the linears run on the person head's fp32 kernels (16-row tiles)")))
+    return lines
+
+
+def block_params(rn, Cd):
+    return dict(ln1_w=1 + 0.1 * rn(Cd), ln1_b=0.1 * rn(Cd), qkv_w=rn(3 * Cd, Cd) * Cd ** -0.5, qkv_b=0.1 * rn(3 * Cd), proj_w=rn(Cd, Cd) * Cd ** -0.5,
+                proj_b=0.1 * rn(Cd), ls1=0.5 + 0.1 * rn(Cd), ln2_w=1 + 0.1 * rn(Cd), ln2_b=0.1 * rn(Cd), fc1_w=rn(4 * Cd, Cd) * Cd ** -0.5,
+                fc1_b=0.1 * rn(4 * Cd), fc2_w=rn(Cd, 4 * Cd) * (4 * Cd) ** -0.5, fc2_b=0.1 * rn(Cd), ls2=0.5 + 0.1 * rn(Cd))
+
+
+def attention_bf16_lines(shape, qkv, dO, rn, a):
+    """The attention pair and the block with and without bf16-operand attention, the forms alternating."""
+    L = _lib.lib()
+    B, T, Tp, Cd, H = shape["images"], shape["T"], shape["Tp"], shape["C"], shape["H"]
+    M = B * Tp
+    med = lambda v: sorted(v)[len(v) // 2]
+    o32, l32 = bt.attention_tape(qkv, B, T, Tp, H)
+    o16, l16 = bt.attention_bf16_tape(qkv, B, T, Tp, H)
+    dqkv = torch.empty(M, 3 * Cd, device=DEV)
+    ms = timed({"tape": lambda: bt.attention_tape(qkv, B, T, Tp, H), "tape_bf16": lambda: bt.attention_bf16_tape(qkv, B, T, Tp, H),
+                "attention_bwd": lambda: bt.attention_backward(qkv, o32, l32, dO, B, T, Tp, H, dqkv=dqkv),
+                "attention_bwd_bf16": lambda: bt.attention_bf16_backward(qkv, o16, l16, dO, B, T, Tp, H, dqkv=dqkv)}, a)
+    unit = float(B) * H * T * T * 64
+    lines = [report("attention_bf16", ms, dict(shape, tape_gflop=round(6 * unit / 1e9, 1), backward_gflop=round(18 * unit / 1e9, 1),
+                                               workspace_bytes=int(L.mhmr_attention_bf16_workspace_bytes(B, Tp, Cd, H)),
+                                               workspace_bytes_f32=int(L.mhmr_attention_f32_backward_workspace_bytes(B, Tp, H)),
+                                               tape_bf16_tflops=round(6 * unit / (med(ms["tape_bf16"]) * 1e-3) / 1e12, 1),
+                                               backward_bf16_tflops=round(18 * unit / (med(ms["attention_bwd_bf16"]) * 1e-3) / 1e12, 1),
+                                               median_ratio_tape_f32_over_bf16=round(med(ms["tape"]) / med(ms["tape_bf16"]), 2),
+                                               median_ratio_backward_f32_over_bf16=round(med(ms["attention_bwd"]) / med(ms["attention_bwd_bf16"]), 2),
+                                               note="the bf16 flop counts are the products the kernels compute (the tape S twice, the backward S and "
+                                                    "dP twice); its times include the fp32 -> bf16 conversions"))]
+    del o32, l32, o16, l16, dqkv
+    params = block_params(rn, Cd)
+    x_in, g_out = rn(M, Cd), rn(M, Cd)
+    ms = timed({"block_bwd": lambda: bt.block_backward(params, x_in, g_out, B, T, Tp, H),
+                "block_bwd_bf16": lambda: bt.block_backward(params, x_in, g_out, B, T, Tp, H, precision="bf16"),
+                "block_bwd_bf16_attention": lambda: bt.block_backward(params, x_in, g_out, B, T, Tp, H, precision="bf16", attention="bf16")}, a)
+    wsb = L.mhmr_vit_block_backward_workspace_bytes_pa
+    lines.append(report("block_backward_bf16_attention", ms, dict(
+        shape, workspace_bytes_f32=int(wsb(B, Tp, Cd, 0, 0)), workspace_bytes_bf16=int(wsb(B, Tp, Cd, 1, 0)), workspace_bytes=int(wsb(B, Tp, Cd, 1, 1)),
+        median_ratio_bf16_over_bf16_attention=round(med(ms["block_bwd_bf16"]) / med(ms["block_bwd_bf16_attention"]), 2),
+        median_ratio_f32_over_bf16_attention=round(med(ms["block_bwd"]) / med(ms["block_bwd_bf16_attention"]), 2),
+        note="tape + backward in three forms, alternating: exact fp32, bf16 linears, bf16 linears and bf16 attention")))
     return lines
 
 
@@ -148,7 +199,7 @@ def model_level(name, backbone, S, B, a):
     smplx_data, mean_params = synthetic.make_smplx_data(0), synthetic.make_mean_params(0)
     m = Model(backbone=backbone, img_size=S, smplx_data=smplx_data, mean_params=mean_params, precision="f16")
     m.load_state_dict(synthetic.make_state_dict(backbone, S, seed=0, mean_params=mean_params), strict=True)
-    m = m.to(DEV).eval().train_backbone_(1, precision=a.precision)
+    m = m.to(DEV).eval().train_backbone_(1, precision=a.precision, attention=a.attention)
     G = S // 14
     x = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(0)).to(DEV)
     K = synthetic.get_camera_K(S, B).to(DEV)
@@ -164,6 +215,7 @@ def model_level(name, backbone, S, B, a):
     med = lambda v: sorted(v)[len(v) // 2]
     return [report("model", ms, dict(config=name, backbone=backbone, size=S, images=B, dtype=m.packed_precision, trainable_blocks=1,
                                      **({"backward_precision": a.precision} if a.precision != "f32" else {}),
+                                     **({"backward_attention": a.attention} if a.attention != "f32" else {}),
                                      image_blocks=m._nsplit(B), median_ratio_train_step_over_forward=round(med(ms["train_step"]) / med(ms["forward"]), 2),
                                      note="train_step = the forward with the tap + backward of a random-cotangent scalar on the scores (detector's "
                                           "feature cotangent, final norm, one block); no optimiser step, no re-pack"))]
@@ -196,12 +248,15 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"], help="bf16: also time the bf16-operand form (section 30)")
-    ap.add_argument("--out", default=None, help="default profiles/backbone_bwd_bench.txt (profiles/backbone_bwd_bench_bf16.txt with --precision bf16)")
+    ap.add_argument("--attention", default="f32", choices=["f32", "bf16"], help="bf16: time the bf16-operand attention next to the others (section 31)")
+    ap.add_argument("--out", default=None, help="default profiles/backbone_bwd_bench.txt (profiles/backbone_bwd_bench_bf16.txt with --precision bf16, "
+                                                "profiles/backbone_bwd_bench_bf16_attention.txt with --attention bf16)")
     ap.add_argument("--embed", action="store_true", help="time the embedding backward (section 29) instead, appended to --embed-out")
     ap.add_argument("--embed-out", default=os.path.join(ROOT, "profiles", "embed_bwd_bench.txt"))
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "backbone_bwd_bench_bf16.txt" if a.precision == "bf16" else "backbone_bwd_bench.txt")
+        a.out = os.path.join(ROOT, "profiles", "backbone_bwd_bench_bf16_attention.txt" if a.attention == "bf16" else
+                             "backbone_bwd_bench_bf16.txt" if a.precision == "bf16" else "backbone_bwd_bench.txt")
     if not torch.cuda.is_available():
         raise SystemExit("backbone_bwd_bench measures on the GPU; there is none here")
     main(a)
