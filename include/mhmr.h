@@ -282,7 +282,7 @@ int mhmr_attention16_pitch(const void* qk, const void* vt, void* out, int B, int
 /* mhmr_layernorm16 into rows of pitch ld16 elements, with the bf8 copy at byte offset o8 (0 = none). */
 int mhmr_layernorm16_pitch(const float* in, const float* w, const float* b, void* out16, int ld16, int o8, int rows, int C, float eps,
                            int dtype, void* stream);
-/* The attention of the f16x3 mode (csrc/attention_f32.hip): qkv fp32 [B*Tp, 3C] = (Q | K | V) un-scaled, head h at columns h*64;
+/* The attention of the f16x3 mode (csrc/attention_f32.hip, which also holds mhmr_attention_f32_tape / _backward below): qkv fp32 [B*Tp, 3C] = (Q | K | V) un-scaled, head h at columns h*64;
  * out op16 PAIR [B*Tp, 2C] = [hi | lo] of softmax(Q K^T / 8) V over the T real keys; every product on v_mfma_f32_16x16x4_f32 (exact fp32).
  * Rows >= T of an image are written as zeros or as the (finite) attention of a padding row: never left unwritten.   Tp % 64 == 0.
  * hi and lo are taken from ONE fp32 value of o: hi + lo = o to 2^-22 (f16) / 2^-16 (bf16) relative, ties of op16(o) included. */

@@ -1,12 +1,13 @@
 """Training the last backbone blocks: the backward of a ViT block and of the self-attention over all tokens of an
 image, in fp32 at the fp32 master weights, evaluated at the residual stream the inference forward produced.
 
-The functions here run the kernels of csrc/vit_bwd.hip on device tensors and allocate their outputs and workspaces.  There is no CPU
-path.  ``precision="bf16"`` gives the linears of a block bf16 operands with fp32 accumulation (csrc/linear_bf16.hip),
-in the recomputed tape and in both backward products; attention, LayerNorm and the column sums stay exact, and ``"f32"`` is the default.
-``attention="bf16"`` is the independent switch of the attention tape and backward: bf16 operands, fp32 accumulation,
-fp32 logits (csrc/attention_bf16.hip; ``attention_bf16_tape`` / ``attention_bf16_backward`` run the pair on its own).  Token rows follow the forward's layout: ``Tp`` rows per image, patch rows first, the class token at row ``N = T - 1``, padding
-behind it."""
+The functions here run the block and tail backward of csrc/vit_bwd.hip and the exact attention pair of csrc/attention_f32.hip on device
+tensors and allocate their outputs and workspaces.  There is no CPU path.  ``precision="bf16"`` gives the linears
+of a block bf16 operands with fp32 accumulation (csrc/linear_bf16.hip), in the recomputed tape and in both backward products; attention,
+LayerNorm and the column sums stay exact, and ``"f32"`` is the default.  ``attention="bf16"`` is the independent
+switch of the attention tape and backward: bf16 operands, fp32 accumulation, fp32 logits (csrc/attention_bf16.hip;
+``attention_bf16_tape`` / ``attention_bf16_backward`` run the pair on its own).  Token rows follow the forward's layout: ``Tp`` rows per
+image, patch rows first, the class token at row ``N = T - 1``, padding behind it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -49,64 +50,62 @@ def _f32(t):
     return t.detach().to(torch.float32).contiguous()
 
 
-def attention_tape(qkv, B, T, Tp, H, stream=None):
-    """``mhmr_attention_f32_tape``: qkv [B*Tp, 3C] fp32 -> (out32 [B*Tp, C], lse [B, H, Tp])."""
+def _call(entry, args, dev, stream=None, ws=None):
+    """``entry(*args, [workspace, workspace_bytes,] stream)`` on ``stream`` (default: the current stream of ``dev``), checked under the
+    entry's name.  ``ws`` = (the entry's workspace-size entry, *its arguments): a uint8 workspace of that size is allocated on ``dev``."""
+    if ws is not None:
+        nbytes = _lib.workspace_bytes(*ws)
+        wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # alive until the call is enqueued
+        args += (wsb.data_ptr(), nbytes)
+    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+    _lib.check(getattr(_lib.lib(), entry)(*args, stream), entry)
+
+
+def _attention_ws(kind, B, Tp, Cd, H):
+    """``_call``'s ``ws`` of the attention backward of ``kind`` ("f32" or "bf16"; the bf16 tape takes the same workspace)."""
+    return ("mhmr_attention_bf16_workspace_bytes", B, Tp, Cd, H) if kind == "bf16" else ("mhmr_attention_f32_backward_workspace_bytes", B, Tp, H)
+
+
+def _attention_tape(kind, qkv, B, T, Tp, H, stream):
     qkv = _f32(qkv)
     dev, Cd = qkv.device, qkv.shape[1] // 3
     out32 = torch.empty(B * Tp, Cd, dtype=torch.float32, device=dev)
     lse = torch.empty(B, H, Tp, dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(_lib.lib().mhmr_attention_f32_tape(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), B, T, Tp, Cd, H, stream),
-               "mhmr_attention_f32_tape")
+    _call(f"mhmr_attention_{kind}_tape", (qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), B, T, Tp, Cd, H), dev, stream,
+          _attention_ws(kind, B, Tp, Cd, H) if kind == "bf16" else None)
     return out32, lse
+
+
+def _attention_backward(kind, qkv, out32, lse, dO, B, T, Tp, H, stream, dqkv):
+    qkv, out32, lse = _f32(qkv), _f32(out32), _f32(lse)
+    dev, Cd = qkv.device, qkv.shape[1] // 3
+    if dO.dtype != torch.float32 or dO.stride(-1) != 1:
+        dO = _f32(dO)
+    if dqkv is None:
+        dqkv = torch.empty(B * Tp, 3 * Cd, dtype=torch.float32, device=dev)
+    _call(f"mhmr_attention_{kind}_backward", (qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), dO.data_ptr(), dO.stride(0), dqkv.data_ptr(), B,
+                                              T, Tp, Cd, H), dev, stream, _attention_ws(kind, B, Tp, Cd, H))
+    return dqkv
+
+
+def attention_tape(qkv, B, T, Tp, H, stream=None):
+    """``mhmr_attention_f32_tape``: qkv [B*Tp, 3C] fp32 -> (out32 [B*Tp, C], lse [B, H, Tp])."""
+    return _attention_tape("f32", qkv, B, T, Tp, H, stream)
 
 
 def attention_backward(qkv, out32, lse, dO, B, T, Tp, H, stream=None, dqkv=None):
     """``mhmr_attention_f32_backward``: -> dqkv [B*Tp, 3C] with respect to the un-scaled Q, K and V."""
-    L = _lib.lib()
-    qkv, out32, lse = _f32(qkv), _f32(out32), _f32(lse)
-    dev, Cd = qkv.device, qkv.shape[1] // 3
-    if dO.dtype != torch.float32 or dO.stride(-1) != 1:
-        dO = _f32(dO)
-    if dqkv is None:
-        dqkv = torch.empty(B * Tp, 3 * Cd, dtype=torch.float32, device=dev)
-    nbytes = _lib.workspace_bytes("mhmr_attention_f32_backward_workspace_bytes", B, Tp, H)
-    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(L.mhmr_attention_f32_backward(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), dO.data_ptr(), dO.stride(0), dqkv.data_ptr(), B,
-                                             T, Tp, Cd, H, wsb.data_ptr(), nbytes, stream), "mhmr_attention_f32_backward")
-    return dqkv
+    return _attention_backward("f32", qkv, out32, lse, dO, B, T, Tp, H, stream, dqkv)
 
 
 def attention_bf16_tape(qkv, B, T, Tp, H, stream=None):
     """``mhmr_attention_bf16_tape``: qkv [B*Tp, 3C] fp32 -> (out32 [B*Tp, C], lse [B, H, Tp]) with bf16 operands."""
-    qkv = _f32(qkv)
-    dev, Cd = qkv.device, qkv.shape[1] // 3
-    out32 = torch.empty(B * Tp, Cd, dtype=torch.float32, device=dev)
-    lse = torch.empty(B, H, Tp, dtype=torch.float32, device=dev)
-    nbytes = _lib.workspace_bytes("mhmr_attention_bf16_workspace_bytes", B, Tp, Cd, H)
-    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(_lib.lib().mhmr_attention_bf16_tape(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), B, T, Tp, Cd, H, wsb.data_ptr(), nbytes, stream),
-               "mhmr_attention_bf16_tape")
-    return out32, lse
+    return _attention_tape("bf16", qkv, B, T, Tp, H, stream)
 
 
 def attention_bf16_backward(qkv, out32, lse, dO, B, T, Tp, H, stream=None, dqkv=None):
     """``mhmr_attention_bf16_backward``: -> dqkv [B*Tp, 3C] with respect to the un-scaled Q, K and V; ``out32`` and ``lse`` are the tape's."""
-    L = _lib.lib()
-    qkv, out32, lse = _f32(qkv), _f32(out32), _f32(lse)
-    dev, Cd = qkv.device, qkv.shape[1] // 3
-    if dO.dtype != torch.float32 or dO.stride(-1) != 1:
-        dO = _f32(dO)
-    if dqkv is None:
-        dqkv = torch.empty(B * Tp, 3 * Cd, dtype=torch.float32, device=dev)
-    nbytes = _lib.workspace_bytes("mhmr_attention_bf16_workspace_bytes", B, Tp, Cd, H)
-    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(L.mhmr_attention_bf16_backward(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), dO.data_ptr(), dO.stride(0), dqkv.data_ptr(), B,
-                                              T, Tp, Cd, H, wsb.data_ptr(), nbytes, stream), "mhmr_attention_bf16_backward")
-    return dqkv
+    return _attention_backward("bf16", qkv, out32, lse, dO, B, T, Tp, H, stream, dqkv)
 
 
 def block_tensors(block, device=None) -> dict:
@@ -135,11 +134,8 @@ def linear_bf16(X, W, bias=None, stream=None):
     bias = None if bias is None else _f32(bias)
     (M, K), N = X.shape, W.shape[0]
     Y = torch.empty(M, N, dtype=torch.float32, device=X.device)
-    nbytes = _lib.workspace_bytes("mhmr_linear_bf16_workspace_bytes", M, N, K)
-    wsb = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
-    stream = torch.cuda.current_stream(X.device).cuda_stream if stream is None else stream
-    _lib.check(_lib.lib().mhmr_linear_bf16(X.data_ptr(), K, W.data_ptr(), K, _lib.ptr(bias), Y.data_ptr(), N, M, N, K, wsb.data_ptr(), nbytes, stream),
-               "mhmr_linear_bf16")
+    _call("mhmr_linear_bf16", (X.data_ptr(), K, W.data_ptr(), K, _lib.ptr(bias), Y.data_ptr(), N, M, N, K), X.device, stream,
+          ("mhmr_linear_bf16_workspace_bytes", M, N, K))
     return Y
 
 
@@ -149,11 +145,8 @@ def linear_bf16_backward_input(dY, W, dR=None, stream=None):
     dR = None if dR is None else _f32(dR)
     (M, N), K = dY.shape, W.shape[1]
     dX = torch.empty(M, K, dtype=torch.float32, device=dY.device)
-    nbytes = _lib.workspace_bytes("mhmr_linear_bf16_workspace_bytes", M, N, K)
-    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dY.device)
-    stream = torch.cuda.current_stream(dY.device).cuda_stream if stream is None else stream
-    _lib.check(_lib.lib().mhmr_linear_bf16_backward_input(dY.data_ptr(), N, W.data_ptr(), K, _lib.ptr(dR), K, dX.data_ptr(), K, M, N, K, wsb.data_ptr(),
-                                                          nbytes, stream), "mhmr_linear_bf16_backward_input")
+    _call("mhmr_linear_bf16_backward_input", (dY.data_ptr(), N, W.data_ptr(), K, _lib.ptr(dR), K, dX.data_ptr(), K, M, N, K), dY.device, stream,
+          ("mhmr_linear_bf16_workspace_bytes", M, N, K))
     return dX
 
 
@@ -163,11 +156,8 @@ def linear_bf16_backward_weight(dY, X, stream=None):
     (M, N), K = dY.shape, X.shape[1]
     dW = torch.empty(N, K, dtype=torch.float32, device=dY.device)
     db = torch.empty(N, dtype=torch.float32, device=dY.device)
-    nbytes = _lib.workspace_bytes("mhmr_linear_bf16_workspace_bytes", M, N, K)
-    wsb = torch.empty(nbytes, dtype=torch.uint8, device=dY.device)
-    stream = torch.cuda.current_stream(dY.device).cuda_stream if stream is None else stream
-    _lib.check(_lib.lib().mhmr_linear_bf16_backward_weight(dY.data_ptr(), N, X.data_ptr(), K, dW.data_ptr(), K, db.data_ptr(), M, N, K, wsb.data_ptr(),
-                                                           nbytes, stream), "mhmr_linear_bf16_backward_weight")
+    _call("mhmr_linear_bf16_backward_weight", (dY.data_ptr(), N, X.data_ptr(), K, dW.data_ptr(), K, db.data_ptr(), M, N, K), dY.device, stream,
+          ("mhmr_linear_bf16_workspace_bytes", M, N, K))
     return dW, db
 
 
@@ -176,7 +166,6 @@ def block_backward(params: dict, x_in, g_out, B, T, Tp, H, stream=None, precisio
     [B*Tp, C] -> (g_in [B*Tp, C], {field: gradient of the parameter's shape}).  ``precision``: "f32" (the exact linears) or "bf16"
     (bf16 operands, fp32 accumulation).  ``attention``: the same two names for the attention tape and backward
     (DESIGN.md section 31)."""
-    L = _lib.lib()
     prec, att = _lib.bwd_precision(precision), _lib.attn_precision(attention)
     x_in, g_out = _f32(x_in), _f32(g_out)
     dev, Cd = x_in.device, x_in.shape[1]
@@ -187,8 +176,7 @@ def block_backward(params: dict, x_in, g_out, B, T, Tp, H, stream=None, precisio
     d = fill_block_desc(_lib.VitBlockBackwardDesc(), params, grads, B, T, Tp, Cd, H)
     d.linear_precision = prec
     d.x_in, d.g_out, d.g_in, d.workspace, d.workspace_bytes = x_in.data_ptr(), g_out.data_ptr(), g_in.data_ptr(), wsb.data_ptr(), nbytes
-    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(L.mhmr_vit_block_backward_a(C.byref(d), att, stream), "mhmr_vit_block_backward_a")
+    _call("mhmr_vit_block_backward_a", (C.byref(d), att), dev, stream)
     return g_in, grads
 
 
@@ -196,7 +184,6 @@ def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H,
     """``mhmr_vit_tail_backward`` on device tensors: final norm + the blocks of ``blocks`` ([{descriptor field: fp32 tensor}], first block
     first) at the tapped streams ``tap [n, B*Tp, C]``; ``resid [B*Tp, C]`` the stream the final norm read; ``g_feat [B*N, C]``
     -> (g_stream [B*Tp, C], g_norm_w, g_norm_b, [{field: gradient}] per block).  ``precision``, ``attention``: as in ``block_backward``, for every block."""
-    L = _lib.lib()
     prec, att = _lib.bwd_precision(precision), _lib.attn_precision(attention)
     n, dev, Cd = len(blocks), resid.device, resid.shape[-1]
     g_feat = _f32(g_feat).reshape(B * N, Cd)
@@ -215,8 +202,7 @@ def tail_backward(norm_w, norm_b, blocks: list, tap, resid, g_feat, B, N, Tp, H,
     d.norm_w, d.norm_b, d.blocks = norm_w.data_ptr(), norm_b.data_ptr(), C.cast(descs, C.POINTER(_lib.VitBlockBackwardDesc))
     d.tap, d.resid, d.g_feat = tap.data_ptr(), resid.data_ptr(), g_feat.data_ptr()
     d.g_norm_w, d.g_norm_b, d.g_stream, d.workspace, d.workspace_bytes = g_norm_w.data_ptr(), g_norm_b.data_ptr(), g_stream.data_ptr(), wsb.data_ptr(), nbytes
-    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(L.mhmr_vit_tail_backward_a(C.byref(d), att, stream), "mhmr_vit_tail_backward_a")
+    _call("mhmr_vit_tail_backward_a", (C.byref(d), att), dev, stream)
     return g_stream, g_norm_w, g_norm_b, grads
 
 
@@ -226,7 +212,6 @@ def embed_backward(x, g_stream, B, G, M, Tp, stream=None):
     -> {g_patch_w [C, 588], g_patch_b [C], g_pos [1 + M*M, C], g_cls [C]}."""
     import numpy as np
     from . import packing
-    L = _lib.lib()
     x, g_stream = _f32(x), _f32(g_stream)
     dev, Cd = g_stream.device, g_stream.shape[1]
     assert tuple(x.shape) == (B, 3, 14 * G, 14 * G) and g_stream.shape[0] == B * Tp
@@ -240,8 +225,7 @@ def embed_backward(x, g_stream, B, G, M, Tp, stream=None):
     d.x, d.g_stream, d.interp, d.workspace, d.workspace_bytes = x.data_ptr(), g_stream.data_ptr(), interp.data_ptr(), wsb.data_ptr(), nbytes
     for f, t in out.items():
         setattr(d, f, t.data_ptr())
-    stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-    _lib.check(L.mhmr_vit_embed_backward(C.byref(d), stream), "mhmr_vit_embed_backward")
+    _call("mhmr_vit_embed_backward", (C.byref(d),), dev, stream)
     return out
 
 
@@ -326,5 +310,6 @@ def attach(model, P, ws, B, x=None):
         return _TailFunction.apply(model, st, *[p for _, p in named])
 
 
-__all__ = ["BLOCK_FIELDS", "EMBED_FIELDS", "backbone_parameter_names", "embedding_parameter_names", "attention_tape", "attention_backward", "attention_bf16_tape", "attention_bf16_backward",
-           "block_tensors", "linear_bf16", "linear_bf16_backward_input", "linear_bf16_backward_weight", "block_backward", "tail_backward", "embed_backward", "model_tail_backward", "embeddings_on", "attach"]
+__all__ = ["BLOCK_FIELDS", "EMBED_FIELDS", "backbone_parameter_names", "embedding_parameter_names", "attention_tape", "attention_backward",
+           "attention_bf16_tape", "attention_bf16_backward", "block_tensors", "linear_bf16", "linear_bf16_backward_input",
+           "linear_bf16_backward_weight", "block_backward", "tail_backward", "embed_backward", "model_tail_backward", "embeddings_on", "attach"]

@@ -1,5 +1,5 @@
 // Attention tape and backward with bf16 operands and fp32 accumulation: the mixed-precision form of
-// vit_bwd.hip's attention pair.  Every tensor at the interface is fp32 in the layouts of mhmr_attention_f32_tape / _backward;
+// attention_f32.hip's tape and backward.  Every tensor at the interface is fp32 in the layouts of mhmr_attention_f32_tape / _backward;
 // r() is round-to-nearest-even fp32 -> bf16.  Per (image, head), over the T real rows:
 //     S_ij  = MHMR_ATTN_QSCALE * sum_d r(Q_i[d]) r(K_j[d])        lse_i = log2 sum_j exp2(S_ij)        P_ij = exp2(S_ij - lse_i)
 //     O_i   = sum_j r(P_ij) r(V_j)                                D_i   = sum_d dO_i[d] O_i[d]  (unrounded, fp32, fixed order)
@@ -369,9 +369,6 @@ __global__ __launch_bounds__(256, 2) void attn16_bwd_kv_kernel(const __bf16* __r
     }
 }
 
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
-
 // the workspace: qkv as it lies, dO as it lies, three transposed copies (tr0 = V^T in the tape, K^T in the backward), D
 struct Attn16Layout { long long qkvb, dob, tr0, qt, gt, D, total; };
 Attn16Layout attn16_layout(long long B, long long Tp, long long C) {
@@ -385,8 +382,7 @@ Attn16Layout attn16_layout(long long B, long long Tp, long long C) {
 }
 
 int attn16_shape_rc(int B, int T, int Tp, int C, int H) {
-    if (B < 0 || T < 0 || Tp < 0 || C < 0 || H < 0) return MHMR_ERR_BAD_ARG;
-    if (B == 0 || T == 0 || Tp % 64 || Tp < T || C != 64 * H || H > 65535 || B > 65535) return MHMR_ERR_BAD_SHAPE;
+    TRY(mhmr_attention_shape_rc(B, T, Tp, C, H));
     if ((long long)B * Tp / 64 > 65535) return MHMR_ERR_BAD_SHAPE;           // row tiles of the transposing convert kernel
     return 0;
 }

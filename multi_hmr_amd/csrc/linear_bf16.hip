@@ -187,8 +187,6 @@ struct BiasTerm {
     }
 };
 
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 inline int weight_slices(long long M) { return (int)((M + WSLICE - 1) / WSLICE); }
 
 // the workspace of one linear: the two bf16 operands, the weight side's partial products and the scratch of the bias sums

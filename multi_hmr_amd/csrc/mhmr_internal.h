@@ -146,6 +146,14 @@ enum ProfKind { PROF_GEMM = 0, PROF_ATTN = 1, PROF_LBS = 2, PROF_KINDS = 3 };
         if (rc__ != 0) return rc__; \
     } while (0)
 
+// The shape rule of the training attention (tape and backward, fp32 and bf16) and of the block backward around it: heads of 64, Tp rows
+// per image in workgroups of 64, (Tp / 64, H, B) as the launch grid.  Each entry point adds its own.
+inline int mhmr_attention_shape_rc(int B, int T, int Tp, int C, int H) {
+    if (B < 0 || T < 0 || Tp < 0 || C < 0 || H < 0) return MHMR_ERR_BAD_ARG;
+    if (B == 0 || T == 0 || Tp % 64 || Tp < T || C != 64 * H || H > 65535 || B > 65535) return MHMR_ERR_BAD_SHAPE;
+    return 0;
+}
+
 // ================================================================================================================================
 // Every function one translation unit defines and another calls, by defining file.  Default arguments live here, once.
 // ================================================================================================================================
@@ -171,6 +179,12 @@ int mhmr_attention_flag_count_impl(int B, int Tp, int H);
 
 // ---- attention_f32.hip
 int mhmr_launch_attention_f32(const float* qkv, void* out, int B, int T, int Tp, int C, int H, int dtype, hipStream_t s);
+// the exact-fp32 attention tape and backward; arguments validated by the caller as the extern "C" entries do; ws holds
+// mhmr_attention_f32_bwd_bytes(B, Tp, C)
+long long mhmr_attention_f32_bwd_bytes(int B, int Tp, int C);
+int mhmr_launch_attention_f32_tape(const float* qkv, float* out32, float* lse, int B, int T, int Tp, int C, int H, hipStream_t s);
+int mhmr_launch_attention_f32_bwd(const float* qkv, const float* out32, const float* lse, const float* dO, int lddo, float* dqkv, int B, int T,
+                                  int Tp, int C, int H, void* ws, hipStream_t s);
 
 // ---- vit_misc.hip
 int mhmr_launch_im2col(const float* x, void* a, int B, int S, int G, int Kp, int dtype, hipStream_t s);

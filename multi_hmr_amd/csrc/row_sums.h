@@ -10,6 +10,10 @@
 
 namespace {
 
+// ---------------------------------------------------------------- host helpers of the launchers
+inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }      // workgroups of 256 threads over n elements
+inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
 // ---------------------------------------------------------------- workspace cursor: every piece 256-byte aligned
 inline long long align256(long long v) { return (v + 255) / 256 * 256; }
 struct WsCursor {

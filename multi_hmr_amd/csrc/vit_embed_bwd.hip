@@ -27,9 +27,6 @@ constexpr int PB_SLICE = 32;                               // rows per first-sta
 constexpr int EMBED_MAX_GRID = 1024, EMBED_MAX_TABLE = 4096;      // G and M: every element count below stays far inside 64 bits
 constexpr long long EMBED_MAX_ROWS = 16LL * 65535;         // B * Tp, the block backward's own limit (vit_bwd.hip block_shape_rc)
 
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
-
 // dW[n][k] = sum over the patch rows m = (b, gy, gx) of g_stream[b Tp + gy G + gx][n] * x[b][ch][14 gy + py][14 gx + px].
 // Lane group g takes row m + g of every four: its (b, gy, gx) advances by four rows per step, digit by digit, so the loop holds no
 // division.  A row past the last one (b == B) contributes an exact zero; its addresses are those of the last row.

@@ -1,5 +1,6 @@
-"""-m "not gpu": the host side of the backbone backward -- the entries of csrc/vit_bwd.hip are declared, exported
-and bound, their descriptors match the header, every entry validates its arguments before any launch (so these calls run without a GPU),
+"""-m "not gpu": the host side of the backbone backward -- the entries of csrc/vit_bwd.hip and the attention pair
+of csrc/attention_f32.hip are declared, exported and bound, their descriptors match the header, every entry validates its arguments
+before any launch (so these calls run without a GPU),
 the closed-form attention oracle equals fp64 autograd, and the Python surface names the right parameters."""
 import ctypes as C
 import os

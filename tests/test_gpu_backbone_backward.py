@@ -1,4 +1,4 @@
-"""-m gpu: the backward of the last backbone blocks (csrc/vit_bwd.hip, multi_hmr_amd/backbone_train.py) -- the
+"""-m gpu: the backward of the last backbone blocks (csrc/vit_bwd.hip, csrc/attention_f32.hip, multi_hmr_amd/backbone_train.py) -- the
 attention backward against the fp64 closed form, the block backward against fp64 autograd of oracle/dinov2_ref's own Block.
 
 Measure and gate (tests/backbone_bwd_oracle.py): per tensor the relative L2 error against fp64 and the maximum error relative to the
@@ -126,6 +126,34 @@ def test_attention_backward_against_the_fp64_closed_form(L, T, Tp):
         _, _, other = _attention_run(L, c["qkv"], c["dO"], B, T, Tp, H, refill=77 + T)
         assert torch.equal(other, dqkv), "the padding rows reached a real row"
     bo.gate(f"attention T {T} Tp {Tp}", rows)
+
+
+@pytest.mark.parametrize("name,dt,tdt", [("f16", _lib.DT_F16, torch.float16), ("bf16", _lib.DT_BF16, torch.bfloat16)])
+@pytest.mark.parametrize("T", [1, 15, 16, 17, 64, 65, 130])
+def test_the_tape_is_the_forward_with_an_fp32_output(L, T, name, dt, tdt):
+    """csrc/attention_f32.hip: mhmr_attention_f32 and mhmr_attention_f32_tape run one key-tile step, so on every real row the forward's
+    [hi | lo] pair is, bit for bit, the split of the tape's fp32 out32 (conversions round to nearest even, as torch's do).  Rows >= T are
+    not compared: the forward leaves finite values in the rest of T's 16-row group, the tape writes zeros."""
+    B, H, Cd, Tp = 2, 2, 128, bo.roundup(T, 64)
+    g = torch.Generator().manual_seed(6100 + T)
+    qkv = rn(g, B * Tp, 3 * Cd)                                # the padding rows hold finite values of their own
+    qkv[:, :Cd] *= 2.0
+    qkv = qkv.to(dev())
+    pair = torch.full((B * Tp, 2 * Cd), float("nan"), dtype=tdt, device=dev())
+    ob, out32 = guarded(B * Tp, Cd)
+    lb, lse = guarded(B, H, Tp)
+    _lib.check(L.mhmr_attention_f32(qkv.data_ptr(), pair.data_ptr(), B, T, Tp, Cd, H, dt, stream()), "attention_f32")
+    _lib.check(L.mhmr_attention_f32_tape(qkv.data_ptr(), out32.data_ptr(), lse.data_ptr(), B, T, Tp, Cd, H, stream()), "tape")
+    torch.cuda.synchronize()
+    assert intact(ob, lb), "a write behind an output"
+    real = torch.arange(B * Tp) % Tp < T
+    o, p = out32.cpu()[real], pair.cpu()[real]
+    hi, lo = p[:, :Cd], p[:, Cd:]
+    want_hi = o.to(tdt)
+    want_lo = (o - want_hi.float()).to(tdt)
+    nh, nl = int((hi.view(torch.int16) != want_hi.view(torch.int16)).sum()), int((lo.view(torch.int16) != want_lo.view(torch.int16)).sum())
+    print(f"[tape == forward, T {T} {name}] {o.numel()} elements: hi differs in {nh}, lo differs in {nl}")
+    assert bool(torch.isfinite(o).all()) and nh == 0 and nl == 0
 
 
 # ------------------------------------------------------------------------------------------------------ (2) block backward
