@@ -1126,6 +1126,69 @@ int mhmr_adam_step(const mhmr_adam_segment* segs_host, const mhmr_adam_segment* 
                    double max_norm, double* partials, long long partials_count, float* norm_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Fit persons to 2D keypoints (csrc/fit.hip): Adam on the read-out row r = [pose6d 318 | betas nb |
+ * cam 3 | expr 10] and the offset o [2] of every person, from the anchors r0, o0 (the network's prediction), against
+ * targets kp [NJ][2] in pixels with weights c [NJ] >= 0 (c = 0: the joint is not given), NJ = J + E + L of the body model.
+ * The objective is separable per person -- no sum crosses persons:
+ *   (loc, rotvec, shape, expression, dist) = mhmr_heads_decode(r, o, det, K)                          unchanged, fp32
+ *   u_j    = joints of mhmr_body_forward(pose55(rotvec), [shape | expression], transl = NULL, K = NULL)
+ *   transl = dist K_b^-1 [loc; 1],  x_j = (u_j - u_center) + transl,  j2d_j = project(x_j, K_b),  b = det_b[p]
+ *   s_j    = |j2d_j - kp_j|^2 / sigma^2,   rho(s) = s (MHMR_FIT_L2)  or  s / (1 + s) (MHMR_FIT_GMOF)
+ *   E_p    = sum_j c_j rho(s_j) + lambda_pose |r_pose6d - r0_pose6d|^2 + lambda_shape |r_betas - r0_betas|^2
+ *            + lambda_depth (r_cam0 - r0_cam0)^2 + lambda_expr |r_expr - r0_expr|^2 + lambda_loc |o - o0|^2
+ * Elements are fp32; the sum over the joints and each prior sum are fp64 in index order, each rounded once; E_p = the data term
+ * plus lambda * sum of the five priors in that order, in fp64, rounded once.  A joint with c_j = 0 (or a NaN weight) is a SELECT:
+ * exact zeros in the value and the gradient, whatever its target holds (NaN, Inf).  The cotangent
+ * g_j2d_j = 2 c_j rho'(s_j) (j2d_j - kp_j) / sigma^2 (rho' = 1, or 1 / (1 + s)^2) goes through mhmr_heads_place_backward,
+ * mhmr_body_backward (g_vertices = NULL) and mhmr_heads_decode_backward; the prior terms 2 lambda (r - r0) are added in fp32 and
+ * the result is multiplied by the 0/1 column mask [318 + nb + 13 + 2] (read-out columns, then the two offset columns).
+ * cam[1:3] keep their exact-zero gradient (no prior reads them); a masked column's parameter and moments are never written.
+ * Per step: the Adam element of mhmr_adam_step (the same function, csrc/adam_element.h; no clipping) in place on readout, offset,
+ * exp_avg and exp_avg_sq [P][318 + nb + 13 + 2], with lr / (1 - beta1^t) and sqrt(1 - beta2^t) of t = step0 + 1, step0 + 2, ...
+ * taken in double on the host and rounded once: a second call with step0 = the steps done and the same moments continues the
+ * first, bit for bit.
+ * The entry enqueues, `steps` times: decode -> stage -> body forward -> objective -> placement backward -> body backward ->
+ * stage back -> decode backward -> update, then one more evaluation without the update for objective[steps] and grad (skipped
+ * when both are NULL).  steps = 0 is "value and gradient only".  objective [steps + 1][P] (nullable): E_p at every iterate,
+ * the last included.  grad [P][318 + nb + 13 + 2] (nullable): the masked gradient at the last iterate.
+ * The body model may be any (c, bc) pair whose chain is SMPL-X's (J = 55, nc = nb + 10): the full model, or the gathered model
+ * of BodyModel.keypoint_model(), which holds the <= E + 3 L vertices the output joints read.  readout0 has readout's pitch ldr.
+ * No atomics, no allocation, no synchronisation; every output element is written; two calls give the same bits; person p of a
+ * batch gets the bits it gets alone.  Validated before the first launch: a NULL descriptor, model or required pointer, P < 0,
+ * steps < 0, step0 < 0, sigma, fn or (steps > 0) lr not finite and positive, a negative or non-finite lambda, robust outside the
+ * two kinds, betas outside [0, 1), eps < 0, center_joint >= NJ, patch <= 0, bc->n != E + 3 L, a short workspace ->
+ * MHMR_ERR_BAD_ARG; J != 55, nb != nc - 10, nb outside [0, 64], ldr < 318 + nb + 13, P > 65535, NJ > 8192, the shape limits of
+ * mhmr_body_forward -> MHMR_ERR_BAD_SHAPE; P == 0 launches nothing and returns 0.
+ * mhmr_fit_keypoints_workspace_bytes: bytes for (c, P), monotone in P; negative = the error code.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define MHMR_FIT_L2 0
+#define MHMR_FIT_GMOF 1
+typedef struct {
+    const mhmr_body_consts* c;
+    const mhmr_body_bwd_consts* bc;
+    int P, nb, ldr, patch, nearness, center_joint;   /* center_joint < 0: no recentring (x = u + transl)                  */
+    double fn;                                       /* normalising focal length (the decode reads its float rounding)    */
+    float *readout, *offset;                         /* in/out [P][ldr], [P][2]                                           */
+    const float *readout0, *offset0;                 /* anchors [P][ldr], [P][2]                                          */
+    const int *det_b, *det_y, *det_x;                /* [P]                                                               */
+    const float* K;                                  /* [B][3][3]                                                         */
+    const float *keypoints, *confidence;             /* [P][NJ][2], [P][NJ]                                               */
+    float sigma;
+    int robust;                                      /* MHMR_FIT_*                                                        */
+    float lambda_pose, lambda_shape, lambda_depth, lambda_expr, lambda_loc;
+    const float* mask;                               /* [318 + nb + 13 + 2] of 0 / 1                                      */
+    int steps, step0;
+    double lr, beta1, beta2, eps;
+    float *exp_avg, *exp_avg_sq;                     /* in/out [P][318 + nb + 13 + 2] (may be NULL when steps == 0)       */
+    float* objective;                                /* [steps + 1][P] or NULL                                            */
+    float* grad;                                     /* [P][318 + nb + 13 + 2] or NULL                                    */
+    void* workspace;
+    long long workspace_bytes;
+} mhmr_fit_desc;
+long long mhmr_fit_keypoints_workspace_bytes(const mhmr_body_consts* c, int P);
+int mhmr_fit_keypoints(const mhmr_fit_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Backward of one ViT block: the derivative of the fp32 function
  *     x -> x + ls1 * proj(MHSA(norm1(x))),  then  x -> x + ls2 * fc2(gelu(fc1(norm2(x))))
  * (attention scale head_dim^-0.5, erf GELU, LayerNorm eps 1e-6) with the fp32 master weights in torch layout,

@@ -12,8 +12,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
-HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", os.path.join("..", "..", "include", "mhmr.h")]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "fit.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
 DT_BF16, DT_F16 = 0, 1
@@ -47,8 +47,9 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: loss.hip: every element of the training loss is the reference's fp32 subtraction(s), rounded one by one (its sign is the gradient).
 #: optim.hip: the Adam update is torch's sequence of fp32 operations, each rounded on its own.
 #: attention_bf16.hip: the logit S = fl(QSCALE * acc) is rounded before exp2(S - lse) in all three kernels, as the contract states it.
+#: fit.hip: its update kernel runs optim.hip's Adam element (csrc/adam_element.h) and must round it the same way.
 EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
-               "optim.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"]}
+               "optim.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -223,6 +224,21 @@ class HeadsDecodeBackwardDesc(C.Structure):
                                     "g_dist_postprocessed", "g_transl", "g_loc", "g_offset_direct", "g_readout", "g_offset")])
 
 
+FIT_L2, FIT_GMOF = 0, 1              # include/mhmr.h MHMR_FIT_*
+FIT_ROBUST = {"l2": FIT_L2, "gmof": FIT_GMOF}
+
+
+class FitDesc(C.Structure):
+    """include/mhmr.h mhmr_fit_desc."""
+    _fields_ = ([("c", C.POINTER(BodyConsts)), ("bc", C.POINTER(BodyBwdConsts))] +
+                [(n, _i) for n in ("P", "nb", "ldr", "patch", "nearness", "center_joint")] + [("fn", C.c_double)] +
+                [(n, _vp) for n in ("readout", "offset", "readout0", "offset0", "det_b", "det_y", "det_x", "K", "keypoints", "confidence")] +
+                [("sigma", _f), ("robust", _i)] +
+                [(n, _f) for n in ("lambda_pose", "lambda_shape", "lambda_depth", "lambda_expr", "lambda_loc")] + [("mask", _vp)] +
+                [("steps", _i), ("step0", _i)] + [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps")] +
+                [(n, _vp) for n in ("exp_avg", "exp_avg_sq", "objective", "grad", "workspace")] + [("workspace_bytes", C.c_longlong)])
+
+
 class PreImage(C.Structure):
     """include/mhmr.h mhmr_pre_image: one image of mhmr_preprocess_u8_batch (device pointers + the geometry of its plan)."""
     _fields_ = ([("img", _vp)] + [(n, _i) for n in ("H", "W", "ow", "oh", "y0", "rows", "pad_x", "pad_y", "ksh", "ksv")] +
@@ -395,6 +411,8 @@ _SIGS = {
     "mhmr_loss_forward": ([C.POINTER(LossDesc), _vp, C.c_longlong, _vp, _vp], _i),
     "mhmr_loss_backward": ([C.POINTER(LossDesc), _vp, _fp, C.POINTER(LossGrads), _vp], _i),
     "mhmr_adam_step": ([C.POINTER(AdamSegment), _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_longlong, _vp, _vp], _i),
+    "mhmr_fit_keypoints_workspace_bytes": ([C.POINTER(BodyConsts), _i], C.c_longlong),
+    "mhmr_fit_keypoints": ([C.POINTER(FitDesc), _vp], _i),
     "mhmr_attention_f32_tape": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mhmr_attention_f32_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
     "mhmr_attention_f32_backward": ([_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),

@@ -106,6 +106,42 @@ class BodyModel:
             self.lmk_vidx, self.lmk_bary = np.zeros((0, 3), dtype=np.int64), np.zeros((0, 3), dtype=np.float32)
         self.num_out_joints = J + len(self.extra_joint_verts) + len(self.lmk_vidx)
         self._packed: dict = {}
+        self._source = None           # keypoint_model(): the model this one was gathered from
+        self._keypoint = None         # keypoint_model()'s cached result
+        self.vertex_ids = None        # keypoint_model(): ids of the kept vertices in the source model, sorted
+
+    def keypoint_model(self) -> "BodyModel":
+        """The model of the OUTPUT JOINTS alone (cached): its vertices are the sorted unique ids of the picked vertices and the landmark
+        corners -- all that ``joints`` reads besides the chain -- so ``mhmr_body_forward`` / ``mhmr_body_backward`` run on it as they are
+        over at most ``E + 3 L`` vertex columns (SMPL-X: <= 174, padded to 192, instead of 10 496).  ``v_template``, ``shapedirs``,
+        ``posedirs`` and the skinning weights are gathered; the picked ids and landmark corners are renumbered; the joint regression
+        (``J0``, ``JS``), ``parents`` and the barycentric weights are the source's own.  ``joints`` of the result equal the source's bit
+        for bit (a vertex is computed from its own columns only); ``vertices`` are the kept ones, in ``vertex_ids`` order; ``faces`` is
+        empty.  A model without picked vertices and landmarks has no keypoint model."""
+        if self._keypoint is None:
+            ids = np.unique(np.concatenate([self.extra_joint_verts, self.lmk_vidx.reshape(-1)]).astype(np.int64))
+            if ids.size == 0:
+                raise ValueError("keypoint_model: the model has neither picked-vertex joints nor landmarks")
+            km = object.__new__(BodyModel)
+            km.__dict__.update(self.__dict__)
+            km._packed, km._source, km._keypoint, km.vertex_ids = {}, self, None, ids
+            km.v_template, km.shapedirs = np.ascontiguousarray(self.v_template[ids]), np.ascontiguousarray(self.shapedirs[ids])
+            km.posedirs, km.lbs_weights = np.ascontiguousarray(self.posedirs[ids]), np.ascontiguousarray(self.lbs_weights[ids])
+            km.num_vertices = int(ids.size)
+            km.faces, km.J_regressor = np.zeros((0, 3), dtype=np.int64), None
+            km.extra_joint_verts = np.searchsorted(ids, self.extra_joint_verts).astype(np.int64)
+            km.lmk_vidx = np.searchsorted(ids, self.lmk_vidx).astype(np.int64)
+            self._keypoint = km
+        return self._keypoint
+
+    def _joint_rest(self):
+        """(J0 [J, 3], JS [3 J, nc]) in float64: the rest joints and their shape directions -- of the source, for a gathered model."""
+        if self._source is not None:
+            return self._source._joint_rest()
+        Jr = self.J_regressor.astype(np.float64)
+        nc = self.shapedirs.shape[-1]
+        return (Jr @ self.v_template.astype(np.float64),
+                np.einsum("jv,vkl->jkl", Jr, self.shapedirs.astype(np.float64)).reshape(self.num_joints * 3, nc))
 
     # ---- constants, once per device
     def _consts(self, device):
@@ -121,9 +157,7 @@ class BodyModel:
         basis[nc:, :, :V] = self.posedirs.transpose(2, 1, 0)
         vtemp = np.zeros((3, Vp), dtype=np.float32)
         vtemp[:, :V] = self.v_template.T
-        Jr = self.J_regressor.astype(np.float64)
-        J0 = Jr @ self.v_template.astype(np.float64)
-        JS = np.einsum("jv,vkl->jkl", Jr, self.shapedirs.astype(np.float64)).reshape(J * 3, nc)
+        J0, JS = self._joint_rest()
         W = np.zeros((J, Vp), dtype=np.float32)
         W[:, :V] = self.lbs_weights.T
         t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dt)

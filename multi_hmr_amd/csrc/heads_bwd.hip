@@ -45,7 +45,8 @@ __device__ __forceinline__ void store16(float* p, f32x4 v) { __builtin_memcpy(p,
 __device__ __forceinline__ void point_cotangent(const float* u, const float* jc, const float* t, const float* K, bool has2, float gu, float gv,
                                                 float* g) {
     if (!has2) return;
-    const float x[3] = {(u[0] - jc[0]) + t[0], (u[1] - jc[1]) + t[1], (u[2] - jc[2]) + t[2]};
+    float x[3];
+    place_point(u, jc, t, x);
     project_jacobian_t(K, x, gu, gv, g);
 }
 

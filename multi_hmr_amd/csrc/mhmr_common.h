@@ -127,8 +127,23 @@ __device__ __forceinline__ void inv3x3(const T* k, T* o) {
     o[6] = Cc * id; o[7] = -(a * h - b * g) * id; o[8] = (a * e - b * d) * id;
 }
 
+// The SMPL-X layer's placement of one point, blocks/smpl_layer.py:128-136: x = (u - centre) + transl, in this association (centre = 0
+// without a centre joint).  One definition for the placement backward of the prediction decode and the keypoint fit's forward.
+template <typename T>
+__device__ __forceinline__ void place_point(const T* u, const T* jc, const T* t, T* x) {
+    x[0] = (u[0] - jc[0]) + t[0];
+    x[1] = (u[1] - jc[1]) + t[1];
+    x[2] = (u[2] - jc[2]) + t[2];
+}
+// transl = dist * K^-1 [loc; 1] (utils/camera.py:30-48) from the inverse inv3x3 leaves: the row's three terms first, then the distance
+template <typename T>
+__device__ __forceinline__ void place_transl(const T* Ki, T lx, T ly, T dist, T* t) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t[a] = (Ki[a * 3] * lx + Ki[a * 3 + 1] * ly + Ki[a * 3 + 2]) * dist;
+}
+
 // Pinhole projection, utils/camera.py:14-27: y = x / x_z, then K y (all three terms, as the einsum), and its Jacobian.  One definition
-// for the body model's forward and backward and for the placement backward of the prediction decode.
+// for the body model's forward and backward, for the placement backward of the prediction decode and for the keypoint fit.
 __device__ __forceinline__ void project(const float* __restrict__ K, float x, float y, float z, float* __restrict__ out) {
     const float a = x / z, b = y / z, c = z / z;
     out[0] = K[0] * a + K[1] * b + K[2] * c;

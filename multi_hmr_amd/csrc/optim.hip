@@ -9,16 +9,12 @@
 // -- and the 16-byte and the element-by-element forms run the same function per element: the same bits.
 #include "mhmr_common.h"
 #include "mhmr_internal.h"
+#include "adam_element.h"      // AdamK, adam_element: the element function, shared with fit.hip
 
 namespace {
 
 constexpr int CHUNK = MHMR_ADAM_CHUNK, THREADS = 256;
 static_assert(CHUNK % (THREADS * 4) == 0, "a chunk is a whole number of 4-element groups per thread");
-
-struct AdamK {
-    float w1, b2, w2, eps;      // 1 - beta1, beta2, 1 - beta2 (differences taken in double, rounded once), eps
-    float max_norm;             // > 0: clipping
-};
 
 // the segment of chunk b: the last one whose first chunk is <= b (chunk0 strictly increases: every segment has at least one element)
 __device__ __forceinline__ int find_segment(const mhmr_adam_segment* __restrict__ segs, int nsegs, int b) {
@@ -28,14 +24,6 @@ __device__ __forceinline__ int find_segment(const mhmr_adam_segment* __restrict_
         if (segs[mid].chunk0 <= b) lo = mid; else hi = mid - 1;
     }
     return lo;
-}
-
-__device__ __forceinline__ void adam_element(float& p, float& m, float& v, float g, const AdamK& k, float step_size, float bc2_sqrt) {
-    m = __builtin_fmaf(k.w1, g - m, m);              // exp_avg.lerp_(grad, 1 - beta1)        (weight < 0.5: fma(w, end - start, start), as ATen's lerp)
-    v = v * k.b2;                                    // exp_avg_sq.mul_(beta2)
-    v = __builtin_fmaf(k.w2 * g, g, v);              //           .addcmul_(grad, grad, value=1 - beta2)
-    const float denom = sqrtf(v) / bc2_sqrt + k.eps; // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-    p = p + (-step_size * m) / denom;                // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
 template <int W> __device__ __forceinline__ void load_w(const float* __restrict__ ptr, long long i, float* out);

@@ -681,8 +681,10 @@ class Model(nn.Module):
         (empty list if nobody is detected); ``is_training=True`` (needs ``idx``) -> dict of batched tensors.
         Extension used by ``distributed.forward_sharded``: ``return_image_index=True`` (inference only) -> (persons, image id [P]);
         ``return_batched=True`` (inference only) -> (dict of batched tensors [P, ...], image id [P]) instead of the per-person list.
-        ``return_readout=True`` (training mode only) adds ``out["readout"]``: a contiguous ``[P, 318 + num_betas + 3 + 10]`` copy of the
-        decoder's read-out rows ``pose6d | betas | cam | expr`` (what ``decode_readout`` takes).
+        ``return_readout=True`` (training mode) adds ``out["readout"]``: a contiguous ``[P, 318 + num_betas + 3 + 10]`` copy of the
+        decoder's read-out rows ``pose6d | betas | cam | expr`` (what ``decode_readout`` takes).  In inference it is read together with
+        ``return_batched=True`` only: the batched dict then also holds ``readout``, ``offset [P, 2]`` and ``idx``, the detections'
+        (image, y, x) as three int64 tensors -- what ``decode_readout`` and ``KeypointFitter.fit`` take (no person: the empty dict).
         ``train_heads=True`` (needs ``is_training=True`` and ``return_readout=True``): the same dict, key for key and bit for bit, with
         ``out["readout"]`` and ``out["offset"]`` attached to autograd with respect to ``heads_parameters()`` (those that require grad:
         ``train_heads_(True)``) -- ``decode_readout`` and ``Loss`` on top, ``backward()``, an optimiser step, ``repack_heads()``.  The
@@ -855,8 +857,9 @@ class Model(nn.Module):
         # nothing.  The first call, and a batch with more persons than the capacity, take the count first (exact sizes).
         cap = self._person_cap.get(B)
         o = persons = None
+        keep = {} if (batched and with_readout) else None          # the read-out rows of the heads launch whose outputs are returned
         if cap is not None:
-            o, det, info, persons = self._detect_and_heads(P, ws, K, k, thr, cap, not batched, stream)
+            o, det, info, persons = self._detect_and_heads(P, ws, K, k, thr, cap, not batched, stream, keep)
             Pn = int(info[3].item())                       # the host sync
             if Pn > cap:
                 o = persons = None
@@ -868,10 +871,15 @@ class Model(nn.Module):
         if Pn == 0:
             return (([] if not batched else {}), torch.zeros(0, dtype=torch.int32, device=dev)) if (with_ids or batched) else []
         if o is None:
-            o, det, info, persons = self._detect_and_heads(P, ws, K, k, thr, Pn, not batched, stream)
+            o, det, info, persons = self._detect_and_heads(P, ws, K, k, thr, Pn, not batched, stream, keep)
         ids = det[0][:Pn]
         if batched:
-            return {n: o[n][:Pn] for n in self.PERSON_KEYS}, ids
+            out = {n: o[n][:Pn] for n in self.PERSON_KEYS}
+            if with_readout:                               # what decode_readout and KeypointFitter.fit take
+                out["readout"] = keep["dec"][:Pn, :318 + P["hph"]["nb"] + 13].contiguous()
+                out["offset"] = o["offset"][:Pn]
+                out["idx"] = tuple(det[i][:Pn].long() for i in range(3))
+            return out, ids
         persons = persons[:Pn]
         return (persons, ids) if with_ids else persons
 
@@ -924,8 +932,9 @@ class Model(nn.Module):
         keys = self.PERSON_KEYS
         return [dict(zip(keys, vals)) for vals in zip(*(o[n][:rows].unbind(0) for n in keys))]
 
-    def _detect_and_heads(self, P, ws, K, k, thr, cap, with_dicts, stream):
-        """Ordered compaction of the detections into `cap` person rows + HPH + SMPL-X layer for those rows (ws["counts"] is in flight)."""
+    def _detect_and_heads(self, P, ws, K, k, thr, cap, with_dicts, stream, keep=None):
+        """Ordered compaction of the detections into `cap` person rows + HPH + SMPL-X layer for those rows (ws["counts"] is in flight).
+        ``keep``: as in ``_heads``."""
         L = _lib.lib()
         dev, B, G = K.device, K.shape[0], P["G"]
         gstart_t, chunks_t, info, ngc, ncc, det, base = self._tables(B, cap, dev, with_det=True)
@@ -940,7 +949,7 @@ class Model(nn.Module):
                                         chunks_t.data_ptr(), ncc, info.data_ptr(), stream), "mhmr_person_groups")
         _lib.check(L.mhmr_detect_write_cap(ws["scores"].data_ptr(), B, G, k, thr, base.data_ptr(), det[0].data_ptr(), det[1].data_ptr(),
                                            det[2].data_ptr(), scores_det.data_ptr(), cap, stream), "mhmr_detect_write_cap")
-        self._heads(P, ws, K, det, cap, gstart_t, ngc, chunks_t, ncc, info, stream, o)
+        self._heads(P, ws, K, det, cap, gstart_t, ngc, chunks_t, ncc, info, stream, o, keep=keep)
         return o, det, info, persons
 
     #: output tensors of the heads: name -> trailing shape (rows = persons)
