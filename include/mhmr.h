@@ -1397,6 +1397,86 @@ long long mhmr_vit_embed_backward_workspace_bytes(int B, int G, int M, int C);
 int mhmr_vit_embed_backward(const mhmr_vit_embed_backward_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Track persons across video frames and smooth them (csrc/track.hip).  One call consumes the
+ * person rows of F consecutive frames -- img_id [P] int64 non-decreasing with values in [0, F) (the order the forward
+ * emits), idx_y, idx_x [P] int64, transl [P][3], readout [P][D] with D = 318 + nb + 13, offset [P][2] = (x, y) -- and
+ * a table of `capacity` slots that lives in a caller-owned device buffer of mhmr_track_state_bytes(capacity, D)
+ * bytes.  A zero-filled buffer is the empty tracker; the call reads and writes the table, and two calls of F1 and
+ * F2 frames leave the table and the outputs that one call of F1 + F2 frames leaves, bit for bit.  Frames without
+ * rows are ordinary; P == 0 lets F frames of time pass.  Everything is fp32, every operation rounded on its own
+ * (no fused multiply-add); there are no atomics, no allocation and no synchronisation, every element of every
+ * output is written by every call, the inputs are never written, two calls give the same bits.
+ *
+ * The table (all 4-byte aligned; D' = D: the read-out without cam[1:3], plus the two location columns):
+ *   byte 0        long long next_id, then 56 reserved bytes (zero)
+ *   byte 64       long long id [capacity]
+ *   then          float pos [capacity][3] (metres), float vel [capacity][3] (metres per frame)
+ *   then          int missed [capacity], int hits [capacity]         (hits > 0 <=> the slot is live)
+ *   then          float x [capacity][D'], float dx [capacity][D']    (the filter state)
+ * Freeing a slot sets hits = 0 and nothing else.
+ *
+ * Association, frame by frame in order.  For every (detection d = row within the frame, live slot t):
+ *   k = missed_t + 1,  p = pos_t + vel_t * k,  e = transl_d - p,  c = (e_x^2 + e_y^2) + e_z^2;
+ * the pair is gated in when c <= max_dist * max_dist (the float product).  The assignment is the one obtained by
+ * sweeping the gated pairs in ascending order of (bits of c, d, t) and taking a pair when neither its detection nor
+ * its slot is taken: GREEDY, not Hungarian, because it has an exact tie rule and an exact restatement on the CPU
+ * (DESIGN.md section 33).  A NaN cost is never gated in.  Then, in this order:
+ *   1. matched:      vel = (transl_d - pos) / k,  pos = transl_d,  missed = 0,  hits += 1
+ *   2. unmatched live slots:  missed += 1; freed when missed > max_age
+ *   3. unmatched detections, in row order: the lowest free slot (those freed in step 2 of this frame included) with
+ *      id = next_id++, pos = transl_d, vel = 0, missed = 0, hits = 1
+ *   4. no free slot: track_id = -1, hits = 0, the row's outputs are its inputs' bits, the table is not touched.
+ *
+ * Filter: a One-Euro filter per column of z = [readout[:318+nb+1] | readout[318+nb+3:] | u | v] of the matched row,
+ * u = ((float)idx_x + 0.5) + offset_x and v likewise with y: the absolute location in patch cells, so a person who
+ * crosses a cell border is continuous.  cam[1:3] are passed through.  With kf = (float)k, dt = kf / fps and
+ * alpha(fc) = 1 / (1 + (1 / (2 pi fc)) / dt), 2 pi the float nearest to it:
+ *   e = z - x,  d = e / dt,  dx <- dx + alpha(dcutoff) * (d - dx),  fc = mincutoff_g + beta_g * |dx|,  x <- x + alpha(fc) * e
+ * with g the column's group: pose (the 318 6D numbers), shape (betas), depth (cam[0]), expr, loc (u, v).  A group
+ * whose bit in `groups` is clear is a SELECT: its columns keep the input's bits and its state is never written.
+ * readout_s is x scattered back into the row, offset_s = (u^ - ((float)idx_x + 0.5), v^ - ((float)idx_y + 0.5)).  A new
+ * track (hits == 1) sets x = z, dx = 0 and its output rows are the input's bits, the offset included.
+ *
+ * track_id [P] int64, hits [P] int32 (after the update), status [1] int32 on the device: 0 = ok, 1 = img_id decreases
+ * or leaves [0, F): then every id is -1, every hits 0, the rows pass through and the table is untouched.
+ * Refused before the first launch: a NULL descriptor, state, workspace or status, a NULL input or output with P > 0,
+ * F < 1, P < 0, capacity outside 1 ... 1024, max_age < 0, fps, dcutoff or the mincutoff of a selected group not finite
+ * and positive, max_dist or a selected beta negative or not finite, bits of `groups` above the five, a short or
+ * misaligned (8 bytes) state or workspace -> MHMR_ERR_BAD_ARG; P > 65535, nb not 10 or 11 -> MHMR_ERR_BAD_SHAPE.
+ * mhmr_track_state_bytes(capacity, D), mhmr_track_workspace_bytes(F, capacity): monotone in each argument;
+ * negative = the error code.  The workspace holds the journal [F][capacity] (row or none, k, new) that the
+ * association kernel hands to the filter kernel.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define MHMR_TRACK_POSE 1
+#define MHMR_TRACK_SHAPE 2
+#define MHMR_TRACK_DEPTH 4
+#define MHMR_TRACK_EXPR 8
+#define MHMR_TRACK_LOC 16
+#define MHMR_TRACK_MAX_CAPACITY 1024
+typedef struct {
+    int F, P, nb, capacity;
+    const long long *img_id, *idx_y, *idx_x;         /* [P]                                                               */
+    const float *transl, *readout, *offset;          /* [P][3], [P][318 + nb + 13], [P][2]                                */
+    float fps, max_dist;
+    int max_age;
+    int groups;                                      /* MHMR_TRACK_* bits of the filtered groups                          */
+    float dcutoff;
+    float mincutoff_pose, mincutoff_shape, mincutoff_depth, mincutoff_expr, mincutoff_loc;
+    float beta_pose, beta_shape, beta_depth, beta_expr, beta_loc;
+    void* state;
+    long long state_bytes;
+    void* workspace;
+    long long workspace_bytes;
+    long long* track_id;                             /* [P]                                                               */
+    int* hits;                                       /* [P]                                                               */
+    float *readout_s, *offset_s;                     /* [P][318 + nb + 13], [P][2]                                        */
+    int* status;                                     /* [1]                                                               */
+} mhmr_track_desc;
+long long mhmr_track_state_bytes(int capacity, int D);
+long long mhmr_track_workspace_bytes(int F, int capacity);
+int mhmr_track_update(const mhmr_track_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement: hipEvent brackets around every launch of one kernel family (0 = GEMM, 1 = attention, 2 = LBS
  * vertex kernel), recorded on the launch stream.  enable(kind >= 0) starts a fresh window, enable(-1) stops;
  * collect() synchronises the recorded events and returns launches, summed milliseconds and summed work

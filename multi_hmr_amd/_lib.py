@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "fit.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -48,8 +48,10 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: optim.hip: the Adam update is torch's sequence of fp32 operations, each rounded on its own.
 #: attention_bf16.hip: the logit S = fl(QSCALE * acc) is rounded before exp2(S - lse) in all three kernels, as the contract states it.
 #: fit.hip: its update kernel runs optim.hip's Adam element (csrc/adam_element.h) and must round it the same way.
+#: track.hip: the association cost and the One-Euro recursion are rounded operation by operation (the tests restate them in numpy).
 EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
-               "optim.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"]}
+               "optim.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"],
+               "track.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -239,6 +241,19 @@ class FitDesc(C.Structure):
                 [(n, _vp) for n in ("exp_avg", "exp_avg_sq", "objective", "grad", "workspace")] + [("workspace_bytes", C.c_longlong)])
 
 
+TRACK_GROUPS = ("pose", "shape", "depth", "expr", "loc")    # include/mhmr.h MHMR_TRACK_*: bit g of mhmr_track_desc.groups
+TRACK_MAX_CAPACITY = 1024           # include/mhmr.h MHMR_TRACK_MAX_CAPACITY
+
+
+class TrackDesc(C.Structure):
+    """include/mhmr.h mhmr_track_desc."""
+    _fields_ = ([(n, _i) for n in ("F", "P", "nb", "capacity")] + [(n, _vp) for n in ("img_id", "idx_y", "idx_x", "transl", "readout", "offset")] +
+                [("fps", _f), ("max_dist", _f), ("max_age", _i), ("groups", _i), ("dcutoff", _f)] +
+                [("mincutoff_" + g, _f) for g in TRACK_GROUPS] + [("beta_" + g, _f) for g in TRACK_GROUPS] +
+                [("state", _vp), ("state_bytes", C.c_longlong), ("workspace", _vp), ("workspace_bytes", C.c_longlong)] +
+                [(n, _vp) for n in ("track_id", "hits", "readout_s", "offset_s", "status")])
+
+
 class PreImage(C.Structure):
     """include/mhmr.h mhmr_pre_image: one image of mhmr_preprocess_u8_batch (device pointers + the geometry of its plan)."""
     _fields_ = ([("img", _vp)] + [(n, _i) for n in ("H", "W", "ow", "oh", "y0", "rows", "pad_x", "pad_y", "ksh", "ksv")] +
@@ -413,6 +428,9 @@ _SIGS = {
     "mhmr_adam_step": ([C.POINTER(AdamSegment), _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_longlong, _vp, _vp], _i),
     "mhmr_fit_keypoints_workspace_bytes": ([C.POINTER(BodyConsts), _i], C.c_longlong),
     "mhmr_fit_keypoints": ([C.POINTER(FitDesc), _vp], _i),
+    "mhmr_track_state_bytes": ([_i, _i], C.c_longlong),
+    "mhmr_track_workspace_bytes": ([_i, _i], C.c_longlong),
+    "mhmr_track_update": ([C.POINTER(TrackDesc), _vp], _i),
     "mhmr_attention_f32_tape": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "mhmr_attention_f32_backward_workspace_bytes": ([_i, _i, _i], C.c_longlong),
     "mhmr_attention_f32_backward": ([_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp], _i),

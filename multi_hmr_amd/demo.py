@@ -108,17 +108,18 @@ def orbit_extrinsics(center, axis, angles):
 
 
 def create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=False, alpha=0.8, fn='rotating.mp4', n_frames=20,
-                          angle_range=60):
+                          angle_range=60, _color=None):
     """demo.py:188-241: the persons turned about person 0's centre, swept to +angle_range about y, to -angle_range about y and to
     +angle_range about x and back, over a white image, with ``n_frames // 4`` copies of the overlay over the photograph at the start
     and between the sweeps -> the frame list (np.uint8 [H, W, 3]), None when there are no persons.  The 3 n_frames rotated frames
     are one ``render.render_views`` call (the vertex normals computed once, not once per frame).  fn: the frames are written as an
-    animated PNG (100 ms per frame, the reference's 10 fps) to ``splitext(fn)[0] + '.png'``; the reference's mp4 needs cv2."""
+    animated PNG (100 ms per frame, the reference's 10 fps) to ``splitext(fn)[0] + '.png'``; the reference's mp4 needs cv2.
+    ``_color``: the persons' colours (``overlay_human_meshes``' argument), None: the palette by row."""
     from PIL import Image
     from . import render
     if len(humans) == 0:
         return None
-    central, _color = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=unique_color, alpha=alpha, _color=None)
+    central, _color = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=unique_color, alpha=alpha, _color=_color)
     central = central.astype(np.uint8)
     name = "verts_smplx" if "verts_smplx" in humans[0] else "v3d"
     center = humans[0][name].mean(0).detach().cpu().numpy()
@@ -152,7 +153,9 @@ def main(argv=None):
     writes every person's distance from the camera on the overlay panel; --save_mesh 1 adds ``<image>_<model>.png.npy`` (float32
     [P, V, 3], the persons' vertices) and ``<image>_<model>.png.glb`` (``scene.create_scene``: the persons in the overlay's colours,
     the photograph and the camera).  ``--batch_size N`` > 1 infers N images per forward (``pipeline.predict_images``) and draws each
-    result as before.  Returns every path written."""
+    result as before.  ``--video 1`` treats the sorted folder as the consecutive frames of one clip (``pipeline.predict_video`` at
+    ``--batch_size``, 32 when that is 1, and ``--fps``): the persons are tracked and smoothed across the frames and every mesh is
+    coloured by ``track_id % len(PALETTE)``, so a person keeps their colour.  Returns every path written."""
     from argparse import ArgumentParser
     from PIL import Image
     from .preprocess import open_image
@@ -171,6 +174,9 @@ def main(argv=None):
     parser.add_argument("--save_mesh", type=int, default=0, choices=[0, 1])
     parser.add_argument("--batch_size", type=int, default=1, help="> 1: decode, preprocess and infer that many images per forward "
                         "(pipeline.predict_images); the files written are the same")
+    parser.add_argument("--video", type=int, default=0, choices=[0, 1], help="1: the sorted folder is one clip (pipeline.predict_video): "
+                        "tracked, smoothed persons, one colour per track")
+    parser.add_argument("--fps", type=float, default=30.0, help="frame rate of the clip (--video 1)")
     args = parser.parse_args(argv)
     assert torch.cuda.is_available()
     suffixes = (".jpg", ".jpeg", ".png", ".webp")
@@ -187,17 +193,19 @@ def main(argv=None):
     os.makedirs(args.out_folder, exist_ok=True)
     written = []
 
-    def write(img_path, humans, K, img_pil_visu):
-        """Overlay (+ side view, + rotating video) of one image with its full-resolution camera K -> the files of that image."""
+    def write(img_path, humans, K, img_pil_visu, colors=None):
+        """Overlay (+ side view, + rotating video) of one image with its full-resolution camera K -> the files of that image.  ``colors``:
+        one per person (the clip's track colours), None: the palette by row."""
         save_fn = os.path.join(args.out_folder, f"{img_path}_{model_name}.png")
         os.makedirs(os.path.dirname(save_fn), exist_ok=True)
-        pred, _color = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha)
+        pred, _color = overlay_human_meshes(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha,
+                                            _color=colors)
         if args.distance:                                                # demo.py:348-350, with the camera of the photograph
             pred = print_distance_on_image(pred, humans, _color, K=K)
         l_img = [np.asarray(img_pil_visu), pred]
         if args.extra_views:                                             # demo.py:351-354: the side view, 30 degrees about y
             frames = create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha,
-                                           fn=None, n_frames=2, angle_range=30)
+                                           fn=None, n_frames=2, angle_range=30, _color=colors)
             l_img.append(frames[1] if frames is not None else np.full_like(pred, 255))
         Image.fromarray(np.concatenate(l_img, 1).astype(np.uint8)).save(save_fn)
         print(f"{len(humans)} persons -> {save_fn}")
@@ -205,7 +213,7 @@ def main(argv=None):
         if args.save_rotating_video:                                     # demo.py:362-364, an animated PNG for the mp4
             fn = os.path.splitext(save_fn)[0] + "_rotating.mp4"
             if create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=args.unique_color, alpha=args.alpha, fn=fn,
-                                     n_frames=20, angle_range=60) is not None:
+                                     n_frames=20, angle_range=60, _color=colors) is not None:
                 written.append(os.path.splitext(fn)[0] + ".png")
         if args.save_mesh:                                               # demo.py:370-384
             name = "verts_smplx" if humans and "verts_smplx" in humans[0] else "v3d"
@@ -218,6 +226,16 @@ def main(argv=None):
             scene.export(save_fn + ".glb")
             written.extend([save_fn + ".npy", save_fn + ".glb"])
 
+    if args.video:                                                       # the folder is one clip: track, smooth, one colour per track
+        from .pipeline import predict_video
+        from .render import PALETTE
+        from .track import Tracker
+        opened = (Image.open(os.path.join(args.img_folder, p)) for p in l_img_path)
+        for r in predict_video(model, opened, batch_size=args.batch_size if args.batch_size > 1 else 32, tracker=Tracker(model, fps=args.fps),
+                               fov=args.fov, det_thresh=args.det_thresh, nms_kernel_size=args.nms_kernel_size):
+            colors = [PALETTE[h["track_id"] % len(PALETTE)] for h in r.humans] or None
+            write(l_img_path[r.index], r.humans, r.K_full, r.source.convert("RGB"), colors)
+        return written
     if args.batch_size > 1:                                              # one forward per batch_size images, then the same drawing
         from .pipeline import predict_images
         opened = (Image.open(os.path.join(args.img_folder, p)) for p in l_img_path)      # decoded on the pipeline's threads

@@ -5,7 +5,8 @@ every image's persons in input order.
 Two layers:
   * ``run_batched``: the scheduling core -- ordering, batching, the partial last batch, the error policy and the look-ahead -- over
     injected ``decode`` / ``preprocess`` / ``forward`` callables.  It knows nothing of the device (tests drive it with fakes).
-  * ``predict_images``: the callables of the real thing and the per-image camera matrices.
+  * ``predict_images``: the callables of the real thing and the per-image camera matrices; ``predict_video``: the same for the
+    consecutive frames of a clip, with the persons tracked and smoothed across frames (``multi_hmr_amd.track``).
 
 Threads, not processes: PIL releases the GIL while it decodes, and exactly one process has the GPU open.  While the forward of batch n
 is in flight a producer thread decodes and stages batch n + 1 (its pinned staging buffer is packed, its copy and its two preprocessing
@@ -161,6 +162,69 @@ def decode_image(source):
     return img, (W, H)
 
 
+class _Stages:
+    """What ``predict_images`` and ``predict_video`` share: the device, the preprocessor, the ONE stream of the iteration, the stage timers
+    and the ``decode`` / ``preprocess`` callables of ``run_batched``."""
+
+    def __init__(self, model, stats):
+        import torch
+        from .preprocess import Preprocessor
+        self.dev = next(model.parameters()).device
+        self.S = int(model.img_size)
+        self.pre = Preprocessor(self.S, self.dev)
+        self.stream = torch.cuda.current_stream(self.dev)
+        self.st = stats if stats is not None else {}
+        for k in ("decode", "stage", "forward", "wait"):
+            self.st.setdefault(k, 0.0)
+        for k in ("images", "batches"):
+            self.st.setdefault(k, 0)
+        self.lock = threading.Lock()
+
+    def decode(self, source):
+        import time
+        t0 = time.perf_counter()
+        try:
+            return decode_image(source)
+        finally:
+            dt = time.perf_counter() - t0
+            with self.lock:
+                self.st["decode"] += dt
+
+    def preprocess(self, items):
+        import time
+        import torch
+        t0 = time.perf_counter()
+        with torch.cuda.stream(self.stream):           # the producer thread enqueues on the iteration's stream
+            x = self.pre.batch([img for img, _ in items])
+        self.st["stage"] += time.perf_counter() - t0
+        return x
+
+    def results(self, forward, sources, batch_size, workers, on_error):
+        """``run_batched`` with these stages and ``forward(x, items) -> [(humans, K [1, 3, 3])]`` -> the ``ImageResult`` of every source."""
+        import time
+        st, S = self.st, self.S
+        gen = run_batched(sources, self.decode, self.preprocess, forward, batch_size=batch_size, workers=workers, on_error=on_error)
+        consumed = 0.0
+        try:
+            while True:
+                t0 = time.perf_counter()
+                try:
+                    index, source, item, output, error = next(gen)
+                except StopIteration:
+                    return
+                finally:
+                    consumed += time.perf_counter() - t0
+                    st["wait"] = consumed - st["forward"]
+                if error is not None:
+                    yield ImageResult(index, source, None, error=error)
+                    continue
+                humans, K = output
+                size = item[1]
+                yield ImageResult(index, source, humans, K, full_resolution_K(K, size, S), size)
+        finally:
+            gen.close()
+
+
 def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_kernel_size=3, workers=DEFAULT_WORKERS,
                    on_error="raise", stats=None):
     """Generator of one ``ImageResult`` per source, in input order.  ``sources``: file paths, PIL images or uint8 ``[H, W, 3]``
@@ -174,38 +238,14 @@ def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_ke
     the consumer waiting for a staged batch) and the counts ``images`` / ``batches``."""
     import time
     import torch
-    from .preprocess import Preprocessor, get_camera_parameters
-    dev = next(model.parameters()).device
-    S = int(model.img_size)
-    pre = Preprocessor(S, dev)
-    stream = torch.cuda.current_stream(dev)
-    st = stats if stats is not None else {}
-    for k in ("decode", "stage", "forward", "wait"):
-        st.setdefault(k, 0.0)
-    for k in ("images", "batches"):
-        st.setdefault(k, 0)
-    lock = threading.Lock()
-
-    def decode(source):
-        t0 = time.perf_counter()
-        try:
-            return decode_image(source)
-        finally:
-            dt = time.perf_counter() - t0
-            with lock:
-                st["decode"] += dt
-
-    def preprocess(items):
-        t0 = time.perf_counter()
-        with torch.cuda.stream(stream):                # the producer thread enqueues on the iteration's stream
-            x = pre.batch([img for img, _ in items])
-        st["stage"] += time.perf_counter() - t0
-        return x
+    from .preprocess import get_camera_parameters
+    sg = _Stages(model, stats)
+    st, S, dev = sg.st, sg.S, sg.dev
 
     def forward(x, items):
         t0 = time.perf_counter()
         B = x.shape[0]
-        with torch.cuda.stream(stream):                # the stream the batch was preprocessed on
+        with torch.cuda.stream(sg.stream):             # the stream the batch was preprocessed on
             K = get_camera_parameters(S, fov=fov, device=dev, batch=B)
             humans, ids = model(x, is_training=False, nms_kernel_size=int(nms_kernel_size), det_thresh=det_thresh, K=K,
                                 return_image_index=True)
@@ -217,23 +257,53 @@ def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_ke
         st["images"] += B
         return [(per_image[b], K[b:b + 1]) for b in range(B)]
 
-    gen = run_batched(sources, decode, preprocess, forward, batch_size=batch_size, workers=workers, on_error=on_error)
-    consumed = 0.0
-    try:
-        while True:
-            t0 = time.perf_counter()
-            try:
-                index, source, item, output, error = next(gen)
-            except StopIteration:
-                return
-            finally:
-                consumed += time.perf_counter() - t0
-                st["wait"] = consumed - st["forward"]
-            if error is not None:
-                yield ImageResult(index, source, None, error=error)
-                continue
-            humans, K = output
-            size = item[1]
-            yield ImageResult(index, source, humans, K, full_resolution_K(K, size, S), size)
-    finally:
-        gen.close()
+    yield from sg.results(forward, sources, batch_size, workers, on_error)
+
+
+def predict_video(model, frames, batch_size=32, tracker=None, fov=60, det_thresh=0.3, nms_kernel_size=3, workers=DEFAULT_WORKERS,
+                  on_error="raise", stats=None):
+    """``predict_images`` for the consecutive frames of one clip: the same sources, batching, stream, ``ImageResult`` and ``stats``, with the
+    persons TRACKED and SMOOTHED across frames and batches.  Per batch: one ``Model.forward`` (``return_batched=True,
+    return_readout=True``), one ``Tracker.update`` and one ``decode_readout`` of the filtered rows.  Every person dict holds the ten
+    ``Model.PERSON_KEYS`` of the smoothed person (``scores`` is the detection's) plus ``track_id`` (int; -1: the tracker's table was full)
+    and ``hits`` (int; frames the track has been seen in).  ``tracker``: a ``Tracker`` of this model (its table persists, so a second clip
+    needs ``tracker.reset()``); ``None``: ``Tracker(model)``.  A ``Tracker(model, smooth=None)`` only tracks: the persons are
+    ``predict_images``' bit for bit.  The ids go to the host in one copy per batch, and the tracker's ``status`` is checked there (it raises
+    ``RuntimeError``).  A source that ``on_error="skip"`` skips is not shown to the tracker: for it no time passes."""
+    import time
+    import torch
+    from .preprocess import get_camera_parameters
+    from .track import Tracker
+    sg = _Stages(model, stats)
+    st, S, dev = sg.st, sg.S, sg.dev
+    tracker = tracker if tracker is not None else Tracker(model)
+    keys = model.PERSON_KEYS
+
+    def forward(x, items):
+        t0 = time.perf_counter()
+        B = x.shape[0]
+        with torch.cuda.stream(sg.stream), torch.no_grad():
+            K = get_camera_parameters(S, fov=fov, device=dev, batch=B)
+            out, ids = model(x, is_training=False, nms_kernel_size=int(nms_kernel_size), det_thresh=det_thresh, K=K, return_batched=True,
+                             return_readout=True)
+            res = tracker.update(out, ids, B)
+            per_image = [[] for _ in range(B)]
+            if out:
+                dec = model.decode_readout(res.readout, res.offset, out["idx"], K)
+                cols = [(out["scores"] if n == "scores" else dec[n].detach()).unbind(0) for n in keys]
+                Pn = int(ids.shape[0])
+                host = torch.cat([res.status.long(), ids.long(), res.track_id, res.hits.long()]).tolist()     # the one copy to the host
+            else:
+                cols, Pn, host = [], 0, res.status.tolist()
+            if host[0] != 0:
+                raise RuntimeError(f"Tracker.update refused the batch (status {host[0]}): the image ids of the forward are not ascending")
+            for p, vals in enumerate(zip(*cols)):
+                h = dict(zip(keys, vals))
+                h["track_id"], h["hits"] = host[1 + Pn + p], host[1 + 2 * Pn + p]
+                per_image[host[1 + p]].append(h)
+        st["forward"] += time.perf_counter() - t0
+        st["batches"] += 1
+        st["images"] += B
+        return [(per_image[b], K[b:b + 1]) for b in range(B)]
+
+    yield from sg.results(forward, frames, batch_size, workers, on_error)
