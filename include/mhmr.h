@@ -1126,6 +1126,62 @@ int mhmr_adam_step(const mhmr_adam_segment* segs_host, const mhmr_adam_segment* 
                    double max_norm, double* partials, long long partials_count, float* norm_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Device re-pack of the DERIVED encoder operands (csrc/encoder_pack.hip): with mhmr_adam_step
+ * over the whole model it replaces the reference's optimizer.step() (train.py:304) plus the host re-pack after it.
+ * A table of jobs; all MHMR_PACK_ROW jobs first, then the MHMR_PACK_POS jobs; one launch per kind.
+ *
+ * MHMR_PACK_ROW -- what vit.pack_block derives from one fp32 linear w [N, K] (K % 4 == 0), one wave per row n:
+ *   Wf[n][k]  = w[n][k] * ln_w[k] (ONE fp32 multiply) with ln_w / ln_b non-NULL (the LayerNorm fold), else w[n][k]
+ *   w16       non-NULL: row n at w16 + n * pitch16 (elements) = round16(Wf[n]), dtype MHMR_ADAM_PACK_F16 / _BF16,
+ *             round to nearest even, f16 subnormals kept; columns K .. pitch16 are never written
+ *   lo        lo_form MHMR_PACK_LO_PAIR: rows lo_row0 .. lo_row0 + lo_rows - 1 of w also get row n - lo_row0 of lo,
+ *             [hi | lo] = [round16(Wf) | round16(Wf - (float)hi)], the sections lo_section (>= K) elements apart, the
+ *             rows lo_pitch apart; MHMR_PACK_LO_TRIPLE: [hi | lo | hi] (the f16x3 operand); _NONE: lo must be NULL
+ *   bias_out  non-NULL (needs bias and the fold): bias_out[n] = (float)((double)bias[n] + sum_k (double)w[n][k] * ln_b[k])
+ *   colsum    non-NULL: colsum[n] = (float)(sum_k hi[n][k] (+ lo[n][k] on the rows of a _PAIR low half)), in fp64
+ *   Both sums: lane l of the wave adds the elements k with (k / 4) % 64 == l in ascending k (hi before lo), then the 64
+ *   lanes are added as a butterfly (l with l ^ 32, ^ 16, ..., ^ 1): the order depends on K alone.
+ *   row0      cumulative N of the row jobs before this one (0 for the first).
+ * MHMR_PACK_POS -- packing.interpolate_pos_embed + the class row of vit.pack_embeddings: pos_embed fp32 [1 + M*M][C],
+ *   cls_token [C] -> pos [1 + G*G][C], cls_pos0 [C] = cls_token + pos[0] (fp32 add).  tap_w fp64 [G][4] / tap_i int
+ *   [G][4]: the separable bicubic weights and clipped source indices of packing._cubic_taps (device memory, made on
+ *   the host once per pack).  pos[1 + y*G + x][c] = (float) sum_b tap_w[x][b] * (sum_a tap_w[y][a] *
+ *   grid[tap_i[y][a]][tap_i[x][b]][c]), fp64, both sums in tap order, rounded once.  G == M copies the table (the
+ *   taps may be NULL).  row0: cumulative 1 + G*G of the position jobs before this one.
+ * Every element has one writer; no atomics: two calls give the same bits.  `jobs_host` / `jobs_dev` as the two
+ * tables of mhmr_adam_step.  Validated on the host copy before any launch -- MHMR_ERR_BAD_ARG: njobs < 0, a NULL
+ * table, an unknown kind or a row job behind a position job, a NULL w, a dtype that is not _F16 / _BF16, ln_w
+ * without ln_b (or the reverse), bias_out without bias or without the fold, lo_form set with lo NULL (or the
+ * reverse), a row job that writes nothing, a wrong row0, NULL position tensors, NULL taps with G != M, two
+ * targets of the table that overlap.  MHMR_ERR_BAD_SHAPE: N, K, M, G, C < 1, K % 4 != 0, pitch16 < K, lo rows
+ * outside [0, N), lo_section < K, a lo_pitch that does not hold the sections, 2^31 or more rows.  njobs == 0
+ * launches nothing.  No device allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define MHMR_PACK_ROW 0
+#define MHMR_PACK_POS 1
+#define MHMR_PACK_LO_NONE 0
+#define MHMR_PACK_LO_PAIR 1
+#define MHMR_PACK_LO_TRIPLE 2
+typedef struct {
+    const float* w;
+    const float* ln_w;
+    const float* ln_b;
+    const float* bias;
+    void* w16;
+    void* lo;
+    float* bias_out;
+    float* colsum;
+    const float* pos_embed;
+    const float* cls_token;
+    const double* tap_w;
+    const int* tap_i;
+    float* pos;
+    float* cls_pos0;
+    int kind, dtype, row0, N, K, pitch16, lo_form, lo_row0, lo_rows, lo_section, lo_pitch, M, G, C;
+} mhmr_pack_job;
+int mhmr_vit_repack(const mhmr_pack_job* jobs_host, const mhmr_pack_job* jobs_dev, int njobs, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Fit persons to 2D keypoints (csrc/fit.hip): Adam on the read-out row r = [pose6d 318 | betas nb |
  * cam 3 | expr 10] and the offset o [2] of every person, from the anchors r0, o0 (the network's prediction), against
  * targets kp [NJ][2] in pixels with weights c [NJ] >= 0 (c = 0: the joint is not given), NJ = J + E + L of the body model.

@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -47,10 +47,11 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: loss.hip: every element of the training loss is the reference's fp32 subtraction(s), rounded one by one (its sign is the gradient).
 #: optim.hip: the Adam update is torch's sequence of fp32 operations, each rounded on its own.
 #: attention_bf16.hip: the logit S = fl(QSCALE * acc) is rounded before exp2(S - lse) in all three kernels, as the contract states it.
+#: encoder_pack.hip: the LayerNorm fold is one fp32 multiply and the low half one fp32 subtraction, as vit.pack_block rounds them.
 #: fit.hip: its update kernel runs optim.hip's Adam element (csrc/adam_element.h) and must round it the same way.
 #: track.hip: the association cost and the One-Euro recursion are rounded operation by operation (the tests restate them in numpy).
 EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
-               "optim.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"],
+               "optim.hip": ["-ffp-contract=off"], "encoder_pack.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"],
                "track.hip": ["-ffp-contract=off"]}
 
 
@@ -342,6 +343,18 @@ ADAM_CHUNK = 2048                   # include/mhmr.h MHMR_ADAM_CHUNK
 ADAM_PACK_NONE, ADAM_PACK_F32, ADAM_PACK_F16, ADAM_PACK_BF16 = range(4)
 
 
+class PackJob(C.Structure):
+    """include/mhmr.h mhmr_pack_job."""
+    _fields_ = ([(n, _vp) for n in ("w", "ln_w", "ln_b", "bias", "w16", "lo", "bias_out", "colsum", "pos_embed", "cls_token", "tap_w", "tap_i",
+                                    "pos", "cls_pos0")] +
+                [(n, _i) for n in ("kind", "dtype", "row0", "N", "K", "pitch16", "lo_form", "lo_row0", "lo_rows", "lo_section", "lo_pitch",
+                                   "M", "G", "C")])
+
+
+PACK_ROW, PACK_POS = 0, 1           # include/mhmr.h MHMR_PACK_*
+PACK_LO_NONE, PACK_LO_PAIR, PACK_LO_TRIPLE = range(3)
+
+
 _SIGS = {
     "mhmr_version": ([], _i),
     "mhmr_source_hash": ([], C.c_char_p),
@@ -426,6 +439,7 @@ _SIGS = {
     "mhmr_loss_forward": ([C.POINTER(LossDesc), _vp, C.c_longlong, _vp, _vp], _i),
     "mhmr_loss_backward": ([C.POINTER(LossDesc), _vp, _fp, C.POINTER(LossGrads), _vp], _i),
     "mhmr_adam_step": ([C.POINTER(AdamSegment), _vp, _i, C.c_double, C.c_double, C.c_double, C.c_double, _vp, C.c_longlong, _vp, _vp], _i),
+    "mhmr_vit_repack": ([C.POINTER(PackJob), _vp, _i, _vp], _i),
     "mhmr_fit_keypoints_workspace_bytes": ([C.POINTER(BodyConsts), _i], C.c_longlong),
     "mhmr_fit_keypoints": ([C.POINTER(FitDesc), _vp], _i),
     "mhmr_track_state_bytes": ([_i, _i], C.c_longlong),

@@ -5,9 +5,10 @@ Two differences from the reference, both on purpose:
 
 * by default it trains the heads (``x_attention_head``, ``mlp_offset``) and the detector (``mlp_classif``) on a FROZEN backbone, so the
   optimiser holds ``model.heads_parameters()`` (+ ``model.detection_parameters()``), not ``model.parameters()``; ``--train_backbone N``
-  adds the final norm and the last N encoder blocks (and, with N = the depth, the token embedding) under ``torch.optim.Adam``;
+  adds the final norm and the last N encoder blocks (and, with N = the depth, the token embedding) under ``torch.optim.Adam``, or
+  under ``ModelAdam`` with ``--fused_adam 1`` (DESIGN.md section 34);
 * the master weights are fp32 and there is no autocast: the 16-bit operands of the forward are the model's packed copies, which the
-  optimiser step rewrites (``HeadsAdam``) or ``repack_heads()`` / ``repack_backbone()`` refresh (any other ``torch.optim`` optimiser).
+  optimiser step rewrites (``HeadsAdam``, ``ModelAdam``) or ``repack_heads()`` / ``repack_backbone()`` refresh (any other ``torch.optim`` optimiser).
   ``--amp 1`` (the reference's default) gives the linears of the backbone BACKWARD bf16 operands with fp32 accumulation (DESIGN.md
   section 30), ``--amp_attention 1`` (default 0) its attention tape and backward as well (section 31); the heads' backward and every
   forward are what they are without them.
@@ -26,7 +27,7 @@ import torch
 
 from . import _lib
 from .evaluate import Evaluator, evaluate_dataset
-from .optim import HeadsAdam
+from .optim import HeadsAdam, ModelAdam
 
 
 class AverageMeter:
@@ -62,7 +63,7 @@ class Trainer:
     """``Trainer(model, loss, optimizer, args, gt_builder, evaluator=None, writer=None)``.
 
     ``model``: a ``Model`` on the GPU with ``train_heads_(True)`` and / or ``train_detection_(True)``; ``loss``: a ``Loss``; ``optimizer``: a
-    ``HeadsAdam`` (the step rewrites the packed weights) or any ``torch.optim`` optimiser over the same parameters (``repack_heads()`` then
+    ``HeadsAdam`` / ``ModelAdam`` (the step rewrites the packed weights) or any ``torch.optim`` optimiser over the same parameters (``repack_heads()`` then
     runs after every step); ``gt_builder``: a ``GroundTruth``; ``evaluator``: an ``Evaluator`` whose regressors the evaluation uses.
     ``args`` (a namespace) is read for ``save_dir`` ("logs"), ``name`` ("trainval"), ``max_epochs`` (1), ``log_freq`` (100), ``nb_max_ckpt``
     (10), ``det_thresh`` (0.3) and ``nms_kernel_size`` (3); ``log_dir``, ``ckpt_dir`` and ``visu_dir`` are written back into it as the reference
@@ -93,7 +94,7 @@ class Trainer:
             return None
         heads = any(p.requires_grad for p in model.heads_parameters())
         detection = any(p.requires_grad for p in model.detection_parameters())
-        # backbone parameters in the optimiser's groups (any torch.optim optimiser; HeadsAdam covers the heads and the detector only)
+        # backbone parameters in the optimiser's groups (ModelAdam or any torch.optim optimiser; HeadsAdam covers the heads and the detector only)
         in_opt = {id(p) for g in getattr(opt, "param_groups", ()) for p in g["params"]}
         backbone = any(p.requires_grad and id(p) in in_opt for p in model.backbone_parameters(model._backbone_n) + model.embedding_parameters())
         if not (heads or detection or backbone):
@@ -111,7 +112,7 @@ class Trainer:
         opt.step()
         if not isinstance(opt, HeadsAdam):
             model.repack_heads()
-        if backbone:
+        if backbone and not isinstance(opt, ModelAdam):           # (ModelAdam's step has rewritten the packed encoder as well)
             model.repack_backbone()
         opt.zero_grad(set_to_none=True)
         return dict_loss
@@ -267,6 +268,10 @@ def build_parser():
     p.add_argument("--nb_max_ckpt", type=int, default=10)
     p.add_argument("--learning_rate", "-lr", type=float, default=5e-6)
     p.add_argument("--train_detection", type=int, default=1, choices=[0, 1])
+    p.add_argument("--fused_adam", type=int, default=0, choices=[0, 1],
+                   help="with --train_backbone N > 0: 1 = ModelAdam, one fused step over the whole model that rewrites the packed weights; "
+                        "0 = torch.optim.Adam and a re-pack after every step")
+    p.add_argument("--max_grad_norm", type=float, default=None, help="global gradient-norm clipping inside HeadsAdam / ModelAdam (default: none)")
     p.add_argument("--extension", type=str, default="png", choices=["png", "jpg"])
     p.add_argument("--res", type=int, default=None)
     p.add_argument("--flip", type=int, default=1, choices=[0, 1])
@@ -281,16 +286,20 @@ def build_parser():
 def make_optimizer(model, args):
     """The optimiser of the command line.  ``--train_backbone 0``: ``HeadsAdam`` over the heads (and the detector).  ``--train_backbone N``:
     ``train_backbone_(N, precision="bf16" if --amp else "f32", attention="bf16" if --amp_attention else "f32")``, ``train_embeddings_()`` when N is the encoder's depth, and ``torch.optim.Adam``
-    over heads, detector, backbone and embedding parameters (the ``Trainer`` re-packs after each step)."""
+    over heads, detector, backbone and embedding parameters (the ``Trainer`` re-packs after each step) -- or, with ``--fused_adam 1``,
+    ``ModelAdam`` over the same list (its step rewrites the packed weights).  ``--max_grad_norm`` goes to ``HeadsAdam`` / ``ModelAdam``."""
     n, detection = int(getattr(args, "train_backbone", 0) or 0), bool(args.train_detection)
+    clip = getattr(args, "max_grad_norm", None)
     if n <= 0:
-        return HeadsAdam(model, lr=args.learning_rate, detection=detection)
+        return HeadsAdam(model, lr=args.learning_rate, detection=detection, max_grad_norm=clip)
     model.train_backbone_(n, precision="bf16" if int(getattr(args, "amp", 1)) else "f32",
                           attention="bf16" if int(getattr(args, "amp_attention", 0)) else "f32")
     params = model.heads_parameters() + (model.detection_parameters() if detection else []) + model.backbone_parameters(n)
     if n == len(model.backbone.encoder.blocks):
         model.train_embeddings_()
         params += model.embedding_parameters()
+    if int(getattr(args, "fused_adam", 0) or 0):
+        return ModelAdam(model, lr=args.learning_rate, detection=detection, max_grad_norm=clip)
     return torch.optim.Adam(params, lr=args.learning_rate)
 
 
