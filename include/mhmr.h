@@ -747,6 +747,60 @@ int mhmr_eval_mesh_errors(const float* pred, const float* gt, const float* pred_
                           int V, float* pve, float* pa_pve, float* Rts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Evaluation of a whole batch on the device: the reference's greedy 2D matching
+ * (utils/training.py:26-147, the form its evaluation calls: valid=None, every joint valid) image by image, and the
+ * metrics above read through the matcher's pair list.  Nothing is copied back and nothing synchronises.
+ *
+ * mhmr_eval_match.  Predictions pred_j2d: P rows, pred_stride floats apart (>= 2 J), of which the first J joints
+ * (x, y) are read; pred_img [P] the image of each row, ascending, in [0, B).  Ground truth gt_j2d [G][J][2] and
+ * gt_img [G], likewise.  One workgroup per image; an image may have no prediction, no ground truth, or neither.
+ *   cost(p, g)  np.linalg.norm(D, 2), the SPECTRAL norm of the [J][2] matrix D = pred - gt formed in fp32: with
+ *               a = sum dx^2, b = sum dx dy, c = sum dy^2 accumulated in fp64 in joint order,
+ *               cost = sqrt((a + c) / 2 + sqrt(((a - c) / 2)^2 + b^2)).
+ *   iou(p, g)   get_bbx_overlap of the two boxes over all J joints, in fp32 in the host code's operation order
+ *               (inclusive +1 pixel convention; every operation rounded on its own), compared as fp32 with
+ *               iou_thresh.
+ *   loop        while assigned_gt < nG and assigned_pred + fp_rounds < nP: take the remaining pair of lowest
+ *               cost (lowest flat index p nG + g on ties, as np.argmin) and remove it; both members free and
+ *               iou >= iou_thresh: a match; iou < iou_thresh, whatever the members' state: one false-positive
+ *               round (the loop's own counter); otherwise go on.  When the pairs run out the loop stops.
+ * Outputs.  Image i owns min(nP_i, nG_i) consecutive slots of pair_pred / pair_gt [min(P, G)], in image order;
+ * its matches fill them in the order the loop finds them, as indices into the P and G rows; every other slot is
+ * -1.  pred_fp [P] / gt_miss [G]: 1 for a prediction / ground truth without a match, else 0.  counters [4] int64
+ * {count, miss, fp, matched} (count = ground truths, miss / fp = the two flags' sums): ADDED to; the images'
+ * partial counts are summed by one thread in image order.  status [1]: STICKY (ORed into), bits MHMR_EVAL_*:
+ *   DEGENERATE_BOX  an image with pairs has a person whose box has no width or no height (the host's assert);
+ *   NONFINITE       a keypoint among the J of a row is NaN or infinite;
+ *   BAD_IMAGE_IDS   an image column is not ascending or leaves [0, B): the whole call matches nothing.
+ * An image with one of the first two bits is left out: its slots -1, its flags 0, nothing counted; the other
+ * images of the call are unaffected.  workspace: mhmr_eval_match_workspace_bytes(P, G, B) bytes, 8-byte aligned
+ * (the fp64 cost slabs [sum_i nP_i nG_i <= P G], the boxes, the images' segments and partial counts): there is no
+ * per-image capacity.  P, G <= MHMR_EVAL_MAX_PERSONS, B <= MHMR_EVAL_MAX_IMAGES (MHMR_ERR_BAD_SHAPE); P = 0 and
+ * G = 0 are ordinary inputs (their pointers may be NULL).  Three launches on `stream`.
+ *
+ * mhmr_eval_mesh_errors_indexed.  mhmr_eval_mesh_errors with pair m's point sets read at pred[pair_pred[m]]
+ * ([P][V][3]) and gt[pair_gt[m]] ([G][V][3]); the centres ([P][3] / [G][3], NULL = none) are indexed the same
+ * way.  The arithmetic of a pair is that entry's (one device function): pve[m] / pa_pve[m] carry the bits it
+ * gives on gathered copies.  A slot whose index is outside [0, P) / [0, G) (the matcher's -1) writes 0.
+ * sums (nullable) [2] fp64: a second launch of one workgroup adds the valid slots' pve / pa_pve in slot order, in
+ * fp64, and ADDS the two totals to sums; n_valid (nullable, needs sums) [1] int64 gains the number of valid slots.
+ * M == 0 launches nothing.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define MHMR_EVAL_DEGENERATE_BOX 1
+#define MHMR_EVAL_NONFINITE 2
+#define MHMR_EVAL_BAD_IMAGE_IDS 4
+#define MHMR_EVAL_MAX_PERSONS 8192
+#define MHMR_EVAL_MAX_IMAGES 65535
+long long mhmr_eval_match_workspace_bytes(int P, int G, int B);
+int mhmr_eval_match(const float* pred_j2d, long long pred_stride, const int* pred_img, int P, const float* gt_j2d,
+                    const int* gt_img, int G, int J, int B, float iou_thresh, void* workspace, long long workspace_bytes,
+                    int* pair_pred, int* pair_gt, int* pred_fp, int* gt_miss, long long* counters, int* status,
+                    void* stream);
+int mhmr_eval_mesh_errors_indexed(const float* pred, const float* gt, const float* pred_center, const float* gt_center,
+                                  const int* pair_pred, const int* pair_gt, int P, int G, int M, int V, float* pve,
+                                  float* pa_pve, double* sums, long long* n_valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Ground truth for the evaluation loop: what the reference's Trainer.prepare_gt (train.py:58-182)
  * and the 3DPW branch of its evaluate (train.py:383-429) compute with the smplx package and dense matrices.
  *

@@ -242,6 +242,10 @@ class FitDesc(C.Structure):
                 [(n, _vp) for n in ("exp_avg", "exp_avg_sq", "objective", "grad", "workspace")] + [("workspace_bytes", C.c_longlong)])
 
 
+EVAL_STATUS = ("a person's keypoint box has no width or no height", "a keypoint is NaN or infinite",
+               "an image column is not ascending or leaves [0, B)")    # include/mhmr.h MHMR_EVAL_*: bit b of mhmr_eval_match's status
+EVAL_MAX_PERSONS, EVAL_MAX_IMAGES = 8192, 65535                        # include/mhmr.h MHMR_EVAL_MAX_*
+
 TRACK_GROUPS = ("pose", "shape", "depth", "expr", "loc")    # include/mhmr.h MHMR_TRACK_*: bit g of mhmr_track_desc.groups
 TRACK_MAX_CAPACITY = 1024           # include/mhmr.h MHMR_TRACK_MAX_CAPACITY
 
@@ -416,6 +420,9 @@ _SIGS = {
     "mhmr_preprocess_u8_batch": ([C.POINTER(PreImage), _vp, _i, _i, _vp, _vp, _vp], _i),
     "mhmr_preprocess_u8_batch_oriented": ([C.POINTER(PreImageO), _vp, _i, _i, _vp, _vp, _vp], _i),
     "mhmr_eval_mesh_errors": ([_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "mhmr_eval_match_workspace_bytes": ([_i, _i, _i], C.c_longlong),
+    "mhmr_eval_match": ([_vp, C.c_longlong, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "mhmr_eval_mesh_errors_indexed": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "mhmr_body_forward": ([C.POINTER(BodyConsts), _vp, _vp, _vp, _vp, _i] + [_vp] * 6 + [_vp], _i),
     "mhmr_body_backward_workspace_bytes": ([C.POINTER(BodyConsts), _i], C.c_longlong),
     "mhmr_body_backward": ([C.POINTER(BodyBackwardDesc), _vp], _i),

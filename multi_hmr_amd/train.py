@@ -217,12 +217,14 @@ class Trainer:
     @torch.no_grad()
     def evaluate(self, data):
         """``evaluate_dataset`` over ``data`` with the args' ``det_thresh`` / ``nms_kernel_size``; the metrics go to the writer under the data
-        set's ``name`` (``data.dataset.name`` or ``data.name``, "val" otherwise); returns the PVE in mm."""
+        set's ``name`` (``data.dataset.name`` or ``data.name``, "val" otherwise); returns the PVE in mm.  ``args.val_batch_size`` (1) above 1
+        says that ``data`` holds batches of several images: they are evaluated whole, on the device (``batched=True``)."""
         print("\nEVAL: ")
         self.model.eval()
         ev = Evaluator(self.evaluator.smplx2smpl, self.evaluator.h36m_regressor) if self.evaluator is not None else Evaluator()
         summary = evaluate_dataset(self.model, data, self.gt_builder, det_thresh=_arg(self.args, "det_thresh", 0.3),
-                                   nms_kernel_size=_arg(self.args, "nms_kernel_size", 3), evaluator=ev)
+                                   nms_kernel_size=_arg(self.args, "nms_kernel_size", 3), evaluator=ev,
+                                   batched=int(_arg(self.args, "val_batch_size", 1)) > 1)
         name = getattr(getattr(data, "dataset", data), "name", "val")
         print(f"***EVAL METRICS - {name}***")
         for k, v in summary.items():
@@ -259,6 +261,9 @@ def build_parser():
     p.add_argument("--amp_attention", type=int, default=0, choices=[0, 1],
                    help="with --train_backbone: 1 = bf16 operands in the backbone backward's attention tape and backward as well, 0 = exact fp32")
     p.add_argument("--batch_size", type=int, default=2)
+    p.add_argument("--val_batch_size", type=int, default=1,
+                   help="images per validation batch; 1 = image by image with the host matching, as the reference; above 1 the batch is matched "
+                        "per image and measured on the device (its metrics are those of the forward at that batch size)")
     p.add_argument("--num_workers", "-j", type=int, default=8)
     p.add_argument("--img_size", type=int, default=None, help="default: the checkpoint's")
     p.add_argument("--n_iter", "--n_iters_per_epoch", "-iter", type=int, default=100)
@@ -336,7 +341,8 @@ def main(argv=None):
         kw = dict(split=split, training=False, subsample=args.val_subsample[i] if args.val_subsample else 1)
         if name == "BEDLAM":
             kw.update(n=args.val_n[i] if args.val_n else -1, extension=args.extension, res=args.res)
-        vals.append(data.TrainLoader(make(name, **kw), 1, device, workers=args.num_workers))      # the reference evaluates image by image
+        # the reference evaluates image by image; above 1, Trainer.evaluate takes the whole batch on the device
+        vals.append(data.TrainLoader(make(name, **kw), args.val_batch_size, device, workers=args.num_workers))
         print(vals[-1].dataset)
     trainer = Trainer(model, Loss(args), optimizer, args, gt)
     trainer.fit(train, vals)

@@ -6,10 +6,13 @@
            measured copy rate of the MI355X) divided by the time of the whole call (three launches), so a lower bound for the kernel;
   metrics  the 3DPW metric path for 64 matches (smplx2smpl, PVE / PA-PVE, H36M MPJPE / PA-MPJPE: two mhmr_sparse_regress + two
            mhmr_eval_mesh_errors) against the dense 6890 x 10475 matmul + batched SVD registration.
+  validation  evaluate_dataset on the synthetic ViT-L 896^2 model over 64 images: image by image (batched=False, batches of 1) against
+           the batched evaluation (batched=True) in batches of 8 and of 32, per image, with the split into prepare / forward / evaluator
+           and the share of an epoch.
 The two forms of a part are timed alternately (--reps repetitions after --warmup); a time is a host clock around the call ending in a
 device synchronise.  Prints one JSON line per part with median / best / worst of both forms; "faster" is true only if the new path's
 worst repetition beats the torch path's best.
-  python tools/eval_bench.py [--part gt|body|metrics|all] [--reps 15] [--warmup 3]"""
+  python tools/eval_bench.py [--part gt|body|metrics|validation|all] [--reps 15] [--warmup 3]"""
 import argparse
 import json
 import math
@@ -217,9 +220,92 @@ def part_metrics(a):
     return report("metrics_3dpw_64_matches", ms, dict(max_rel_diff_between_forms=diff, dense_matrix_bytes=int(s2s_d.numel() * 4), csr_nnz=rs.nnz))
 
 
+def part_validation(data, a):
+    """The validation loop on the synthetic ViT-L 896^2 model over the same 64 images and ground truth (4 humans per image), three forms
+    timed alternately: evaluate_dataset(batched=False) in batches of 1 (image by image, host matching), batched=True in batches of 8 and
+    of 32.  The synthetic weights make no meaningful detections, so every form runs ``use_gt_idx=True`` (the ground truth's cells through the is_training
+    forward: one prediction per annotated human), which leaves the evaluator the work it has behind a detector that finds everybody.
+    A repetition's time is taken twice, by device events and by the host clock around the whole call (its one final read included).
+    The split into prepare / forward / evaluator comes from a second pass with a synchronise after every phase (their sum exceeds the
+    pipelined time above).  "faster" asks that the batch-32 form's worst repetition beats the per-image form's best."""
+    from multi_hmr_amd import Evaluator, Model, evaluate_dataset
+    S, name, n_img, humans = 896, "dinov2_vitl14", 64, 4
+    mean = synthetic.make_mean_params(0)
+    model = Model(backbone=name, img_size=S, smplx_data=data, mean_params=mean, precision="f16")
+    model.load_state_dict(synthetic.make_state_dict(name, S, seed=0, mean_params=mean), strict=True)
+    model = model.to(DEV).eval()
+    builder = GroundTruth(S, patch_size=14, smplx_neutral=BodyModel(data, "smplx", num_betas=11))
+    g = torch.Generator().manual_seed(0)
+    ys = [go.make_y("smplx", 100 + i, S, [humans], depth=2.6) for i in range(n_img)]
+    xs = [torch.randn(1, 3, S, S, generator=g).to(DEV) for _ in range(n_img)]
+
+    def batches(bs):
+        out = []
+        for i in range(0, n_img, bs):
+            y = {k: (torch.cat([t[k] for t in ys[i:i + bs]]).to(DEV) if isinstance(v, torch.Tensor) else v) for k, v in ys[i].items()}
+            out.append((torch.cat(xs[i:i + bs]), y))
+        return out
+    clone = lambda bl: [(x, {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in y.items()}) for x, y in bl]   # prepare writes into y
+    forms = {"per_image_b1": (batches(1), False), "batched_b8": (batches(8), True), "batched_b32": (batches(32), True)}
+    run = lambda bl, batched: evaluate_dataset(model, bl, builder, use_gt_idx=True, evaluator=Evaluator(), batched=batched)
+    summaries = {k: run(clone(v[0]), v[1]) for k, v in forms.items()}
+    wall, devt = {k: [] for k in forms}, {k: [] for k in forms}
+    for r in range(a.warmup + a.reps):
+        for k, v in forms.items():
+            fresh = clone(v[0])                                                 # outside the clock
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            run(fresh, v[1])
+            e1.record()
+            torch.cuda.synchronize()
+            if r >= a.warmup:
+                wall[k].append((time.perf_counter() - t0) * 1e3 / n_img)
+                devt[k].append(e0.elapsed_time(e1) / n_img)
+
+    def split(bl, batched):
+        t = dict(prepare=0.0, forward=0.0, evaluator=0.0)
+        ev = Evaluator()
+
+        def timed(key, fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            t[key] += (time.perf_counter() - t0) * 1e3 / n_img
+            return out
+        for x, y in clone(bl):
+            gt = timed("prepare", lambda: builder.prepare(y))
+            out = timed("forward", lambda: model(x, idx=gt["idx"], K=gt["K"], is_training=True))
+            if batched:
+                timed("evaluator", lambda: ev.update_batched(out, gt["idx"][0], gt))
+            else:
+                pelvis = out["transl_pelvis"] if "transl_pelvis" in out else out["j3d"][:, :1]
+                pred = [dict(v3d=out["v3d"][i], j3d=out["j3d"][i], j2d=out["j2d"][i], transl_pelvis=pelvis[i]) for i in range(int(gt["idx"][0].shape[0]))]
+                timed("evaluator", lambda: ev.update(pred, gt))
+        timed("evaluator", ev.summary)
+        return {k: round(v, 4) for k, v in t.items()}
+    for k, v in forms.items():
+        split(*v)                                                               # warm
+    stat = lambda v: dict(median_ms=round(float(np.median(v)), 4), best_ms=round(min(v), 4), worst_ms=round(max(v), 4), reps=len(v))
+    out = dict(part="validation_vitl896_64_images", unit="ms per image", humans_per_image=humans)
+    for k, v in forms.items():
+        out[k] = dict(wall=stat(wall[k]), device=stat(devt[k]), split_synchronised=split(*v),
+                      summary={m: round(float(summaries[k][m]), 6) for m in ("pve", "pa_pve", "mpjpe", "pa_mpjpe", "matched", "count")})
+    out["faster"] = bool(max(wall["batched_b32"]) < min(wall["per_image_b1"]))
+    out["median_ratio_b1_over_b32"] = round(float(np.median(wall["per_image_b1"]) / np.median(wall["batched_b32"])), 3)
+    out["margin_ms"] = round(min(wall["per_image_b1"]) - max(wall["batched_b32"]), 4)
+    # share of an epoch of 100 training steps followed by three validation sets of 1000 images (the sizes are an assumption of this line)
+    for tag, step_ms in (("frozen_backbone_14ms_step", 14.0), ("all_blocks_bf16_1700ms_step", 1700.0)):
+        out["epoch_share_" + tag] = {k: round(3000 * float(np.median(wall[k])) / (3000 * float(np.median(wall[k])) + 100 * step_ms), 4) for k in forms}
+    print(json.dumps(out), flush=True)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=["gt", "body", "metrics", "all"], default="all")
+    ap.add_argument("--part", choices=["gt", "body", "metrics", "validation", "all"], default="all")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     a = ap.parse_args()
@@ -232,3 +318,5 @@ if __name__ == "__main__":
         part_body(data, a)
     if a.part in ("metrics", "all"):
         part_metrics(a)
+    if a.part in ("validation", "all"):
+        part_validation(data, a)
