@@ -21,7 +21,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_pre_image_o, mhmr_preprocess_u8_batch_oriented; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
+#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_pre_image_o, mhmr_preprocess_u8_batch_oriented; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points; mhmr_vit_plan); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
 #define MHMR_OK 0
 #define MHMR_ERR_BAD_ARG (-1)
@@ -91,7 +91,7 @@ typedef struct {
     int dtype;              /* MHMR_DT_*                                                                  */
     int B, S, C, H, L;      /* images, image size (S % 14 == 0), embed dim (= 64 H), heads, depth         */
     int G, N, T, Tp;        /* S/14, G*G, N+1, rows per image: T rounded up to a multiple of 64 (128 when a linear
-                               of the encoder runs on the 128x128 kernel: B*Tp or C not a multiple of 256).
+                               of the encoder runs on the 128x128 kernel: B*Tp or C not a multiple of 256) -- mhmr_vit_plan says which.
                                Token rows of image b: patch n (= y*G + x) at row b*Tp + n, the CLASS token at row b*Tp + N
                                (last: attention is permutation-equivariant), zeros behind it */
     int Kp;                 /* 588 rounded up to a multiple of 64 (= 640)                                 */
@@ -183,6 +183,61 @@ int mhmr_vit_forward(const mhmr_vit_desc* d, const float* x, float* feat32, void
 #define MHMR_VIT_FORM_FC1MAP 0x200u      /* fc1 alone under the token-row map                                                    */
 #define MHMR_VIT_FORM_X3 0x400u          /* the f16x3 forward: none of the other bits                                            */
 int mhmr_vit_form_bits(const mhmr_vit_desc* d, void* stream, unsigned* bits);
+
+/* How to lay out the workspaces of a mhmr_vit_desc, BEFORE there is one: rows per image, row pitch, which optional workspaces to allocate,
+ * and the form mhmr_vit_forward then runs.  The one statement of the rule (csrc/vit_plan.h): mhmr_vit_forward decides its form from the
+ * same file.  Host only: no stream, no device memory; with ncu > 0 it runs on a machine without a GPU.
+ * Rows per image (Tp), T = N + 1 tokens, in the order the rule is applied:
+ *   x3:                                T rounded up to 256 (C % 256 == 0) or 128: all rows through every linear.
+ *   fold, and no token-row map:        T rounded up to 256 -- cpad packs (C = 384), N % 256 != 0, and TINY batches, whose narrowest
+ *                                      linear (B * roundup(T, 256) / 256 * C / 256 tiles of 256x256) is at most 128 tiles: half a round
+ *                                      of the 256 CUs the rule was measured on, a fixed number of the rule and not of the device.
+ *   token-row map, or all 256-tiles:   T rounded up to 64 -- C % 256 == 0 and N % 256 == 0 (the block GEMMs cover the B * N patch rows,
+ *                                      the class rows go through the class-row kernel), or C % 256 == 0 and B * roundup(T, 64) % 256
+ *                                      == 0; B * Tp * C * 4 < 2^32 either way (32-bit residual offsets of the 256x256 kernel).
+ *   otherwise:                         T rounded up to 128, the row tile of the 128x128 kernel.
+ * Where N % 256 == 0 the rule returns a multiple of 256 exactly when the token-row map is off: that is how mhmr_vit_forward tells the
+ * all-rows form from the row map, so a caller must not pad such a description to a multiple of 256 for any other reason.
+ * Every workspace of a mhmr_vit_desc must be ZERO-INITIALISED ONCE by the caller, `att` and `hid` in particular: under the token-row
+ * map (and for fc1 under MHMR_VIT_FORM_FC1MAP) the padding rows of `att` / `hid` (rows > N of an image) are never written -- attention
+ * skips workgroups whose queries are all padding, the class-row launches write row N alone -- while a linear that covers all rows (fc2
+ * under MHMR_VIT_FORM_FC1MAP) reads them, row-locally: NaN / Inf bit patterns there would be carried into the padding rows of the
+ * residual stream, whose keys the attention masks only as long as they are finite. */
+#define MHMR_PLAN_ROWMAP 0x001u          /* clear = MHMR_ROWMAP=0: no token-row map, no 256x256 all-rows form                     */
+#define MHMR_PLAN_GEMM128 0x002u         /* SET = MHMR_GEMM128: the 128x128 kernel everywhere (clear by default, as VITS_256 and LO8) */
+#define MHMR_PLAN_LNFOLD 0x004u          /* clear = MHMR_LNFOLD=0: no LayerNorm fold                                              */
+#define MHMR_PLAN_LO8 0x008u             /* fold-/lo8_eligible: "pack fp8 low-half rows" (a packer opts in); form_bits: "use them" */
+#define MHMR_PLAN_ANYORDER 0x010u        /* (any-order launches: not part of a plan; form_bits never has MHMR_VIT_FORM_AO)        */
+#define MHMR_PLAN_QKV_MERGE 0x020u       /* clear = MHMR_QKV_MERGE=0                                                              */
+#define MHMR_PLAN_FC1_ROWMAP 0x040u      /* clear = MHMR_FC1_ROWMAP=0                                                             */
+#define MHMR_PLAN_CLS_STATS 0x080u       /* clear = MHMR_CLS_STATS=0                                                              */
+#define MHMR_PLAN_TINY_ALLROWS 0x100u    /* clear = MHMR_TINY_ALLROWS=0: tiny batches of a folded pack keep the token-row map     */
+#define MHMR_PLAN_LNFOLD_ALLROWS 0x200u  /* clear = MHMR_LNFOLD_ALLROWS=0: no fold where it needs the all-rows padding            */
+#define MHMR_PLAN_VITS_256 0x400u        /* SET = MHMR_VITS_256=1: C = 384 with folded LayerNorms on the 256x256 kernel (cpad)    */
+#define MHMR_PLAN_DEFAULT 0x3f5u         /* an empty environment (MHMR_PLAN_LO8 clear: nobody packed fp8 rows)                    */
+typedef struct {
+    int C, H, N, B;         /* embed dim (= 64 H), heads, patch tokens per image, images (0: only the two *_eligible answers are valid) */
+    int fold, x3, lo8, cpad;/* the pack's choices: blocks carry folded LayerNorms; f16x3; fp8 low-half rows; mhmr_vit_desc.cpad   */
+    unsigned switches;      /* MHMR_PLAN_*: the entry reads no environment                                                        */
+    int ncu;                /* compute units the launches are planned for; 0 = those of the current device (no device: nothing
+                               that depends on them is planned -- no split-k workspace, no v16; Tp, row_map, pitch do not)       */
+} mhmr_vit_plan_request;
+typedef struct {
+    int Tp;                 /* rows per image                                                                                     */
+    int row_map;            /* the token-row map: block GEMMs over the B * N patch rows                                           */
+    int tiny_batch;         /* the batch is "tiny" in the sense of the rule above (whether or not that changed the layout)          */
+    int pitch;              /* row pitch of xn / att in elements (C; 3C/2 with lo8; 2C with x3)                                   */
+    int need_pstats;        /* allocate pstats and rowstats                                                                       */
+    int need_cls_pstats;    /* allocate cls_pstats                                                                                */
+    int need_v16;           /* allocate v16                                                                                       */
+    long long splitk_bytes; /* allocate splitk of this many bytes (0: none)                                                       */
+    int attn_flags;         /* mhmr_attention_flag_count(B, Tp, H) (0 with x3)                                                    */
+    int fold_eligible;      /* pack time: fold LayerNorms into the linears of a (C, N) encoder                                    */
+    int lo8_eligible;       /* pack time: add fp8 low-half rows                                                                   */
+    unsigned form_bits;     /* MHMR_VIT_FORM_* (never _AO) of a description that offers exactly these workspaces                  */
+} mhmr_vit_plan_result;
+/* MHMR_ERR_BAD_ARG: NULL, B < 0, C <= 0, C != 64 H, N <= 0 or ncu < 0; MHMR_ERR_BAD_SHAPE: lo8 with C % 256 != 0. */
+int mhmr_vit_plan(const mhmr_vit_plan_request* rq, mhmr_vit_plan_result* out);
 
 /* Building blocks, exported for unit tests and bisecting. */
 int mhmr_gemm16(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
 SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
-HEADERS = ["mhmr_common.h", "mhmr_internal.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", os.path.join("..", "..", "include", "mhmr.h")]
+HEADERS = ["mhmr_common.h", "mhmr_internal.h", "vit_plan.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
 DT_BF16, DT_F16 = 0, 1
@@ -23,6 +23,11 @@ ATTN_QSCALE = 0.18033688011112042   # include/mhmr.h MHMR_ATTN_QSCALE
 
 #: include/mhmr.h MHMR_VIT_FORM_*: the bits of mhmr_vit_form_bits, in bit order
 VIT_FORM_BITS = ("rowmap", "allrows256", "nmask", "fold", "lo8_ranges", "cst", "ao", "splitk", "qkv_merge", "fc1map", "x3")
+
+#: include/mhmr.h MHMR_PLAN_*: the switches of mhmr_vit_plan_request, in bit order; PLAN_DEFAULT = an empty environment
+PLAN_SWITCHES = ("rowmap", "gemm128", "lnfold", "lo8", "anyorder", "qkv_merge", "fc1_rowmap", "cls_stats", "tiny_allrows", "lnfold_allrows", "vits_256")
+PLAN = {n: 1 << i for i, n in enumerate(PLAN_SWITCHES)}
+PLAN_DEFAULT = 0x3f5
 
 _vp, _fp, _ip, _i, _f = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float  # all device pointers are void*
 _f32p = C.POINTER(C.c_float)        # a typed float*: the nullable outputs appended to a descriptor (set with f32p(tensor); NULL by default)
@@ -128,6 +133,15 @@ class VitDesc(C.Structure):
                 [(n, _vp) for n in ("a_patch", "resid", "xn", "qk", "vt", "att", "hid", "attn_flags", "pstats", "rowstats")] +
                 [("lo8", _i), ("x3", _i), ("qkv32", _vp), ("hid32", _vp), ("splitk", _vp), ("splitk_bytes", C.c_longlong), ("cpad", _i), ("v16", _vp), ("cls_pstats", _vp),
                  ("tap", _vp), ("tap_first", _i)])
+
+
+class VitPlanRequest(C.Structure):
+    _fields_ = [(n, _i) for n in ("C", "H", "N", "B", "fold", "x3", "lo8", "cpad")] + [("switches", C.c_uint), ("ncu", _i)]
+
+
+class VitPlan(C.Structure):
+    _fields_ = ([(n, _i) for n in ("Tp", "row_map", "tiny_batch", "pitch", "need_pstats", "need_cls_pstats", "need_v16")] + [("splitk_bytes", C.c_longlong)] +
+                [(n, _i) for n in ("attn_flags", "fold_eligible", "lo8_eligible")] + [("form_bits", C.c_uint)])
 
 
 class HphLayer(C.Structure):
@@ -364,6 +378,7 @@ _SIGS = {
     "mhmr_source_hash": ([], C.c_char_p),
     "mhmr_vit_forward": ([C.POINTER(VitDesc), _vp, _vp, _vp, _i, _vp], _i),
     "mhmr_vit_form_bits": ([C.POINTER(VitDesc), _vp, C.POINTER(C.c_uint)], _i),
+    "mhmr_vit_plan": ([C.POINTER(VitPlanRequest), C.POINTER(VitPlan)], _i),
     "mhmr_gemm16": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mhmr_gemm16_ex": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mhmr_gemm16_ln": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),

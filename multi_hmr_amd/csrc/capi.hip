@@ -5,6 +5,7 @@
 #include "mhmr_common.h"
 #include <stdlib.h>
 #include "mhmr_internal.h"
+#include "vit_plan.h"
 
 thread_local int g_mhmr_anyorder = 0;        // mhmr_internal.h: the next launches of this host thread go out without the AQL barrier bit
 #ifndef MHMR_ANYORDER_DEFAULT
@@ -303,24 +304,13 @@ static int vit_forward_x3(const mhmr_vit_desc* d, const float* x, float* feat32,
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ mhmr_vit_forward: decide, then launch
-// vit_switches (the environment) -> vit_form (everything decided before the block loop) -> per block: vit_block_ops (which weights,
-// which low halves, which launches merge) -> vit_launch (the launches, in stream order).
+// vit_switches (the environment) -> vit_form (vit_plan.h: everything decided before the block loop) -> per block: vit_block_ops (which
+// weights, which low halves, which launches merge) -> vit_launch (the launches, in stream order).
 namespace {
-
-// The environment switches of the forward: A/B measurements and bisecting; everything is on by default.
-struct VitSwitches {
-    bool rowmap;        // MHMR_ROWMAP=0: no token-row map and no 256x256 all-rows form: one GEMM over all B * Tp rows
-    bool gemm128;       // MHMR_GEMM128 set (gemm.hip forces the 128x128 kernel everywhere): the same
-    bool lnfold;        // MHMR_LNFOLD=0: LayerNorm as launches of its own
-    bool lo8;           // MHMR_LO8=0: the fp8 low-half ranges of a lo8 pack are not used
-    bool anyorder;      // MHMR_ANYORDER=0 / 1 (default MHMR_ANYORDER_DEFAULT)
-    bool qkv_merge;     // MHMR_QKV_MERGE=0: Q | K and V as two launches in a short batch too
-    bool fc1_rowmap;    // MHMR_FC1_ROWMAP=0: fc1 of a short batch over all rows
-    bool cls_stats;     // MHMR_CLS_STATS=0: row statistics as ln_stats launches
-};
 
 inline bool env_not_zero(const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); }
 
+// (the three layout switches of VitSwitches are the caller's: the forward finds their outcome in the description)
 VitSwitches vit_switches() {
     static const VitSwitches once = [] {
         VitSwitches w{};
@@ -344,84 +334,6 @@ bool stream_takes_anyorder(hipStream_t s) {
     if (g_prof.kind >= 0) return false;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     return hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
-}
-
-// The form of one forward: everything that is decided before the block loop.
-struct VitForm {
-    int rc = 0;              // MHMR_ERR_*: this description cannot run
-    // Token rows of an image: patches 0..N-1, the class token at row N, zero padding up to Tp (vit_misc.hip).  When the patch rows of
-    // an image are whole 256-row tiles and every linear runs on the 256x256 kernel, the five big GEMMs of a block cover the B * N
-    // patch rows only (GemmArgs::img_rows: exact tile rounds) and the B class rows go through the skinny kernel (vit_cls.hip);
-    // otherwise one GEMM covers all B * Tp rows.
-    bool rowmap = false;
-    int Mg = 0, img_rows = 0, img_stride = 0;      // rows of a block GEMM; its token-row map (0, 0: rows are physical)
-    long long cls_row = 0;   // the class row inside an image
-    int vcol = 0;            // its (key-permuted) V^T column
-    // ... or, without the row map (N not a multiple of 256: 1288^2, 518^2), every block linear on the 256x256 kernel over ALL B * Tp rows
-    // (Tp a multiple of 256: vit.padded_tokens): the class and padding rows are rows like any other, with block sums of their own
-    bool allrows256 = false;
-    // (C = 384, ViT-S: the three linears whose output is C wide -- V, proj, fc2 -- run as N = Cp = 512 with the last 128 columns masked,
-    // GemmArgs::n_valid; the caller says with mhmr_vit_desc.cpad that their weights and per-column vectors are zero-padded for it)
-    bool nmask = false;
-    int Cp = 0;
-    // LayerNorm fold (GemmArgs in mhmr_internal.h): needs every block linear on the 256x256 kernel and the two workspaces
-    bool fold = false;
-    // fp8 low-half ranges (mhmr_vit_desc.lo8): the rows of `xn` and `att` are 3C/2 elements wide (the bf8 copy of a row behind its C values)
-    bool lo8 = false;
-    bool lo8_ranges = false; // ... and a block's v_w8 / proj_w8 run as such a range (needs the 256x256 kernel for that launch)
-    int pit = 0;             // row pitch of xn / att in elements
-    int o8 = 0;              // byte offset of the bf8 copy inside such a row
-    // Row statistics inside the class-row launches (vit_cls.hip, round 6): with mhmr_vit_desc.cls_pstats the residual class-row launch of
-    // proj / fc2 also carries the patch rows' statistics (extra workgroups) and leaves block sums of the class rows, from which the class-row
-    // consumers take (mean, rstd) themselves: no ln_stats launch at all under the token-row map.
-    bool cst = false;
-    // Any-order launches (mhmr_internal.h): the V projection and the class-row linears are independent of the big GEMM launched right in
-    // front of them and nothing reads their outputs before the next ordinary launch
-    bool ao = false;
-    // Split-k residual linears (a batch of one: all rows through the 256x256 kernel, 68 / 40 tiles on 256 CUs): the k range is cut so that
-    // tiles x slices fill the chip, and the reduction that follows (vit_misc.hip splitk_resid_kernel) runs the residual epilogue AND leaves
-    // the row statistics, so the ln_stats launch behind such a linear disappears.  Needs the workspace mhmr_vit_desc.splitk.
-    bool splitk = false;
-    // A short batch (all rows, the whole qkv linear at most one round of tiles): ONE launch for Q | K | V + a transpose of the V rows
-    // (gemm256.hip QKV), instead of two launches of half a round each.  Needs mhmr_vit_desc.v16 (and, per block, a V without a low half).
-    bool qkv_merge = false;
-    // One 896^2 image over all rows is 17 row tiles x 16 column tiles = 272 tiles: one round of the chip + 16 tiles that cost a second.
-    // When the PATCH rows alone fit one round (16 x 16 = 256), fc1 -- and only fc1, and only with its LayerNorm folded -- takes the
-    // token-row map and its class rows the skinny kernel; the padding rows of `hid` are then never written (they stay as allocated:
-    // zero) and nobody reads what the padding rows of the residual stream become.
-    bool fc1map = false;
-    // mhmr_vit_desc.x3: the f16x3 forward (vit_forward_x3) runs, and nothing above applies
-    bool x3 = false;
-};
-
-VitForm vit_form(const mhmr_vit_desc* d, const VitSwitches& w, int ncu, bool anyorder_stream) {
-    VitForm f;
-    const int B = d->B, C = d->C, N = d->N, Tp = d->Tp, M = B * Tp;
-    const bool k256 = w.rowmap && !w.gemm128;
-    const bool fits = (uint64_t)M * (uint64_t)C * 4u < (1ull << 32);
-    // (Tp a multiple of 256 where N is one too -- the row map's own padding is N + 64 -- is the caller saying "all rows": multi_hmr_amd/vit.py
-    // (row_map, padded_tokens) pads tiny batches that way, whose launches are latency-bound and not worth six class-row launches per block)
-    f.rowmap = k256 && C % 256 == 0 && N % 256 == 0 && Tp % 256 != 0 && fits;
-    f.Mg = f.rowmap ? B * N : M;
-    f.img_rows = f.rowmap ? N : 0;
-    f.img_stride = f.rowmap ? Tp : 0;
-    f.cls_row = (long long)N;
-    f.vcol = (N & ~12) | ((N & 4) << 1) | ((N & 8) >> 1);
-    f.Cp = (C + 255) / 256 * 256;
-    f.allrows256 = !f.rowmap && k256 && (C % 256 == 0 || (C % 128 == 0 && d->cpad == f.Cp)) && M % 256 == 0 && fits;
-    f.nmask = f.allrows256 && C % 256 != 0;
-    f.fold = (f.rowmap || f.allrows256) && w.lnfold && d->pstats && d->rowstats;
-    f.lo8 = d->lo8 != 0 && C % 256 == 0;
-    if (d->lo8 && !f.lo8) { f.rc = MHMR_ERR_BAD_SHAPE; return f; }
-    f.lo8_ranges = f.lo8 && w.lo8 && (f.rowmap || f.allrows256);
-    f.pit = f.lo8 ? C + C / 2 : C;
-    f.o8 = 2 * C;
-    f.cst = w.cls_stats && f.rowmap && f.fold && !f.lo8 && d->cls_pstats && C % 128 == 0 && C <= 1024;
-    f.ao = w.anyorder && anyorder_stream;
-    f.splitk = f.allrows256 && f.fold && d->splitk;
-    f.qkv_merge = w.qkv_merge && f.allrows256 && !f.nmask && d->v16 && (M / 256) * (3 * C / 256) <= ncu;
-    f.fc1map = w.fc1_rowmap && f.allrows256 && !f.nmask && N % 256 == 0 && (M / 256) * (4 * C / 256) > ncu && (B * N / 256) * (4 * C / 256) <= ncu;
-    return f;
 }
 
 // A weight whose rows may carry the low halves behind the high ones ([W_hi | W_lo] along k, one accumulator chain): k = the whole k
@@ -652,7 +564,9 @@ int vit_form_of(const mhmr_vit_desc* d, hipStream_t s, VitForm* f) {
     if (d->tap && (d->tap_first < 0 || d->tap_first > d->L || !d->resid)) return MHMR_ERR_BAD_ARG;
     if (d->x3) { *f = VitForm{}; f->x3 = true; return 0; }      // vit_forward_x3: none of the choices below exists there
     const VitSwitches w = vit_switches();
-    *f = vit_form(d, w, mhmr_cu_count(), w.anyorder && stream_takes_anyorder(s));
+    const VitLayout lay{d->B, d->C, d->N, d->Tp, d->cpad, d->lo8, d->pstats && d->rowstats, d->cls_pstats != nullptr, d->splitk != nullptr,
+                        d->v16 != nullptr};
+    *f = vit_form(lay, w, mhmr_cu_count(), w.anyorder && stream_takes_anyorder(s));
     return f->rc;
 }
 
@@ -675,10 +589,39 @@ int mhmr_vit_form_bits(const mhmr_vit_desc* d, void* stream, unsigned* bits) {
     VitForm f;
     const int rc = vit_form_of(d, (hipStream_t)stream, &f);
     if (rc) return rc;
-    *bits = (f.rowmap ? MHMR_VIT_FORM_ROWMAP : 0u) | (f.allrows256 ? MHMR_VIT_FORM_ALLROWS256 : 0u) | (f.nmask ? MHMR_VIT_FORM_NMASK : 0u) |
-            (f.fold ? MHMR_VIT_FORM_FOLD : 0u) | (f.lo8_ranges ? MHMR_VIT_FORM_LO8_RANGES : 0u) | (f.cst ? MHMR_VIT_FORM_CST : 0u) |
-            (f.ao ? MHMR_VIT_FORM_AO : 0u) | (f.splitk ? MHMR_VIT_FORM_SPLITK : 0u) | (f.qkv_merge ? MHMR_VIT_FORM_QKV_MERGE : 0u) |
-            (f.fc1map ? MHMR_VIT_FORM_FC1MAP : 0u) | (f.x3 ? MHMR_VIT_FORM_X3 : 0u);
+    *bits = vit_form_bits(f);
+    return 0;
+}
+
+int mhmr_vit_plan(const mhmr_vit_plan_request* rq, mhmr_vit_plan_result* out) {
+    if (!rq || !out || rq->B < 0 || rq->C <= 0 || rq->C != 64 * rq->H || rq->N <= 0 || rq->ncu < 0) return MHMR_ERR_BAD_ARG;
+    const VitSwitches w = vit_switches_of_mask(rq->switches);
+    const VitPack p{rq->C, rq->N, rq->N + 1, rq->B, rq->fold != 0, rq->x3 != 0, rq->lo8 != 0, rq->cpad};
+    const int B = p.B, C = p.C, ncu = rq->ncu > 0 || B == 0 ? rq->ncu : mhmr_cu_count();
+    mhmr_vit_plan_result r{};
+    r.fold_eligible = vit_fold_eligible(C, p.N, w);
+    r.lo8_eligible = vit_lo8_eligible(C, w);
+    r.Tp = vit_rows_per_image(p, w);
+    r.row_map = vit_row_map(p, w);
+    r.tiny_batch = vit_tiny_batch(p);
+    r.pitch = vit_pitch(p);
+    r.need_pstats = vit_need_pstats(p);
+    r.need_cls_pstats = vit_need_cls_pstats(p, w);
+    if (vit_may_splitk(p, w))
+        for (int K = C; K <= 4 * C; K *= 2) {
+            int ks = 0, S = 0;
+            const long long M = (long long)B * r.Tp;
+            if (mhmr_splitk_plan_on(ncu, (int)M, C, K, &ks, &S) && S * M * C * 4 > r.splitk_bytes) r.splitk_bytes = S * M * C * 4;
+        }
+    r.need_v16 = r.splitk_bytes > 0;      // the merged qkv launch of a short batch leaves the V rows there
+    r.attn_flags = p.x3 ? 0 : mhmr_attention_flag_count_impl(B, r.Tp, rq->H);
+    // the form: vit_form itself, on a description that offers exactly these workspaces
+    VitForm f;
+    f.x3 = p.x3;
+    if (!p.x3) f = vit_form(VitLayout{B, C, p.N, r.Tp, p.cpad, p.lo8, r.need_pstats != 0, r.need_cls_pstats != 0, r.splitk_bytes > 0, r.need_v16 != 0}, w, ncu, false);
+    if (f.rc) return f.rc;
+    r.form_bits = vit_form_bits(f);
+    *out = r;
     return 0;
 }
 

@@ -293,11 +293,13 @@ static const bool g_force_gemm128 = getenv("MHMR_GEMM128") != nullptr;
 // Split-k for a SHORT launch (gemm256.hip SPLITK): when the tiles of an [M, N] output fill at most half of the chip, cut K into nslices
 // slices of ksplit k tiles (whole pairs; the last slice may be shorter) so that tiles x slices fill one round of CUs.  false = do not split.
 // MHMR_SPLITK=0 switches it off (A/B measurements).
-bool mhmr_splitk_plan(int M, int N, int K, int* ksplit, int* nslices) {
+bool mhmr_splitk_plan(int M, int N, int K, int* ksplit, int* nslices) { return mhmr_splitk_plan_on(mhmr_cu_count(), M, N, K, ksplit, nslices); }
+
+// ... on a device of ncu compute units (mhmr_vit_plan: a caller may plan for a device it does not have)
+bool mhmr_splitk_plan_on(int ncu, int M, int N, int K, int* ksplit, int* nslices) {
     static const bool on = !(getenv("MHMR_SPLITK") && atoi(getenv("MHMR_SPLITK")) == 0);
     if (!on || g_force_gemm128 || M <= 0 || M % 256 || N % 256 || K % 128) return false;
     if (N > 1024) return false;                 // widths the reduction has a kernel for (vit_misc.hip: mhmr_launch_splitk_resid, C = 256 .. 1024)
-    const int ncu = mhmr_cu_count();
     const int tiles = (M / 256) * (N / 256), nt = K / 64;
     if (ncu <= 0 || tiles <= 0) return false;
     int S = ncu / tiles;

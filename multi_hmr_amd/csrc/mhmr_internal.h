@@ -165,6 +165,7 @@ void prof_end(int kind, hipStream_t s, double work);
 int mhmr_launch_gemm(const GemmArgs& g, int dtype, hipStream_t s);
 int mhmr_cu_count();      // multiProcessorCount of the CURRENT device (cached per device id)
 bool mhmr_splitk_plan(int M, int N, int K, int* ksplit, int* nslices);
+bool mhmr_splitk_plan_on(int ncu, int M, int N, int K, int* ksplit, int* nslices);
 
 // ---- gemm256.hip
 bool mhmr_gemm256_eligible(const GemmArgs& g);

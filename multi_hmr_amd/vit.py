@@ -139,31 +139,59 @@ def lo8_rows(w_hi16: torch.Tensor, w32: torch.Tensor):
     return rows, 127 + e, q.double() * 2.0 ** e
 
 
-def lo8_eligible(C: int) -> bool:
-    """fp8 low-half ranges need the 256x256 kernel's 128-deep fp8 k tiles in whole pairs: embed_dim a multiple of 256 (ViT-B / ViT-L).
-    OFF unless MHMR_LO8=1: built, parity-green (tests/test_gpu_kernels.py::test_gemm_fp8_low_half_range, the full-size goldens) and
-    measured SLOWER than the 16-bit low halves on this power-clocked chip -- 135.8 vs 133.6 ms per headline step, interleaved on one box
-    (profiles/r05_session_d_fp8_low_half_ab.txt, r05_session_e_lo8_kernel_trace.txt): the fp8 k tiles, nominally twice the rate, took
-    as long as the 16-bit tiles they replaced (V 425 vs ~443 us, proj 569 vs ~513 us), and the 3C/2 row pitch the bf8 copies need cost
-    every other consumer of those rows (fc1 +28 us, QK +17 us, attention +28 us per launch)."""
+# ---- the layout rule: rows per image, optional workspaces, the two pack-time predicates.  It lives in the library (csrc/vit_plan.h,
+# include/mhmr.h mhmr_vit_plan), beside the function that picks the forward's launch sequence from the layout; this file asks.
+def switches() -> int:
+    """The MHMR_PLAN_* mask of the environment, read per call (tests and A/B runs flip the switches inside one process).  The four
+    switches that only pick launches (MHMR_ANYORDER, _QKV_MERGE, _FC1_ROWMAP, _CLS_STATS) the library reads itself: on here.
+    MHMR_LO8 has two meanings and both stay: here it is "pack the fp8 low-half rows", opt-in (=1) -- built, parity-green and measured
+    SLOWER than the 16-bit low halves (135.8 vs 133.6 ms per headline step, profiles/r05_session_d_fp8_low_half_ab.txt) --; in the
+    library's own environment read it is "use the rows a pack has", on unless =0.  MHMR_VITS_256=1 is opt-in for the same reason
+    (2523-2763 against 2755-2768 img/s at 16 images of 672^2, profiles/r06_session_b.txt)."""
     import os
-    return C % 256 == 0 and os.environ.get("MHMR_LO8", "0") == "1" and "MHMR_GEMM128" not in os.environ
+    env, bit = os.environ, _lib.PLAN
+    m = bit["anyorder"] | bit["qkv_merge"] | bit["fc1_rowmap"] | bit["cls_stats"]
+    for name in ("rowmap", "lnfold", "tiny_allrows", "lnfold_allrows"):
+        m |= bit[name] if env.get("MHMR_" + name.upper(), "1") != "0" else 0
+    m |= bit["gemm128"] if "MHMR_GEMM128" in env else 0
+    m |= bit["lo8"] if env.get("MHMR_LO8", "0") == "1" else 0
+    m |= bit["vits_256"] if env.get("MHMR_VITS_256", "0") == "1" else 0
+    return m
+
+
+def plan(P: dict, B: int, ncu: int = 0, sw: int | None = None):
+    """``mhmr_vit_plan`` for a pack (or a bare ``{"C": .., "T": ..}``) and a batch -> ``_lib.VitPlan``.  ncu = 0: the current device's
+    compute units; sw: a switch mask instead of the environment's."""
+    rq = _lib.VitPlanRequest(C=P["C"], H=P.get("H", P["C"] // 64), N=P["T"] - 1, B=B, fold=bool(P.get("fold")), x3=bool(P.get("x3")),
+                             lo8=bool(P.get("lo8")), cpad=P.get("cpad") or 0, switches=switches() if sw is None else sw, ncu=ncu)
+    out = _lib.VitPlan()
+    _lib.check(_lib.lib().mhmr_vit_plan(C.byref(rq), C.byref(out)), "mhmr_vit_plan")
+    return out
+
+
+def lo8_eligible(C: int) -> bool:
+    """Pack fp8 low-half rows (ViT-B / ViT-L, MHMR_LO8=1)."""
+    return bool(plan({"C": C, "T": 257}, 0).lo8_eligible)
 
 
 def fold_eligible(C: int, N: int) -> bool:
-    """The LayerNorm fold (csrc/gemm256.hip, GemmArgs::pstats / rowstats) needs every block linear on the 256x256 kernel: embed_dim a
-    multiple of 256 (ViT-B / ViT-L), and either the token-row map (N a multiple of 256) or, for any other N (1288^2: 8464), the rows
-    of an image padded to a multiple of 256 so that the GEMMs cover whole tiles of ALL rows (padded_tokens).  MHMR_LNFOLD=0 /
-    MHMR_ROWMAP=0 switch it off (A/B measurements)."""
-    import os
-    wide = C % 256 == 0
-    # ViT-S (C = 384, round 6): its C-wide linears run as N = 512 with masked columns (mhmr_vit_desc.cpad), always over all rows
-    # OFF unless MHMR_VITS_256=1: built, parity-green and measured SLOWER at BASELINE's config 2 (16 images, two blocks of 8: 2523-2763 against
-    # 2755-2768 img/s on the 128x128 kernel, one box, interleaved: profiles/r06_session_b.txt): 80 row tiles x 2 column tiles = 160 tiles of
-    # 256x256 are 0.6 rounds of the chip, a quarter of them masked, and K = 384 is six k tiles -- the tile is too coarse for this batch
-    narrow = C % 128 == 0 and os.environ.get("MHMR_VITS_256", "0") == "1" and os.environ.get("MHMR_LNFOLD_ALLROWS", "1") != "0"
-    return (os.environ.get("MHMR_LNFOLD", "1") != "0" and os.environ.get("MHMR_ROWMAP", "1") != "0" and "MHMR_GEMM128" not in os.environ and
-            ((wide and (N % 256 == 0 or os.environ.get("MHMR_LNFOLD_ALLROWS", "1") != "0")) or (not wide and narrow)))
+    """Fold the LayerNorms of a (C, N) encoder into its linears."""
+    return bool(plan({"C": C, "T": N + 1}, 0).fold_eligible)
+
+
+def tiny_batch(P: dict, B: int) -> bool:
+    """The narrowest block linear of the whole batch is at most half a round of 256x256 tiles."""
+    return bool(plan(P, B).tiny_batch)
+
+
+def row_map(P: dict, B: int) -> bool:
+    """The block GEMMs cover the B * N patch rows only; the class rows go through csrc/vit_cls.hip."""
+    return bool(plan(P, B).row_map)
+
+
+def padded_tokens(P: dict, B: int) -> int:
+    """Rows per image in the token-major workspaces (patch tokens, the class token, zero padding)."""
+    return plan(P, B).Tp
 
 
 def pack_encoder(enc, img_size: int, precision: str, device, wlo: str | None = None, lnfold: bool | None = None) -> dict:
@@ -329,42 +357,6 @@ def pack_block(P: dict, b, i: int):
     return t, sc
 
 
-def tiny_batch(P: dict, B: int) -> bool:
-    """The narrowest block linear (N = embed_dim) of the whole batch is at most HALF a round of 256x256 tiles on the chip (896^2: one
-    image; 672^2: up to three).  Such a launch is latency, not throughput: exact tile rounds buy nothing, while the class-row kernels the
-    token-row map needs are six more launches per block (~25 % of a batch-1 forward together with the row statistics)."""
-    return P["C"] % 256 == 0 and (B * roundup(P["T"], 256) // 256) * (P["C"] // 256) <= 128
-
-
-def row_map(P: dict, B: int) -> bool:
-    """Mirror of the rule in csrc/capi.hip (mhmr_vit_forward): the five big GEMMs of a block run over the B * N patch rows only (the
-    class rows through csrc/vit_cls.hip) when an image's patch rows are whole 256-row tiles of the 256x256 kernel -- except for tiny
-    batches with folded LayerNorms, which run ALL rows (class and padding rows included, Tp a multiple of 256: that is how capi.hip tells)
-    through the big GEMMs and launch no class-row kernel at all."""
-    import os
-    T = P["T"]
-    return (not P.get("x3") and os.environ.get("MHMR_ROWMAP", "1") != "0" and "MHMR_GEMM128" not in os.environ and P["C"] % 256 == 0 and (T - 1) % 256 == 0 and
-            B * roundup(T, 64) * P["C"] * 4 < 2 ** 32 and not (P.get("fold") and tiny_batch(P, B) and os.environ.get("MHMR_TINY_ALLROWS", "1") != "0"))
-
-
-def padded_tokens(P: dict, B: int) -> int:
-    """Rows per image in the token-major workspaces (patch tokens, the class token, zero padding).  A multiple of 64 (the attention key
-    tile, the V^T row granularity) when every linear of the encoder stays on the 256x256 kernel -- the GEMMs cover the patch rows only
-    (row_map), or embed_dim and B * Tp are multiples of 256; otherwise a multiple of 128, the row tile of the 128x128 kernel.
-    896^2: 4160 instead of 4224 rows per image."""
-    import os
-    if P.get("x3"):
-        return roundup(P["T"], 256 if P["C"] % 256 == 0 else 128)      # all rows through every linear: whole tiles for every batch size
-    if P.get("fold") and (P.get("cpad") or (P["T"] - 1) % 256 or (not row_map(P, B) and tiny_batch(P, B) and os.environ.get("MHMR_ROWMAP", "1") != "0" and
-                                                                  "MHMR_GEMM128" not in os.environ)):
-        return roundup(P["T"], 256)        # folded LayerNorms without the row map: whole 256-row tiles of all rows, for every batch size
-    t64, t128 = roundup(P["T"], 64), roundup(P["T"], 128)
-    # the predicate of csrc/gemm256.hip mhmr_gemm256_eligible for the residual GEMMs over all B * Tp rows (32-bit residual offsets),
-    # and the switch that forces the 128x128 kernel everywhere
-    all_rows_256 = (P["C"] % 256 == 0 and (B * t64) % 256 == 0 and B * t64 * P["C"] * 4 < 2 ** 32 and "MHMR_GEMM128" not in os.environ)
-    return t64 if (row_map(P, B) and "MHMR_GEMM128" not in os.environ) or all_rows_256 else t128
-
-
 class WorkspaceCache:
     """The workspaces of the TWO most recent (pack, batch size) pairs: a run whose last batch of an epoch is smaller alternates between
     two batch sizes without re-allocating (and zero-filling) a multi-GB workspace at every switch, while a model does not pin one per
@@ -390,15 +382,16 @@ class WorkspaceCache:
         the extras cover the whole batch.  The top-level buffer names (``hid`` ...) are those of part 0."""
         if B % nsplit:
             raise ValueError(f"batch {B} does not split into {nsplit} equal image blocks")
-        key = (id(P), B, nsplit, padded_tokens(P, B // nsplit), tap)  # (the row padding follows environment switches: A/B runs in one process)
+        Bh = B // nsplit
+        pl = plan(P, Bh)                                   # (the layout follows environment switches: A/B runs in one process)
+        key = (id(P), B, nsplit, pl.Tp, tap)
         if key in self._ws:
             self._ws[key] = self._ws.pop(key)             # most recent last
             return self._ws[key]
         while len(self._ws) >= self.KEEP:                 # free the oldest before allocating
             self._ws.pop(next(iter(self._ws)))
         dev, tdt = P["device"], P["tdt"]
-        Bh = B // nsplit
-        Cd, N, Tp, H = P["C"], P["N"], padded_tokens(P, Bh), P["H"]
+        Cd, N, Tp, pit = P["C"], P["N"], pl.Tp, pl.pitch
         z = lambda *s, dtype=tdt: torch.zeros(*s, dtype=dtype, device=dev)
         if P.get("fold") and Bh * Tp * Cd * 4 >= 2 ** 32:
             raise _lib.MhmrError(f"batch {Bh} is too large for this pack's folded LayerNorms (32-bit residual offsets of the 256x256 kernel); "
@@ -409,26 +402,22 @@ class WorkspaceCache:
         for i in range(nsplit):
             Mp = roundup(Bh * N, 128)
             if x3:       # operand pairs [hi | lo] and the two fp32 intermediates (include/mhmr.h, mhmr_vit_desc.x3)
-                b = dict(a_patch=z(Mp, 2 * P["Kp"]), resid=z(Bh * Tp, Cd, dtype=torch.float32), xn=z(Bh * Tp, 2 * Cd), att=z(Bh * Tp, 2 * Cd),
+                b = dict(a_patch=z(Mp, 2 * P["Kp"]), resid=z(Bh * Tp, Cd, dtype=torch.float32), xn=z(Bh * Tp, pit), att=z(Bh * Tp, pit),
                          hid=z(Bh * Tp, 8 * Cd), qkv32=z(Bh * Tp, 3 * Cd, dtype=torch.float32), hid32=z(Bh * Tp, 4 * Cd, dtype=torch.float32))
             else:
-                pit = Cd + Cd // 2 if P.get("lo8") else Cd       # lo8: a row of xn / att carries its bf8 copy behind its C values
                 b = dict(a_patch=z(Mp, P["Kp"]), resid=z(Bh * Tp, Cd, dtype=torch.float32), xn=z(Bh * Tp, pit), qk=z(Bh * Tp, 2 * Cd),
-                         vt=z(Bh * H * 64, Tp), att=z(Bh * Tp, pit), hid=z(Bh * Tp, 4 * Cd),
-                         attn_flags=z(_lib.lib().mhmr_attention_flag_count(Bh, Tp, H), dtype=torch.int32))
-            if P.get("fold"):
+                         vt=z(Bh * P["H"] * 64, Tp), att=z(Bh * Tp, pit), hid=z(Bh * Tp, 4 * Cd), attn_flags=z(pl.attn_flags, dtype=torch.int32))
+            if pl.need_pstats:
                 b.update(pstats=z(Bh * Tp, Cd // 64, 2, dtype=torch.float32), rowstats=z(Bh * Tp, 2, dtype=torch.float32))
-            if P.get("fold") and not x3 and row_map(P, Bh):
+            if pl.need_cls_pstats:
                 b["cls_pstats"] = z(Bh, Cd // 16, 2, dtype=torch.float32)       # block sums of the class rows (csrc/vit_cls.hip)
-            # split-k residual linears (csrc/capi.hip): only the all-rows form of a tiny batch has launches short enough to be split
-            skb = 0
-            if P.get("fold") and not x3 and not P.get("lo8") and Tp % 256 == 0 and not row_map(P, Bh):
-                skb = max(_lib.lib().mhmr_splitk_workspace_bytes(Bh * Tp, Cd, kk) for kk in (Cd, 2 * Cd, 4 * Cd))
+            skb = pl.splitk_bytes        # split-k residual linears (csrc/capi.hip) of the all-rows form of a tiny batch
             if skb:
                 b["splitk"] = z(skb // 4, dtype=torch.float32)
+            if pl.need_v16:
                 b["v16"] = z(Bh * Tp, Cd)            # the merged qkv launch of a short batch (csrc/capi.hip) leaves the V rows here
             d = _lib.VitDesc()
-            d.dtype, d.B, d.S, d.C, d.H, d.L = P["dt_id"], Bh, P["S"], Cd, H, P["L"]
+            d.dtype, d.B, d.S, d.C, d.H, d.L = P["dt_id"], Bh, P["S"], Cd, P["H"], P["L"]
             d.G, d.N, d.T, d.Tp, d.Kp = P["G"], N, P["T"], Tp, P["Kp"]
             d.patch_w, d.patch_b, d.cls_pos0, d.pos = v["patch_w"], v["patch_b"], v["cls_pos0"], v["pos"]
             d.blocks = C.cast(v["blocks"], C.POINTER(_lib.VitBlock))
@@ -437,8 +426,7 @@ class WorkspaceCache:
                 setattr(d, n, b[n].data_ptr() if n in b else None)
             d.x3 = 1 if x3 else 0
             d.lo8 = 1 if (P.get("lo8") and not x3) else 0
-            d.pstats = b["pstats"].data_ptr() if P.get("fold") else None
-            d.rowstats = b["rowstats"].data_ptr() if P.get("fold") else None
+            d.pstats, d.rowstats = (b["pstats"].data_ptr(), b["rowstats"].data_ptr()) if pl.need_pstats else (None, None)
             d.splitk, d.splitk_bytes = (b["splitk"].data_ptr(), skb) if skb else (None, 0)
             d.cpad = P.get("cpad", 0) if not x3 else 0
             d.v16 = b["v16"].data_ptr() if "v16" in b else None

@@ -61,6 +61,9 @@ def check_form(out, P, B, name):
     """the form that ran is the form the case is about, and the form the Python side predicts"""
     vf.check_want(out["bits"], vf.CASES[name]["want"], name)
     assert out["bits"] - {"ao"} == vf.predict_bits(P, B, name, vf.cu_count()), (name, sorted(out["bits"]))
+    # ... and the form the library plans for this pack and batch, when the case runs the workspace as planned
+    if not vf.CASES[name].get("null") and not vf.CASES[name].get("tp_all_rows"):
+        assert out["bits"] - {"ao"} == vf.bit_names(vit.plan(P, B).form_bits), (name, sorted(out["bits"]))
 
 
 def same_rows(a, b, where):

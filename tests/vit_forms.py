@@ -1,7 +1,7 @@
 """The ViT forward, form by form: fp64 truth, a rounding model, the case table and the harness of tests/test_gpu_vit_forms.py,
 tests/test_vit_forms_host.py and tests/vit_forms_child.py.  Not a conftest and no fixtures: plain functions.
 
-``mhmr_vit_forward`` (csrc/capi.hip: vit_form -> vit_block_ops -> vit_launch) picks one of about ten launch sequences per call.  Every case
+``mhmr_vit_forward`` (csrc/vit_plan.h vit_form -> csrc/capi.hip vit_block_ops -> vit_launch) picks one of about ten launch sequences per call.  Every case
 below names one of them, says how it is selected (only through switches Python reads per call, ``pack_encoder`` arguments and NULLed
 optional workspace pointers -- never through the switches C++ reads once per process) and which bits ``mhmr_vit_form_bits`` must report.
 
@@ -87,7 +87,7 @@ def case_precision(name: str, precision: str = "f16") -> str:
 
 
 def fc1map_batch(ncu: int, Cd: int = 768, N: int = 256, Tp: int = 512) -> int:
-    """The smallest tiny batch for which csrc/capi.hip vit_form takes fc1 alone under the token-row map on a device of ncu CUs: all rows
+    """The smallest tiny batch for which csrc/vit_plan.h vit_form takes fc1 alone under the token-row map on a device of ncu CUs: all rows
     of fc1 are more 256x256 tiles than CUs, the patch rows alone are not."""
     for B in range(1, 129):
         if (B * Tp // 256) * (4 * Cd // 256) > ncu and (B * N // 256) * (4 * Cd // 256) <= ncu and (B * Tp // 256) * (Cd // 256) <= 128:
