@@ -21,7 +21,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_pre_image_o, mhmr_preprocess_u8_batch_oriented; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points; mhmr_vit_plan); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
+#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_pre_image_o, mhmr_preprocess_u8_batch_oriented; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points; mhmr_vit_plan; mhmr_render_maps_desc, mhmr_render_maps, mhmr_point_visibility_desc, mhmr_render_point_visibility, mhmr_render_amodal_workspace_bytes, mhmr_render_amodal); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
 #define MHMR_OK 0
 #define MHMR_ERR_BAD_ARG (-1)
@@ -1085,6 +1085,87 @@ int mhmr_render_meshes(const mhmr_render_desc* d, void* stream);
  * large-face list, plus the fp64 world normals when nviews > 1. */
 long long mhmr_render_views_workspace_bytes(const mhmr_render_desc* d, int nviews);
 int mhmr_render_views(const mhmr_render_desc* d, int nviews, const float* view_Rt, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Per-pixel maps and per-person statistics from the rasteriser's keys (csrc/render_maps.hip; multi_hmr_amd/maps.py
+ * is the Python surface, tests/maps_oracle.py the numpy restatement).  keys [B][NV][H][W] is key_out of
+ * mhmr_render_meshes (NV = 1) or mhmr_render_views of the same scene: (float_bits(Z) << 32) | (p F + f), ~0 where
+ * nothing is drawn.  P, F and image_index [P] are that call's; face_label [F] (uint8, each < L, L <= 255) is
+ * optional.  A pixel whose key is ~0, or names a person >= P, or a person p with image_index[p] != its image b, is
+ * background.  Every output is optional (NULL = skipped):
+ *   person [B][NV][H][W] int32   low32(key) / F                          background -1
+ *   face   [B][NV][H][W] int32   low32(key) % F                          background -1
+ *   depth  [B][NV][H][W] fp32    the key's high word, reinterpreted      background 0 (as pyrender's depth map)
+ *   label  [B][NV][H][W] uint8   face_label[face]                        background 255
+ * and per person p and view v of image image_index[p]:
+ *   visible_px [P][NV] int32     pixels of view (image_index[p], v) that p wins            0 when none
+ *   bbox [P][NV][4] int32        x0, y0, x1, y1 of those pixels, inclusive                 W, H, -1, -1 when none
+ *   zmin [P][NV] fp32            their smallest depth                                      +inf when none
+ *   label_px [P][NV][L] int32    their count per label (labels >= L are not counted)       0
+ * A person whose image_index is outside [0, B) wins no pixel in the renderer and has the empty statistics here.
+ * The statistics are initialised inside the call and reduced with integer add / min / max only (zmin through the
+ * unsigned bit pattern: Z >= znear > 0), pre-reduced per wave and per workgroup: the same bits on every call.
+ * label and label_px need face_label (MHMR_ERR_BAD_ARG), label_px needs L >= 1.  B NV <= 65535 and P F < 2^32 - 1 as
+ * in the renderer, L in [0, 255], P >= 0, F >= 1 when P > 0: MHMR_ERR_BAD_SHAPE otherwise.  P == 0 is legal (every
+ * pixel is background).  No workspace, no allocation, no synchronisation; the launches go to `stream`.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, NV, H, W;
+    int P, F;
+    const unsigned long long* keys;
+    const int* image_index;
+    const unsigned char* face_label;
+    int L;
+    int* person;
+    int* face;
+    float* depth;
+    unsigned char* label;
+    int* visible_px;
+    int* bbox;
+    float* zmin;
+    int* label_px;
+} mhmr_render_maps_desc;
+
+int mhmr_render_maps(const mhmr_render_maps_desc* d, void* stream);
+
+/* Visibility of 3D points against the keys: points [P][N][3] fp32, person p's point n at points[p * pstride + 3 n + axis]
+ * (pstride >= 3 N: the v3d and j3d blocks are read in place), out [P][NV][N] uint8:
+ *   0 occluded, 1 visible, 2 projects outside the image, 3 Z < znear or a non-finite coordinate.
+ * In fp64, every step rounded on its own: X = R x + t with the renderer's expression ((R0 x0 + R1 x1) + R2 x2) + t and
+ * view convention (K[b], view_Rt[b][v], b = image_index[p]; NULL = identity); a non-finite x or X, or Z < znear,
+ * gives 3; u = fx X / Z + cx, v = fy Y / Z + cy; the pixel is (r, c) = (floor(v), floor(u)), outside [0, H) x [0, W)
+ * gives 2; a pixel whose key is ~0 gives 1; otherwise 1 iff Z <= (double)fp32_depth_of_key + (double)tau, else 0.
+ * tau (metres, >= 0) is the caller's margin: a few centimetres for vertices, about a limb's radius for joints.  A
+ * person whose image_index is outside [0, B) gets 2 everywhere.  znear <= 0 or tau < 0 (or NaN): MHMR_ERR_BAD_ARG;
+ * shapes as above, P N < 2^31: MHMR_ERR_BAD_SHAPE.  P N == 0 launches nothing. */
+typedef struct {
+    int B, NV, H, W;
+    int P, N;
+    const float* points;
+    long long pstride;
+    const int* image_index;
+    const float* K;
+    const float* view_Rt;
+    const unsigned long long* keys;
+    float znear, tau;
+    unsigned char* out;
+} mhmr_point_visibility_desc;
+
+int mhmr_render_point_visibility(const mhmr_point_visibility_desc* d, void* stream);
+
+/* Amodal area: amodal_px [P][nviews] int32 = the number of pixels person p would win in view v of image
+ * image_index[p] if they were alone in it: by definition the count of drawn keys of a mhmr_render_views call that
+ * holds only that person, so face drop, cull (d->cull_back), coverage and the znear / zfar test of the fp32 depth are
+ * the renderer's (the same code, csrc/render_shared.h).  0 for a person whose image_index is outside [0, B).  Read
+ * from d: B, H, W, P, V, F, verts, vstride, faces, image_index, K, znear, zfar, cull_back, workspace,
+ * workspace_bytes; the image inputs and outputs, colours, normals and shading fields are not read; d->Rt must be
+ * NULL (MHMR_ERR_BAD_ARG), view_Rt [B][nviews][3][4] or NULL as in mhmr_render_views.  Persons are taken in passes of
+ * as many as the workspace holds (a coverage bit per pixel and view, a list of the faces with a large pixel box):
+ * mhmr_render_amodal_workspace_bytes(d, nviews, n) is what passes of n persons need, linear in n and independent of
+ * P; a workspace smaller than the answer for n = 1 is MHMR_ERR_BAD_SHAPE.  The result does not depend on the pass
+ * size.  P == 0 launches nothing. */
+long long mhmr_render_amodal_workspace_bytes(const mhmr_render_desc* d, int nviews, int persons_per_pass);
+int mhmr_render_amodal(const mhmr_render_desc* d, int nviews, const float* view_Rt, int* amodal_px, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Scene packing for the 3D export (reference utils/render.py:62-173 create_scene, demo.py:371-384): P meshes

@@ -12,8 +12,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "scene.hip", "loss.hip", "capi.hip"]
-HEADERS = ["mhmr_common.h", "mhmr_internal.h", "vit_plan.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", os.path.join("..", "..", "include", "mhmr.h")]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "render_maps.hip", "scene.hip", "loss.hip", "capi.hip"]
+HEADERS = ["mhmr_common.h", "mhmr_internal.h", "vit_plan.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", "render_shared.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
 DT_BF16, DT_F16 = 0, 1
@@ -48,14 +48,15 @@ class MhmrError(RuntimeError):
 #: internal launchers and template helpers.
 COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: per-translation-unit extra flags.  render.hip: every step rounded on its own (the render contract's fp64 geometry and fp32 blend
-#: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  scene.hip: the same fp64 geometry.
+#: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  render_maps.hip: the same geometry
+#: (csrc/render_shared.h), which must agree with render.hip's bit for bit.  scene.hip: the same fp64 geometry.
 #: loss.hip: every element of the training loss is the reference's fp32 subtraction(s), rounded one by one (its sign is the gradient).
 #: optim.hip: the Adam update is torch's sequence of fp32 operations, each rounded on its own.
 #: attention_bf16.hip: the logit S = fl(QSCALE * acc) is rounded before exp2(S - lse) in all three kernels, as the contract states it.
 #: encoder_pack.hip: the LayerNorm fold is one fp32 multiply and the low half one fp32 subtraction, as vit.pack_block rounds them.
 #: fit.hip: its update kernel runs optim.hip's Adam element (csrc/adam_element.h) and must round it the same way.
 #: track.hip: the association cost and the One-Euro recursion are rounded operation by operation (the tests restate them in numpy).
-EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
+EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "render_maps.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
                "optim.hip": ["-ffp-contract=off"], "encoder_pack.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"],
                "track.hip": ["-ffp-contract=off"]}
 
@@ -194,6 +195,18 @@ class RenderDesc(C.Structure):
                 [(n, _f) for n in ("alpha", "intensity", "ambient", "metallic", "roughness", "znear", "zfar")] +
                 [("smooth", _i), ("cull_back", _i), ("img_in", _vp), ("img_out", _vp), ("workspace", _vp),
                  ("workspace_bytes", C.c_longlong), ("key_out", _vp), ("rgb_out", _vp)])
+
+
+class RenderMapsDesc(C.Structure):
+    """include/mhmr.h mhmr_render_maps_desc."""
+    _fields_ = ([(n, _i) for n in ("B", "NV", "H", "W", "P", "F")] + [("keys", _vp), ("image_index", _vp), ("face_label", _vp), ("L", _i)] +
+                [(n, _vp) for n in ("person", "face", "depth", "label", "visible_px", "bbox", "zmin", "label_px")])
+
+
+class PointVisibilityDesc(C.Structure):
+    """include/mhmr.h mhmr_point_visibility_desc."""
+    _fields_ = ([(n, _i) for n in ("B", "NV", "H", "W", "P", "N")] + [("points", _vp), ("pstride", C.c_longlong)] +
+                [(n, _vp) for n in ("image_index", "K", "view_Rt", "keys")] + [("znear", _f), ("tau", _f), ("out", _vp)])
 
 
 class SceneDesc(C.Structure):
@@ -456,6 +469,10 @@ _SIGS = {
     "mhmr_render_meshes": ([C.POINTER(RenderDesc), _vp], _i),
     "mhmr_render_views_workspace_bytes": ([C.POINTER(RenderDesc), _i], C.c_longlong),
     "mhmr_render_views": ([C.POINTER(RenderDesc), _i, _vp, _vp], _i),
+    "mhmr_render_maps": ([C.POINTER(RenderMapsDesc), _vp], _i),
+    "mhmr_render_point_visibility": ([C.POINTER(PointVisibilityDesc), _vp], _i),
+    "mhmr_render_amodal_workspace_bytes": ([C.POINTER(RenderDesc), _i, _i], C.c_longlong),
+    "mhmr_render_amodal": ([C.POINTER(RenderDesc), _i, _vp, _vp, _vp], _i),
     "mhmr_scene_pack": ([C.POINTER(SceneDesc), _vp], _i),
     "mhmr_loss_workspace_bytes": ([], C.c_longlong),
     "mhmr_loss_forward": ([C.POINTER(LossDesc), _vp, C.c_longlong, _vp, _vp], _i),

@@ -4,6 +4,7 @@ the repository root: test and benchmark infrastructure)."""
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -46,6 +47,36 @@ _LMK = [f"face_landmark_{i}" for i in range(51)]
 #: first 127 entries of smplx.joint_names.JOINT_NAMES (reference utils/humans.py:25-26)
 SMPLX_JOINT_NAMES = _BODY + _HANDS + _EXTRA + _LMK
 assert len(SMPLX_JOINT_NAMES) == 127 and SMPLX_JOINT_NAMES[15] == "head" and SMPLX_JOINT_NAMES[55] == "nose"
+
+
+class BodyParts(NamedTuple):
+    """Part names and, per skeleton joint, the index of the part its skinned surface belongs to."""
+    names: tuple
+    joint_part: tuple
+
+
+def _smplx_body_parts() -> BodyParts:
+    sides = ("upper_leg", "lower_leg", "foot", "upper_arm", "lower_arm", "hand")
+    names = ("torso", "head") + tuple(f"{s}_{n}" for n in sides for s in ("left", "right"))
+    limb = {"hip": "upper_leg", "knee": "lower_leg", "ankle": "foot", "foot": "foot", "collar": None, "shoulder": "upper_arm",
+            "elbow": "lower_arm", "wrist": "hand"}
+    table = []
+    for j in SMPLX_JOINT_NAMES[:SMPLX_NUM_JOINTS]:
+        side, _, rest = j.partition("_")
+        if side not in ("left", "right"):
+            part = "head" if j in ("neck", "head", "jaw") else "torso"      # pelvis, spine1-3
+        elif rest == "eye_smplhf":
+            part = "head"
+        elif rest in limb:
+            part = f"{side}_{limb[rest]}" if limb[rest] else "torso"        # the collars move the upper torso
+        else:
+            part = f"{side}_hand"                                           # the fifteen finger joints of each hand
+        table.append(names.index(part))
+    return BodyParts(names, tuple(table))
+
+
+#: the fourteen body parts of the part segmentation (multi_hmr_amd/maps.py) and the part of each of the 55 SMPL-X skeleton joints
+SMPLX_BODY_PARTS = _smplx_body_parts()
 
 # ----------------------------------------------------------------------------------------------
 # SMPL topology (ground truth of 3DPW, train.py:42-43, 76-94) and the H36M joint subset of its metrics

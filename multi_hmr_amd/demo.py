@@ -152,7 +152,9 @@ def main(argv=None):
     was detected); --save_rotating_video 1 adds ``<image>_<model>_rotating.png`` (animated, when somebody was detected); --distance 1
     writes every person's distance from the camera on the overlay panel; --save_mesh 1 adds ``<image>_<model>.png.npy`` (float32
     [P, V, 3], the persons' vertices) and ``<image>_<model>.png.glb`` (``scene.create_scene``: the persons in the overlay's colours,
-    the photograph and the camera).  ``--batch_size N`` > 1 infers N images per forward (``pipeline.predict_images``) and draws each
+    the photograph and the camera); --save_masks 1 adds ``<image>_<model>_mask.png`` (per pixel the person's index + 1, 0 = background;
+    8-bit up to 255 persons, 16-bit beyond) and ``<image>_<model>_parts.png`` (the body part + 1 of ``constants.SMPLX_BODY_PARTS``, 0 =
+    background), both at the photograph's size (``maps.render_maps``), and prints each person's occlusion.  ``--batch_size N`` > 1 infers N images per forward (``pipeline.predict_images``) and draws each
     result as before.  ``--video 1`` treats the sorted folder as the consecutive frames of one clip (``pipeline.predict_video`` at
     ``--batch_size``, 32 when that is 1, and ``--fps``): the persons are tracked and smoothed across the frames and every mesh is
     coloured by ``track_id % len(PALETTE)``, so a person keeps their colour.  Returns every path written."""
@@ -172,6 +174,8 @@ def main(argv=None):
     parser.add_argument("--save_rotating_video", type=int, default=0, choices=[0, 1])
     parser.add_argument("--distance", type=int, default=0, choices=[0, 1])
     parser.add_argument("--save_mesh", type=int, default=0, choices=[0, 1])
+    parser.add_argument("--save_masks", type=int, default=0, choices=[0, 1], help="1: instance mask and body-part PNGs, and each "
+                        "person's occlusion on the terminal")
     parser.add_argument("--batch_size", type=int, default=1, help="> 1: decode, preprocess and infer that many images per forward "
                         "(pipeline.predict_images); the files written are the same")
     parser.add_argument("--video", type=int, default=0, choices=[0, 1], help="1: the sorted folder is one clip (pipeline.predict_video): "
@@ -225,6 +229,22 @@ def main(argv=None):
             scene = create_scene(img_pil_visu, l_mesh, [faces for _ in humans], color=cols, metallicFactor=0., roughnessFactor=0.5, K=K)
             scene.export(save_fn + ".glb")
             written.extend([save_fn + ".npy", save_fn + ".glb"])
+
+        if args.save_masks:
+            from .maps import render_maps
+            name = "verts_smplx" if humans and "verts_smplx" in humans[0] else "v3d"
+            V = int(model.smpl_layer["neutral_10"].bm_x.num_vertices)
+            verts = _stacked([h[name] for h in humans]) if humans else torch.zeros(0, V, 3, device="cuda")
+            size = (img_pil_visu.size[1], img_pil_visu.size[0])
+            m = render_maps(verts, torch.zeros(len(humans), dtype=torch.int32), torch.as_tensor(K)[:1].detach().float(), faces, size,
+                            face_labels=model.face_part_labels())
+            stem = os.path.splitext(save_fn)[0]
+            ids = (m.person[0] + 1).cpu().numpy()
+            Image.fromarray(ids.astype(np.uint8 if len(humans) <= 255 else np.uint16)).save(stem + "_mask.png")
+            Image.fromarray(((m.label[0].to(torch.int32) + 1) % 256).cpu().numpy().astype(np.uint8)).save(stem + "_parts.png")
+            for j, (o, v, a) in enumerate(zip(m.occlusion.tolist(), m.visible_px.tolist(), m.amodal_px.tolist())):
+                print(f"  person {j}: occlusion {o:.3f} ({v} of {a} px visible)")
+            written.extend([stem + "_mask.png", stem + "_parts.png"])
 
     if args.video:                                                       # the folder is one clip: track, smooth, one colour per track
         from .pipeline import predict_video

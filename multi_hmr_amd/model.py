@@ -727,6 +727,16 @@ class Model(nn.Module):
         from . import heads
         return heads.decode_readout(self, readout, offset, idx, K)
 
+    def face_part_labels(self):
+        """uint8 [F]: the body part (``constants.SMPLX_BODY_PARTS.names``) of every face of the model's own SMPL-X layer, from its skinning
+        weights (``maps.part_labels``); what ``maps.render_maps(face_labels=...)`` takes.  Computed once, on the host."""
+        if getattr(self, "_face_parts", None) is None:
+            from .constants import SMPLX_BODY_PARTS
+            from .maps import part_labels
+            faces = next(iter(self.smpl_layer.values())).bm_x.faces
+            self._face_parts = part_labels(np.asarray(self._smplx_data["weights"]), faces, groups=SMPLX_BODY_PARTS.joint_part)
+        return self._face_parts
+
     def _body_model(self):
         """The fp32 body model of the prediction's parameters (built on first use: only ``decode_readout``'s backward needs it)."""
         if getattr(self, "_bm32", None) is None:

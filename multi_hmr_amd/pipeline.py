@@ -225,8 +225,26 @@ class _Stages:
             gen.close()
 
 
+OCCLUSION_KEYS = ("visible_px", "amodal_px", "occlusion", "bbox_visible")
+
+
+def add_occlusion(model, persons, verts, image_index, K, size):
+    """Adds ``OCCLUSION_KEYS`` to the person dicts of one batch (``persons`` in the row order of ``verts`` [P, V, 3] and ``image_index``
+    [P]): one ``maps.render_maps`` call with geometry only, in the model-input camera ``K`` [B, 3, 3] at ``size`` x ``size`` pixels.
+    ``visible_px`` / ``amodal_px`` (int32 scalars), ``occlusion`` (float32 scalar: the share of the person hidden behind others) and
+    ``bbox_visible`` (int32 [4]: x0, y0, x1, y1 inclusive; W, H, -1, -1 when nothing is visible) are device tensors."""
+    if not persons:
+        return
+    from .maps import render_maps
+    faces = next(iter(model.smpl_layer.values())).bm_x.faces
+    m = render_maps(verts, image_index, K, faces, (size, size))
+    cols = [t.unbind(0) for t in (m.visible_px, m.amodal_px, m.occlusion, m.bbox)]
+    for h, vals in zip(persons, zip(*cols)):
+        h.update(zip(OCCLUSION_KEYS, vals))
+
+
 def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_kernel_size=3, workers=DEFAULT_WORKERS,
-                   on_error="raise", stats=None):
+                   on_error="raise", stats=None, occlusion=False):
     """Generator of one ``ImageResult`` per source, in input order.  ``sources``: file paths, PIL images or uint8 ``[H, W, 3]``
     arrays, in any mix; any iterable, an iterator of unknown length (video frames) included.  One ``Model.forward`` per
     ``batch_size`` images (the last batch at its own size), ``r.humans`` = that image's person dicts.  ``r.K`` is the camera of the
@@ -235,7 +253,9 @@ def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_ke
     Runs on the model's device, and all of it -- every batch's preprocessing and forward -- on ONE stream: the one that is current
     when the iteration starts, whatever the caller makes current between two results.  ``stats``: a dict that receives the seconds spent per stage
     (``decode`` summed over the worker threads, ``stage`` = packing + enqueueing on the producer thread, ``forward`` and ``wait`` =
-    the consumer waiting for a staged batch) and the counts ``images`` / ``batches``."""
+    the consumer waiting for a staged batch) and the counts ``images`` / ``batches``.  ``occlusion=True`` adds ``visible_px``,
+    ``amodal_px``, ``occlusion`` and ``bbox_visible`` to every person dict (``add_occlusion``: one ``maps.render_maps`` call per batch,
+    in the model-input camera ``r.K``); the other keys are untouched."""
     import time
     import torch
     from .preprocess import get_camera_parameters
@@ -249,6 +269,9 @@ def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_ke
             K = get_camera_parameters(S, fov=fov, device=dev, batch=B)
             humans, ids = model(x, is_training=False, nms_kernel_size=int(nms_kernel_size), det_thresh=det_thresh, K=K,
                                 return_image_index=True)
+            if occlusion and humans:
+                from .demo import _stacked
+                add_occlusion(model, humans, _stacked([h["v3d"] for h in humans]), ids, K, S)
         per_image = [[] for _ in range(B)]
         for h, i in zip(humans, ids.tolist()):
             per_image[i].append(h)
@@ -261,7 +284,7 @@ def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_ke
 
 
 def predict_video(model, frames, batch_size=32, tracker=None, fov=60, det_thresh=0.3, nms_kernel_size=3, workers=DEFAULT_WORKERS,
-                  on_error="raise", stats=None):
+                  on_error="raise", stats=None, occlusion=False):
     """``predict_images`` for the consecutive frames of one clip: the same sources, batching, stream, ``ImageResult`` and ``stats``, with the
     persons TRACKED and SMOOTHED across frames and batches.  Per batch: one ``Model.forward`` (``return_batched=True,
     return_readout=True``), one ``Tracker.update`` and one ``decode_readout`` of the filtered rows.  Every person dict holds the ten
@@ -297,10 +320,14 @@ def predict_video(model, frames, batch_size=32, tracker=None, fov=60, det_thresh
                 cols, Pn, host = [], 0, res.status.tolist()
             if host[0] != 0:
                 raise RuntimeError(f"Tracker.update refused the batch (status {host[0]}): the image ids of the forward are not ascending")
+            rows = []
             for p, vals in enumerate(zip(*cols)):
                 h = dict(zip(keys, vals))
                 h["track_id"], h["hits"] = host[1 + Pn + p], host[1 + 2 * Pn + p]
                 per_image[host[1 + p]].append(h)
+                rows.append(h)
+            if occlusion and rows:
+                add_occlusion(model, rows, dec["v3d"].detach(), ids, K, S)
         st["forward"] += time.perf_counter() - t0
         st["batches"] += 1
         st["images"] += B
