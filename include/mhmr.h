@@ -21,7 +21,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_pre_image_o, mhmr_preprocess_u8_batch_oriented; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points; mhmr_vit_plan; mhmr_render_maps_desc, mhmr_render_maps, mhmr_point_visibility_desc, mhmr_render_point_visibility, mhmr_render_amodal_workspace_bytes, mhmr_render_amodal); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
+#define MHMR_VERSION 106   /* 106 (later, additive: mhmr_pre_image, mhmr_preprocess_u8_batch; mhmr_pre_image_o, mhmr_preprocess_u8_batch_oriented; mhmr_render_desc, mhmr_render_workspace_bytes, mhmr_render_meshes; mhmr_hph_self_attn, mhmr_hph_cross_attn, mhmr_hph_decode; mhmr_render_views_workspace_bytes, mhmr_render_views; mhmr_scene_pack; mhmr_body_consts, mhmr_body_forward, mhmr_sparse_regress, mhmr_gt_targets, mhmr_rotvec_to_rotmat, mhmr_project_points; mhmr_vit_plan; mhmr_render_maps_desc, mhmr_render_maps, mhmr_point_visibility_desc, mhmr_render_point_visibility, mhmr_render_amodal_workspace_bytes, mhmr_render_amodal; mhmr_contact_desc, mhmr_contact_workspace_bytes, mhmr_contact_check_faces, mhmr_contact); 106: mhmr_attention16_ex variant 10 (class query on workgroups of its own; opt-in); the fc1 epilogue's GELU is max(x,0) - |x| exp2(P5(|x|)) (6.4e-7 absolute; was Abramowitz-Stegun 7.1.25, 2.6e-5); 105: mhmr_vit_desc.cls_pstats (row statistics inside the class-row launches); mhmr_vit_desc.v16 (merged qkv launch of a short batch); mhmr_vit_desc.cpad (ViT-S on the 256x256 kernel: C-wide linears as N = 512 with masked columns); mhmr_vit_desc.{splitk, splitk_bytes}, mhmr_splitk_workspace_bytes, mhmr_gemm16_splitk_resid: split-k residual linears for launches that fill less than half the chip (a batch of one); 104: mhmr_vit_desc.{x3, qkv32, hid32}: the f16x3 precision mode (three 16-bit products per term in every backbone linear, fp32 attention); mhmr_gemm16_ex a_k with K = 3 a_k; mhmr_attention_f32; 103: mhmr_attention16_ex variant 6 (the default of mhmr_vit_forward); mhmr_camera_embed(num_bands), mhmr_hph_desc.cam_dim; mhmr_lbs_consts.basis16 layout (high halves for k < Kb - 64); mhmr_person_groups, mhmr_detect_write_cap, mhmr_hph_desc.nvalid (no host round trip for the person set; group / chunk counts of mhmr_hph_forward are upper bounds); 102: mhmr_lbs_consts: extra joints as virtual vertex tiles (Vl, xbary); 101: class token LAST in the token rows, mhmr_vit_block.{v_w2,proj_w2}, mhmr_gemm16_ex, mhmr_cls_linear16, mhmr_attention16_ex variants 4 / 5 */
 
 #define MHMR_OK 0
 #define MHMR_ERR_BAD_ARG (-1)
@@ -1166,6 +1166,90 @@ int mhmr_render_point_visibility(const mhmr_point_visibility_desc* d, void* stre
  * size.  P == 0 launches nothing. */
 long long mhmr_render_amodal_workspace_bytes(const mhmr_render_desc* d, int nviews, int persons_per_pass);
 int mhmr_render_amodal(const mhmr_render_desc* d, int nviews, const float* view_Rt, int* amodal_px, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Contacts between persons: signed distances from every vertex to the other persons' surfaces, penetration and
+ * contact counts (csrc/contact.hip; multi_hmr_amd/contact.py is the Python surface, tests/contact_oracle.py the
+ * numpy restatement).  This comment is the contract.
+ * Inputs.  verts [P][V][3] fp32, person p's vertex n at verts[p * vstride + 3 n + axis], vstride >= 3 V (the
+ * forward's v3d block is read in place, as mhmr_point_visibility_desc.pstride); image_index [P]; faces [F][3] int32,
+ * shared by all persons; the margins max_dist >= 0 (finite) and 0 <= tau <= max_dist, in metres.  Both margins are
+ * CONVENTIONS of the caller, not measurements: max_dist is how far the search looks, tau what counts as touching.
+ * Validity and boxes.  A person is valid when every coordinate is finite.  aabb[p] = (min xyz, max xyz) in fp32
+ * (comparisons only: exact).  An invalid person takes no part, neither as a nor as b, has the empty values below,
+ * valid[p] = 0 and aabb[p] = (+inf x 3, -inf x 3).
+ * Pairs.  The ordered pair (a, b) is evaluated iff a != b, both are valid, image_index[a] == image_index[b], and the
+ * two boxes, EACH inflated by max_dist (lo - max_dist, hi + max_dist: one fp32 operation per bound), intersect:
+ * lo_a' <= hi_b' and lo_b' <= hi_a' on every axis.  Inside an evaluated pair, vertex v of a is evaluated iff
+ * lo_b' <= v <= hi_b' on every axis; every other vertex is "farther than max_dist" from b.  The cull is part of the
+ * result (the corner regions of the inflated box are farther than max_dist and are dropped by the s <= max_dist rule
+ * below; nothing nearer than max_dist is ever culled).
+ * Faces.  A face whose fp32 normal (b - a) x (c - a), every difference and product rounded on its own
+ * (n_x = fl(fl(u_y v_z) - fl(u_z v_y)) and cyclic), is the zero vector is skipped for the distance and for the
+ * winding number; so is, on the device, a face with an index outside [0, V) (it is never dereferenced).
+ * mhmr_contact cannot read device memory before a launch: mhmr_contact_check_faces(faces_host, F, V) is the host
+ * check, MHMR_ERR_BAD_SHAPE for an index outside [0, V); the Python layer runs it once per face array.
+ * Per evaluated (v, b), over b's non-skipped faces in ascending order:
+ *   closest point: per face by the region method (vertex / edge / interior; Ericson, Real-Time Collision Detection
+ *     5.1.5) as c_f = a + s (b - a) + t (c - a); the face's squared distance is |(v - a) - s (b - a) - t (c - a)|^2,
+ *     formed from the closest point's offset, never as a difference of squared lengths (which cancels near the
+ *     surface).  nearest face = the lowest face index attaining the smallest squared distance (the square root is
+ *     monotone: it is the smallest distance), c = its c_f, d = sqrt of its squared distance.
+ *   winding number: w = (1 / 4 pi) sum_f 2 atan2(A . (B x C), |A||B||C| + (A . B)|C| + (B . C)|A| + (C . A)|B|), A, B,
+ *     C the face's corners minus v.  The kernel splits the faces over eight waves (wave k takes the k-th eighth of
+ *     every tile of 512 faces, ascending) and adds the eight partial sums in the order ((w0 + w1) + w2) + ... + w7.
+ *   v is INSIDE b iff lo_b <= v <= hi_b on every axis (the UN-inflated box) and |w| > 0.5.  The absolute value makes
+ *     a mirrored (inward-oriented) mesh behave like the upright one; the box test costs nothing for a mesh without
+ *     boundary edges (w = 0 outside its convex hull) and saves the sum for every vertex beside the box.
+ *   signed distance: s = inside ? -d : d.
+ * Outputs.  Every output is optional (NULL = skipped) and initialised inside the call:
+ *   sdf [P][V] fp32               the smallest s over the evaluated b, if <= max_dist            else +inf
+ *   nearest_person [P][V] int32   that b (b ascending, strict <: the lowest b on a tie)           else -1
+ *   nearest_face [P][V] int32     its nearest face                                               else -1
+ *   closest [P][V][3] fp32        its closest point c                                            else the vertex itself
+ *   penetration_depth [P] fp32    max_v max(0, -sdf)                                             0
+ *   inside_count [P] int32        vertices with sdf < 0                                          0
+ *   contact_count [P] int32       vertices with |sdf| <= tau                                     0
+ *   pair_distance [P][P] fp32     [a][b]: smallest s of a's evaluated vertices against b,
+ *                                 kept only when <= max_dist (NOT symmetric: vertex-to-surface
+ *                                 from a's side)                                                 else +inf
+ *   pair_inside [P][P] int32      [a][b]: vertices of a inside b                                 0
+ *   aabb [P][6] fp32, valid [P] uint8   as above
+ * Determinism.  Per-vertex results come from one fixed-order loop; per-person and per-pair results are reduced with
+ * integer add / min / max only (floats through an integer whose order is theirs): two calls give the same bits.
+ * Call.  Everything goes to `stream`; no host synchronisation, no allocation, no host-built pair list (a workgroup
+ * decides from the device-side boxes whether it has work).  workspace: mhmr_contact_workspace_bytes(P, V) bytes (the
+ * boxes and, per person, the ascending list of the vertices that lie in some partner's inflated box: about 36 + 4 V
+ * bytes per person), contents irrelevant on entry.  P == 0 launches nothing; P > 0 with no evaluated pair
+ * is legal.  NULL descriptor, a needed pointer NULL, a negative, NaN or infinite margin or tau > max_dist:
+ * MHMR_ERR_BAD_ARG.  P, V or F < 0, P V >= 2^31, P^2 >= 2^31, vstride < 3 V, a workspace too small:
+ * MHMR_ERR_BAD_SHAPE.  All of it is checked before the first launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int P, V, F;
+    const float* verts;
+    long long vstride;
+    const int* image_index;
+    const int* faces;
+    float max_dist, tau;
+    void* workspace;
+    long long workspace_bytes;
+    float* sdf;
+    int* nearest_person;
+    int* nearest_face;
+    float* closest;
+    float* penetration_depth;
+    int* inside_count;
+    int* contact_count;
+    float* pair_distance;
+    int* pair_inside;
+    float* aabb;
+    unsigned char* valid;
+} mhmr_contact_desc;
+
+long long mhmr_contact_workspace_bytes(int P, int V);
+int mhmr_contact_check_faces(const int* faces_host, int F, int V);
+int mhmr_contact(const mhmr_contact_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Scene packing for the 3D export (reference utils/render.py:62-173 create_scene, demo.py:371-384): P meshes

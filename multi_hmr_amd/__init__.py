@@ -3,6 +3,7 @@ from .model import Model  # noqa: F401
 from .demo import create_rotating_video, forward_model, get_camera_parameters, load_model, open_image, overlay_human_meshes  # noqa: F401
 from .render import render_batch, render_meshes, render_views  # noqa: F401
 from .maps import RenderMaps, part_labels, render_maps  # noqa: F401
+from .contact import Contacts, contacts, penetration_loss  # noqa: F401
 from .scene import create_scene, export_batch, get_bbox, pack_meshes, print_distance_on_image, read_glb  # noqa: F401
 
 from .preprocess import Preprocessor  # noqa: F401
@@ -24,5 +25,5 @@ from .data import BEDLAM, EHF, THREEDPW, AnnotatedImages, TrainLoader  # noqa: F
 __all__ = ["BodyModel", "COCO17", "OPENPOSE_BODY25", "FitResult", "KeypointFitter", "fit", "keypoints_by_name", "Evaluator", "GroundTruth", "HeadsAdam", "ModelAdam", "encoder_segments", "Loss", "Model", "Trainer", "GraphedForward", "SparseRegressor", "evaluate_dataset", "load_body_data",
            "load_h36m_regressor", "load_smplx2smpl", "loss_and_grads", "ImageResult", "PipelineError", "Preprocessor", "create_rotating_video", "create_scene", "export_batch", "forward_model", "get_bbox",
            "get_camera_parameters", "heads", "load_model", "open_image", "overlay_human_meshes", "pack_meshes", "predict_images", "predict_video", "print_distance_on_image",
-           "read_glb", "render_batch", "render_meshes", "render_views", "RenderMaps", "part_labels", "render_maps",
+           "read_glb", "render_batch", "render_meshes", "render_views", "RenderMaps", "part_labels", "render_maps", "Contacts", "contacts", "penetration_loss",
            "TrackResult", "Tracker", "track", "AnnotatedImages", "BEDLAM", "EHF", "THREEDPW", "TrainLoader"]

@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "render_maps.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "render_maps.hip", "contact.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "vit_plan.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", "render_shared.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -56,6 +56,8 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: encoder_pack.hip: the LayerNorm fold is one fp32 multiply and the low half one fp32 subtraction, as vit.pack_block rounds them.
 #: fit.hip: its update kernel runs optim.hip's Adam element (csrc/adam_element.h) and must round it the same way.
 #: track.hip: the association cost and the One-Euro recursion are rounded operation by operation (the tests restate them in numpy).
+#: contact.hip is NOT here: its distances and winding sums are compared with fp64 by tolerance and gain from fused multiply-adds; the
+#: one expression whose zero is part of its contract (the face normal) is formed under `#pragma clang fp contract(off)` in the source.
 EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "render_maps.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
                "optim.hip": ["-ffp-contract=off"], "encoder_pack.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"],
                "track.hip": ["-ffp-contract=off"]}
@@ -207,6 +209,18 @@ class PointVisibilityDesc(C.Structure):
     """include/mhmr.h mhmr_point_visibility_desc."""
     _fields_ = ([(n, _i) for n in ("B", "NV", "H", "W", "P", "N")] + [("points", _vp), ("pstride", C.c_longlong)] +
                 [(n, _vp) for n in ("image_index", "K", "view_Rt", "keys")] + [("znear", _f), ("tau", _f), ("out", _vp)])
+
+
+class ContactDesc(C.Structure):
+    """include/mhmr.h mhmr_contact_desc."""
+    _fields_ = ([(n, _i) for n in ("P", "V", "F")] + [("verts", _vp), ("vstride", C.c_longlong), ("image_index", _vp), ("faces", _vp),
+                 ("max_dist", _f), ("tau", _f), ("workspace", _vp), ("workspace_bytes", C.c_longlong)] +
+                [(n, _vp) for n in ("sdf", "nearest_person", "nearest_face", "closest", "penetration_depth", "inside_count", "contact_count",
+                                    "pair_distance", "pair_inside", "aabb", "valid")])
+
+
+#: faces per LDS tile of csrc/contact.hip (its TILE): the face counts at which the kernel's tiling changes
+CONTACT_FACE_TILE = 512
 
 
 class SceneDesc(C.Structure):
@@ -473,6 +487,9 @@ _SIGS = {
     "mhmr_render_point_visibility": ([C.POINTER(PointVisibilityDesc), _vp], _i),
     "mhmr_render_amodal_workspace_bytes": ([C.POINTER(RenderDesc), _i, _i], C.c_longlong),
     "mhmr_render_amodal": ([C.POINTER(RenderDesc), _i, _vp, _vp, _vp], _i),
+    "mhmr_contact_workspace_bytes": ([_i, _i], C.c_longlong),
+    "mhmr_contact_check_faces": ([_vp, _i, _i], _i),
+    "mhmr_contact": ([C.POINTER(ContactDesc), _vp], _i),
     "mhmr_scene_pack": ([C.POINTER(SceneDesc), _vp], _i),
     "mhmr_loss_workspace_bytes": ([], C.c_longlong),
     "mhmr_loss_forward": ([C.POINTER(LossDesc), _vp, C.c_longlong, _vp, _vp], _i),

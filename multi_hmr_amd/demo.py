@@ -146,6 +146,9 @@ def create_rotating_video(humans, faces, K, model, img_pil_visu, unique_color=Fa
     return frames
 
 
+CONTACT_TAU = 0.01   # contact.contacts' default tau: what --contacts 1 calls touching
+
+
 def main(argv=None):
     """demo.py:231-386: every image of --img_folder -> forward -> overlay -> ``<out_folder>/<image>_<model>.png`` = [input | overlay],
     or [input | overlay | view] with --extra_views 1 (the persons turned 30 degrees about y, over white; a white panel where nobody
@@ -154,7 +157,8 @@ def main(argv=None):
     [P, V, 3], the persons' vertices) and ``<image>_<model>.png.glb`` (``scene.create_scene``: the persons in the overlay's colours,
     the photograph and the camera); --save_masks 1 adds ``<image>_<model>_mask.png`` (per pixel the person's index + 1, 0 = background;
     8-bit up to 255 persons, 16-bit beyond) and ``<image>_<model>_parts.png`` (the body part + 1 of ``constants.SMPLX_BODY_PARTS``, 0 =
-    background), both at the photograph's size (``maps.render_maps``), and prints each person's occlusion.  ``--batch_size N`` > 1 infers N images per forward (``pipeline.predict_images``) and draws each
+    background), both at the photograph's size (``maps.render_maps``), and prints each person's occlusion; --contacts 1 prints the image's touching
+    pairs of persons (symmetric pair distance <= 0.01 m) and each person's penetration depth (``contact.contacts``) and writes nothing.  ``--batch_size N`` > 1 infers N images per forward (``pipeline.predict_images``) and draws each
     result as before.  ``--video 1`` treats the sorted folder as the consecutive frames of one clip (``pipeline.predict_video`` at
     ``--batch_size``, 32 when that is 1, and ``--fps``): the persons are tracked and smoothed across the frames and every mesh is
     coloured by ``track_id % len(PALETTE)``, so a person keeps their colour.  Returns every path written."""
@@ -176,6 +180,8 @@ def main(argv=None):
     parser.add_argument("--save_mesh", type=int, default=0, choices=[0, 1])
     parser.add_argument("--save_masks", type=int, default=0, choices=[0, 1], help="1: instance mask and body-part PNGs, and each "
                         "person's occlusion on the terminal")
+    parser.add_argument("--contacts", type=int, default=0, choices=[0, 1], help="1: each image's touching pairs of persons and every "
+                        "person's penetration depth on the terminal (contact.contacts at its default margins)")
     parser.add_argument("--batch_size", type=int, default=1, help="> 1: decode, preprocess and infer that many images per forward "
                         "(pipeline.predict_images); the files written are the same")
     parser.add_argument("--video", type=int, default=0, choices=[0, 1], help="1: the sorted folder is one clip (pipeline.predict_video): "
@@ -245,6 +251,17 @@ def main(argv=None):
             for j, (o, v, a) in enumerate(zip(m.occlusion.tolist(), m.visible_px.tolist(), m.amodal_px.tolist())):
                 print(f"  person {j}: occlusion {o:.3f} ({v} of {a} px visible)")
             written.extend([stem + "_mask.png", stem + "_parts.png"])
+
+        if args.contacts and humans:
+            from .contact import contacts
+            name = "verts_smplx" if "verts_smplx" in humans[0] else "v3d"
+            c = contacts(_stacked([h[name] for h in humans]), [0] * len(humans), faces,
+                         want=("penetration_depth", "inside_count", "contact_count", "pair_distance"))
+            pd = torch.minimum(c.pair_distance, c.pair_distance.T).tolist()
+            pairs = [(i, j) for i in range(len(humans)) for j in range(i + 1, len(humans)) if pd[i][j] <= CONTACT_TAU]
+            print("  touching: " + (", ".join(f"{i}-{j} ({pd[i][j]:+.3f} m)" for i, j in pairs) if pairs else "nobody"))
+            for j, (d, ni, nc) in enumerate(zip(c.penetration_depth.tolist(), c.inside_count.tolist(), c.contact_count.tolist())):
+                print(f"  person {j}: penetration depth {d:.3f} m ({ni} vertices inside another person, {nc} in contact)")
 
     if args.video:                                                       # the folder is one clip: track, smooth, one colour per track
         from .pipeline import predict_video

@@ -243,8 +243,38 @@ def add_occlusion(model, persons, verts, image_index, K, size):
         h.update(zip(OCCLUSION_KEYS, vals))
 
 
+CONTACT_KEYS = ("penetration_depth", "inside_vertices", "contact_vertices", "contact_with")
+
+
+def add_contacts(model, persons, verts, image_index, max_dist=0.10, tau=0.01):
+    """Adds ``CONTACT_KEYS`` to the person dicts of one batch (``persons`` in the row order of ``verts`` [P, V, 3] and ``image_index``
+    [P]): one ``contact.contacts`` call and one copy to the host.  ``penetration_depth`` (float, metres: how deep the person's deepest
+    vertex lies inside another person), ``inside_vertices`` and ``contact_vertices`` (int: vertices inside another person, and within
+    ``tau`` of another person's surface) and ``contact_with`` (the indices, within the image's ``humans`` list, of the persons whose
+    symmetric pair distance is <= ``tau``).  The margins are conventions (``contact.contacts``)."""
+    if not persons:
+        return
+    import torch
+    from .contact import contacts as _contacts
+    faces = next(iter(model.smpl_layer.values())).bm_x.faces
+    c = _contacts(verts, image_index, faces, max_dist=max_dist, tau=tau,
+                  want=("penetration_depth", "inside_count", "contact_count", "pair_distance"))
+    P = len(persons)
+    ids = torch.as_tensor(image_index).reshape(-1).to(c.pair_distance.device)
+    touching = torch.minimum(c.pair_distance, c.pair_distance.T) <= tau
+    host = torch.cat([c.penetration_depth.double(), c.inside_count.double(), c.contact_count.double(), ids.double(),
+                      touching.double().reshape(-1)]).tolist()                                      # the one copy to the host
+    pen, nin, nct, img, touch = host[:P], host[P:2 * P], host[2 * P:3 * P], host[3 * P:4 * P], host[4 * P:]
+    first = {}
+    for p in range(P):                                                  # a person's index within their image: rows of one image are in order
+        first.setdefault(img[p], []).append(p)
+    rank = {p: j for rows in first.values() for j, p in enumerate(rows)}
+    for p, h in enumerate(persons):
+        h.update(zip(CONTACT_KEYS, (pen[p], int(nin[p]), int(nct[p]), [rank[q] for q in first[img[p]] if touch[p * P + q]])))
+
+
 def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_kernel_size=3, workers=DEFAULT_WORKERS,
-                   on_error="raise", stats=None, occlusion=False):
+                   on_error="raise", stats=None, occlusion=False, contacts=False):
     """Generator of one ``ImageResult`` per source, in input order.  ``sources``: file paths, PIL images or uint8 ``[H, W, 3]``
     arrays, in any mix; any iterable, an iterator of unknown length (video frames) included.  One ``Model.forward`` per
     ``batch_size`` images (the last batch at its own size), ``r.humans`` = that image's person dicts.  ``r.K`` is the camera of the
@@ -255,7 +285,9 @@ def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_ke
     (``decode`` summed over the worker threads, ``stage`` = packing + enqueueing on the producer thread, ``forward`` and ``wait`` =
     the consumer waiting for a staged batch) and the counts ``images`` / ``batches``.  ``occlusion=True`` adds ``visible_px``,
     ``amodal_px``, ``occlusion`` and ``bbox_visible`` to every person dict (``add_occlusion``: one ``maps.render_maps`` call per batch,
-    in the model-input camera ``r.K``); the other keys are untouched."""
+    in the model-input camera ``r.K``); the other keys are untouched.  ``contacts=True`` adds ``penetration_depth``, ``inside_vertices``,
+    ``contact_vertices`` and ``contact_with`` (``add_contacts``: one ``contact.contacts`` call per batch, at its default margins); the other
+    keys are untouched."""
     import time
     import torch
     from .preprocess import get_camera_parameters
@@ -272,6 +304,9 @@ def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_ke
             if occlusion and humans:
                 from .demo import _stacked
                 add_occlusion(model, humans, _stacked([h["v3d"] for h in humans]), ids, K, S)
+            if contacts and humans:
+                from .demo import _stacked
+                add_contacts(model, humans, _stacked([h["v3d"] for h in humans]), ids)
         per_image = [[] for _ in range(B)]
         for h, i in zip(humans, ids.tolist()):
             per_image[i].append(h)
@@ -284,13 +319,13 @@ def predict_images(model, sources, batch_size=32, fov=60, det_thresh=0.3, nms_ke
 
 
 def predict_video(model, frames, batch_size=32, tracker=None, fov=60, det_thresh=0.3, nms_kernel_size=3, workers=DEFAULT_WORKERS,
-                  on_error="raise", stats=None, occlusion=False):
+                  on_error="raise", stats=None, occlusion=False, contacts=False):
     """``predict_images`` for the consecutive frames of one clip: the same sources, batching, stream, ``ImageResult`` and ``stats``, with the
     persons TRACKED and SMOOTHED across frames and batches.  Per batch: one ``Model.forward`` (``return_batched=True,
     return_readout=True``), one ``Tracker.update`` and one ``decode_readout`` of the filtered rows.  Every person dict holds the ten
     ``Model.PERSON_KEYS`` of the smoothed person (``scores`` is the detection's) plus ``track_id`` (int; -1: the tracker's table was full)
     and ``hits`` (int; frames the track has been seen in).  ``tracker``: a ``Tracker`` of this model (its table persists, so a second clip
-    needs ``tracker.reset()``); ``None``: ``Tracker(model)``.  A ``Tracker(model, smooth=None)`` only tracks: the persons are
+    needs ``tracker.reset()``); ``None``: ``Tracker(model)``.  ``occlusion`` and ``contacts`` as in ``predict_images``, of the smoothed persons.  A ``Tracker(model, smooth=None)`` only tracks: the persons are
     ``predict_images``' bit for bit.  The ids go to the host in one copy per batch, and the tracker's ``status`` is checked there (it raises
     ``RuntimeError``).  A source that ``on_error="skip"`` skips is not shown to the tracker: for it no time passes."""
     import time
@@ -328,6 +363,8 @@ def predict_video(model, frames, batch_size=32, tracker=None, fov=60, det_thresh
                 rows.append(h)
             if occlusion and rows:
                 add_occlusion(model, rows, dec["v3d"].detach(), ids, K, S)
+            if contacts and rows:
+                add_contacts(model, rows, dec["v3d"].detach(), ids)
         st["forward"] += time.perf_counter() - t0
         st["batches"] += 1
         st["images"] += B
