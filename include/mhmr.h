@@ -1168,6 +1168,78 @@ long long mhmr_render_amodal_workspace_bytes(const mhmr_render_desc* d, int nvie
 int mhmr_render_amodal(const mhmr_render_desc* d, int nviews, const float* view_Rt, int* amodal_px, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Differentiable read-out of the keys: depth, barycentrics and interpolated vertex attributes per pixel, and their
+ * gradient with respect to the vertices and the attribute table (csrc/raster_grad.hip; multi_hmr_amd/raster.py is
+ * the Python surface, tests/raster_oracle.py the numpy / torch restatement).  This comment is the contract.
+ * Inputs.  The scene as to mhmr_render_views: verts (person p's vertex n at verts[p * vstride + 3 n + axis],
+ * vstride >= 3 V), faces [F][3], image_index [P], K [B][3][3], view_Rt [B][NV][3][4] or NULL (identity), H, W, znear,
+ * cull_back; keys [B][NV][H][W] as in mhmr_render_maps; optional per-vertex attributes attr, fp32: person p's vertex
+ * n has channel c at attr[p * astride + C n + c], C in [0, 16], astride = 0 (one table serves every person) or
+ * >= C V.
+ * Forward, per pixel (b, v, r, c), in fp64 and in the operation order of csrc/render_shared.h, every step rounded
+ * on its own:  the pixel is background exactly as in mhmr_render_maps (key ~0, person >= P, image_index[p] != b).
+ * Otherwise (p, f) = low32(key) / F, % F; X_i = view_position(R, T, x_i) of the face's corners; tri_setup and
+ * tri_cover at the centre (c + 0.5, r + 0.5) give e_i; w_i = (e_i / area) / Z_i, Z = 1 / ((w0 + w1) + w2),
+ * b_i = w_i Z (the perspective-correct barycentrics).  The pixel is STALE when the setup fails, the pixel lies
+ * outside the face's pixel box or its centre is not covered, or a face index is outside [0, V) (never
+ * dereferenced): keys that belong to other vertices.  A stale pixel is background and contributes to no gradient;
+ * it is never an error and never a division by zero.
+ * Outputs, each optional (NULL = skipped), 0 at background pixels:
+ *   depth    [B][NV][H][W]     fp32  (float)Z: for keys rendered from these vertices, the key's high word bit for bit
+ *   bary     [B][NV][H][W][3]  fp32  (float)b_i
+ *   out_attr [B][NV][H][W][C]  fp32  (float)((b0 a0c + b1 a1c) + b2 a2c)
+ * Backward (mhmr_raster_backward): the derivative of exactly that map with the keys held fixed and K, Rt constant.
+ * Cotangents g_depth, g_bary, g_out_attr in the outputs' layouts, each optional (NULL = zero); at background and
+ * stale pixels they are NOT READ (a NaN there changes no bit).  Per owned pixel, with g^_i = g_bary_i +
+ * sum_c g_out_attr_c a_ic and M = [X0 X1 X2]:  g_w_i = Z (g^_i - sum_j g^_j b_j) - g_depth Z^2,  M^T h = g_w,
+ * g_X_i = -w_i h,  g_x_i = R^T g_X_i,  g_a_ic = b_i g_out_attr_c.
+ * Results g_verts [P][V][3] and g_attr [P][V][C] (optional), fp32, contiguous, every element written: zero for a
+ * vertex no owned pixel touches and for a person whose image_index is outside [0, B).  The sums over pixels,
+ * incident faces (ascending, as adj) and views (ascending) are fp64 in an order fixed by the shapes and the keys
+ * (not by scheduling) and rounded to fp32 once: two calls give the same bits.  No floating-point atomics.
+ * adj_off [V + 1], adj: vertex -> incident 3 f + corner entries, ascending (as mhmr_render_desc); read by the
+ * backward only.  The backward takes persons in passes of as many as the workspace holds (9 + 3 C doubles per face
+ * and view, and a list of the faces with a large pixel box): mhmr_raster_workspace_bytes(d, n) is what passes of n
+ * persons need, linear in n and independent of P; the result does not depend on the pass size.
+ * Refused before any launch: B NV > 65535, P F or NV P F >= 2^32 - 1, P V >= 2^31, C outside [0, 16], astride
+ * between 1 and C V - 1, a workspace too small for one person per pass (MHMR_ERR_BAD_SHAPE); znear <= 0, a missing
+ * pointer, attr present without an attribute output (forward: out_attr; backward: g_out_attr or g_attr) or absent
+ * with one (MHMR_ERR_BAD_ARG).  P == 0 is legal: the forward launches only the background fill, the backward
+ * nothing.  No allocation, no synchronisation; the launches go to `stream`.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, NV, H, W;
+    int P, V, F, C;
+    const float* verts;
+    long long vstride;
+    const int* faces;
+    const int* adj_off;
+    const int* adj;
+    const int* image_index;
+    const float* K;
+    const float* view_Rt;
+    const unsigned long long* keys;
+    const float* attr;
+    long long astride;
+    float znear;
+    int cull_back;
+    float* depth;
+    float* bary;
+    float* out_attr;
+    const float* g_depth;
+    const float* g_bary;
+    const float* g_out_attr;
+    float* g_verts;
+    float* g_attr;
+    void* workspace;
+    long long workspace_bytes;
+} mhmr_raster_desc;
+
+long long mhmr_raster_workspace_bytes(const mhmr_raster_desc* d, int persons_per_pass);
+int mhmr_raster_interpolate(const mhmr_raster_desc* d, void* stream);
+int mhmr_raster_backward(const mhmr_raster_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Contacts between persons: signed distances from every vertex to the other persons' surfaces, penetration and
  * contact counts (csrc/contact.hip; multi_hmr_amd/contact.py is the Python surface, tests/contact_oracle.py the
  * numpy restatement).  This comment is the contract.

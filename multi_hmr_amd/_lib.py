@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "render_maps.hip", "contact.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "render_maps.hip", "raster_grad.hip", "contact.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "vit_plan.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", "render_shared.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -50,6 +50,7 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: per-translation-unit extra flags.  render.hip: every step rounded on its own (the render contract's fp64 geometry and fp32 blend
 #: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  render_maps.hip: the same geometry
 #: (csrc/render_shared.h), which must agree with render.hip's bit for bit.  scene.hip: the same fp64 geometry.
+#: raster_grad.hip: the same geometry again: its depth is the key's high word bit for bit, its barycentrics are the oracle's.
 #: loss.hip: every element of the training loss is the reference's fp32 subtraction(s), rounded one by one (its sign is the gradient).
 #: optim.hip: the Adam update is torch's sequence of fp32 operations, each rounded on its own.
 #: attention_bf16.hip: the logit S = fl(QSCALE * acc) is rounded before exp2(S - lse) in all three kernels, as the contract states it.
@@ -60,7 +61,7 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: one expression whose zero is part of its contract (the face normal) is formed under `#pragma clang fp contract(off)` in the source.
 EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "render_maps.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
                "optim.hip": ["-ffp-contract=off"], "encoder_pack.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"],
-               "track.hip": ["-ffp-contract=off"]}
+               "track.hip": ["-ffp-contract=off"], "raster_grad.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -209,6 +210,18 @@ class PointVisibilityDesc(C.Structure):
     """include/mhmr.h mhmr_point_visibility_desc."""
     _fields_ = ([(n, _i) for n in ("B", "NV", "H", "W", "P", "N")] + [("points", _vp), ("pstride", C.c_longlong)] +
                 [(n, _vp) for n in ("image_index", "K", "view_Rt", "keys")] + [("znear", _f), ("tau", _f), ("out", _vp)])
+
+
+class RasterDesc(C.Structure):
+    """include/mhmr.h mhmr_raster_desc."""
+    _fields_ = ([(n, _i) for n in ("B", "NV", "H", "W", "P", "V", "F", "C")] + [("verts", _vp), ("vstride", C.c_longlong)] +
+                [(n, _vp) for n in ("faces", "adj_off", "adj", "image_index", "K", "view_Rt", "keys", "attr")] + [("astride", C.c_longlong)] +
+                [("znear", _f), ("cull_back", _i)] +
+                [(n, _vp) for n in ("depth", "bary", "out_attr", "g_depth", "g_bary", "g_out_attr", "g_verts", "g_attr", "workspace")] +
+                [("workspace_bytes", C.c_longlong)])
+
+
+RASTER_MAX_CHANNELS = 16            # include/mhmr.h mhmr_raster_desc: C in [0, 16]
 
 
 class ContactDesc(C.Structure):
@@ -487,6 +500,9 @@ _SIGS = {
     "mhmr_render_point_visibility": ([C.POINTER(PointVisibilityDesc), _vp], _i),
     "mhmr_render_amodal_workspace_bytes": ([C.POINTER(RenderDesc), _i, _i], C.c_longlong),
     "mhmr_render_amodal": ([C.POINTER(RenderDesc), _i, _vp, _vp, _vp], _i),
+    "mhmr_raster_workspace_bytes": ([C.POINTER(RasterDesc), _i], C.c_longlong),
+    "mhmr_raster_interpolate": ([C.POINTER(RasterDesc), _vp], _i),
+    "mhmr_raster_backward": ([C.POINTER(RasterDesc), _vp], _i),
     "mhmr_contact_workspace_bytes": ([_i, _i], C.c_longlong),
     "mhmr_contact_check_faces": ([_vp, _i, _i], _i),
     "mhmr_contact": ([C.POINTER(ContactDesc), _vp], _i),
