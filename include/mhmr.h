@@ -1240,6 +1240,112 @@ int mhmr_raster_interpolate(const mhmr_raster_desc* d, void* stream);
 int mhmr_raster_backward(const mhmr_raster_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Exact squared Euclidean distance and nearest-pixel maps (csrc/silhouette.hip; multi_hmr_amd/silhouette.py
+ * distance_transform is the Python surface, tests/silhouette_oracle.py the numpy restatement).  This comment is the
+ * contract.  src [N][H][W] uint8, nonzero = "on"; R = max_dist, an integer cap in pixels, 0 = no cap.  With
+ * d2(y, x) = the minimum over the on-pixels (y', x') of the map of (x - x')^2 + (y - y')^2:
+ *   dist2   [N][H][W] int32   d2, and R R + 1 where d2 > R R (R > 0)
+ *   nearest [N][H][W] int32   y' W + x' of the minimiser; when several on-pixels tie, the smallest y' W + x' among
+ *                             ALL of them
+ * Where the map has no on-pixel, or d2 > R R with R > 0: dist2 = 0x7fffffff (R == 0) or R R + 1 (R > 0), nearest =
+ * -1.  Each output is optional (NULL = skipped; with both NULL nothing is launched).  Integer arithmetic only: the
+ * result does not depend on the algorithm and is the same on every call.  The workspace holds one int32 per pixel
+ * (each pixel's nearest on-row of its own column): mhmr_distance_transform_workspace_bytes(d).
+ * 1 <= H, W <= 4096, N >= 0, N max(H, 16) < 2^31, a workspace below that answer: MHMR_ERR_BAD_SHAPE; R < 0 or
+ * R > 46340 (R R + 1 must fit), src or workspace NULL with N > 0: MHMR_ERR_BAD_ARG; both before any launch.
+ * N == 0 launches nothing.  No allocation, no synchronisation; the launches go to `stream`.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int N, H, W;
+    const unsigned char* src;
+    int max_dist;
+    int* dist2;
+    int* nearest;
+    void* workspace;
+    long long workspace_bytes;
+} mhmr_distance_transform_desc;
+
+long long mhmr_distance_transform_workspace_bytes(const mhmr_distance_transform_desc* d);
+int mhmr_distance_transform(const mhmr_distance_transform_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Silhouette term: how far each person's mesh is from lying inside, and from covering, that person's segmentation
+ * mask, and the gradient of both with respect to the vertices (csrc/silhouette.hip; multi_hmr_amd/silhouette.py
+ * silhouette_loss is the Python surface, tests/silhouette_oracle.py the numpy / torch restatement).  This comment is
+ * the contract.
+ * Inputs.  The scene as to mhmr_raster_desc with one view: B, H, W (<= 4096), P, V, F, verts (person p's vertex n at
+ * verts[p * vstride + 3 n + axis], vstride >= 3 V), faces [F][3], image_index [P], K [B][3][3], Rt [B][3][4] or
+ * NULL (identity), znear, zfar, cull_back.  mask [P][H][W] uint8 (nonzero = the person's segment); allowed
+ * [P][H][W] uint8 (where the person may project without cost; NULL = mask); sigma > 0 (pixels); robust
+ * (MHMR_FIT_L2: rho(s) = s, MHMR_FIT_GMOF: rho(s) = s / (1 + s)); R = max_dist >= 1 (pixels, integer).
+ * Projection of vertex n of person p, in fp64, every step rounded on its own (the rule of
+ * mhmr_point_visibility_desc): X = ((R0 x0 + R1 x1) + R2 x2) + t; a non-finite x or X, or Z < znear, makes the
+ * vertex unprojectable; u = fx X / Z + cx, v = fy Y / Z + cy; its pixel is (floor(v), floor(u)), and a vertex whose
+ * pixel is outside [0, H) x [0, W) is outside.  Unprojectable and outside vertices, and every vertex of a person
+ * whose image_index is outside [0, B), contribute to neither term and get gradient 0.  Below, "vertices" are the
+ * others.
+ * Term 0, "outside".  phi_p = sqrt((double)dist2) of mhmr_distance_transform of allowed[p] with cap R, sampled
+ * bilinearly on the pixel-centre grid at (su, sv) = (u - 0.5, v - 0.5) clamped to [0, W - 1] x [0, H - 1]:
+ * x0 = floor(su), x1 = min(x0 + 1, W - 1), tx = su - x0 (rows likewise), phi = (1 - ty) ((1 - tx) phi00 + tx phi10)
+ * + ty ((1 - tx) phi01 + tx phi11).  terms[p][0] = sum over the vertices of rho(phi^2 / sigma^2); counts[p][0] = how
+ * many of them have phi > 0.  Its gradient is the exact derivative of that piecewise-smooth expression through the
+ * projection, K and Rt constant (g_x = R^T g_X); along an axis whose coordinate is clamped (u - 0.5 not inside
+ * (0, W - 1)) the derivative is 0.  Occluded vertices are included: occlusion is the caller's business, through
+ * `allowed`.
+ * Term 1, "uncovered".  cover_p = the pixels mhmr_render_amodal counts for person p (same face drop, cull, coverage
+ * and znear / zfar rule).  The splat map S_p: pixel (floor(v), floor(u)) is owned by the SMALLEST index among the
+ * vertices of p that fall into it.  U_p = the pixels x with mask[p](x) != 0, x not in cover_p and
+ * d2(x, S_p) <= R R; v(x) = the owner of nearest_{S_p}(x) (mhmr_distance_transform's tie rule).  With pi(n) = (u, v)
+ * of vertex n and c(x) = (x + 0.5, y + 0.5):  terms[p][1] = sum over x in U_p of |pi(v(x)) - c(x)|^2 / sigma^2,
+ * counts[p][1] = |U_p|.  It is evaluated through per-vertex integer moments over the pixels assigned to the vertex
+ * (moments [P][V][4] int64: n, sum (2x + 1), sum (2y + 1), sum ((2x + 1)^2 + (2y + 1)^2), integer atomics):
+ * value = (n |pi|^2 - pi . (Sx, Sy) + Sq / 4) / sigma^2 and d / d pi = (2 n pi - (Sx, Sy)) / sigma^2, formed after
+ * shifting the moments, exactly and in integers, to the centre of the vertex's own pixel so that nothing cancels.
+ * THE ASSIGNMENT v(x), THE SET U_p AND THE COVER ARE HELD FIXED (as the correspondences of ICP): the gradient is that
+ * of the value with them constant, and nothing flows through coverage, K or Rt.
+ * Outputs, each optional (NULL = skipped): terms [P][2] fp64; counts [P][2] int32; g_verts [2][P][V][3] fp32, the
+ * gradient of each term on its own, every element written; and for tests and tools splat [P][H][W] int32 (the
+ * owner, -1 where no vertex falls) and moments [P][V][4] int64.  The per-person sums are fp64 in an order the
+ * shapes fix (thread t of 256 adds its vertices t, t + 256, ... ascending, then a binary tree over the threads);
+ * the gradients are rounded to fp32 once.  No floating-point atomics: two calls give the same bits.
+ * Persons are taken in passes of as many as the workspace holds (per person four int32 maps -- the transform of
+ * `allowed`, the splat map, its nearest map, the column scratch -- the coverage bits, the large-face list and the
+ * moments): mhmr_silhouette_workspace_bytes(d, n) is what passes of n persons need, linear in n and independent of
+ * P; the result does not depend on the pass size.
+ * Refused before any launch: B outside [1, 65535], H or W outside [1, 4096], P < 0, V or F < 1 or vstride < 3 V
+ * with P > 0, P F >= 2^32 - 1, P V >= 2^31, a workspace below the answer for n = 1 (MHMR_ERR_BAD_SHAPE); znear <= 0,
+ * zfar <= znear, sigma not positive and finite, robust not MHMR_FIT_*, R < 1 or > 46340, a missing pointer
+ * (MHMR_ERR_BAD_ARG).  P == 0 launches nothing.  No allocation, no synchronisation; the launches go to `stream`.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int B, H, W;
+    int P, V, F;
+    const float* verts;
+    long long vstride;
+    const int* faces;
+    const int* image_index;
+    const float* K;
+    const float* Rt;
+    float znear, zfar;
+    int cull_back;
+    const unsigned char* mask;
+    const unsigned char* allowed;
+    float sigma;
+    int robust;
+    int max_dist;
+    double* terms;
+    int* counts;
+    float* g_verts;
+    int* splat;
+    long long* moments;
+    void* workspace;
+    long long workspace_bytes;
+} mhmr_silhouette_desc;
+
+long long mhmr_silhouette_workspace_bytes(const mhmr_silhouette_desc* d, int persons_per_pass);
+int mhmr_silhouette(const mhmr_silhouette_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Contacts between persons: signed distances from every vertex to the other persons' surfaces, penetration and
  * contact counts (csrc/contact.hip; multi_hmr_amd/contact.py is the Python surface, tests/contact_oracle.py the
  * numpy restatement).  This comment is the contract.

@@ -20,6 +20,8 @@ from . import track  # noqa: F401
 from .track import TrackResult, Tracker  # noqa: F401
 from . import raster  # noqa: F401
 from .raster import Raster, depth_loss, rasterize  # noqa: F401
+from . import silhouette  # noqa: F401
+from .silhouette import Silhouette, assign_instance_masks, distance_transform, silhouette_loss  # noqa: F401
 from .optim import HeadsAdam, ModelAdam, encoder_segments  # noqa: F401
 from .train import Trainer  # noqa: F401
 from .data import BEDLAM, EHF, THREEDPW, AnnotatedImages, TrainLoader  # noqa: F401  (data.collate stays there: .collate is a module)
@@ -28,4 +30,5 @@ __all__ = ["BodyModel", "COCO17", "OPENPOSE_BODY25", "FitResult", "KeypointFitte
            "load_h36m_regressor", "load_smplx2smpl", "loss_and_grads", "ImageResult", "PipelineError", "Preprocessor", "create_rotating_video", "create_scene", "export_batch", "forward_model", "get_bbox",
            "get_camera_parameters", "heads", "load_model", "open_image", "overlay_human_meshes", "pack_meshes", "predict_images", "predict_video", "print_distance_on_image",
            "read_glb", "render_batch", "render_meshes", "render_views", "RenderMaps", "part_labels", "render_maps", "Contacts", "contacts", "penetration_loss", "Raster", "depth_loss", "rasterize",
+           "Silhouette", "assign_instance_masks", "distance_transform", "silhouette", "silhouette_loss",
            "TrackResult", "Tracker", "track", "AnnotatedImages", "BEDLAM", "EHF", "THREEDPW", "TrainLoader"]

@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmhmr.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "render_maps.hip", "raster_grad.hip", "contact.hip", "scene.hip", "loss.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "attention.hip", "attention_f32.hip", "vit_misc.hip", "vit_cls.hip", "hph.hip", "lbs.hip", "preprocess.hip", "evalm.hip", "bodymodel.hip", "bodymodel_bwd.hip", "heads_bwd.hip", "hph_bwd.hip", "detect_bwd.hip", "feature_grad.hip", "vit_bwd.hip", "linear_bf16.hip", "attention_bf16.hip", "vit_embed_bwd.hip", "optim.hip", "encoder_pack.hip", "fit.hip", "track.hip", "anny.hip", "render.hip", "render_maps.hip", "raster_grad.hip", "silhouette.hip", "contact.hip", "scene.hip", "loss.hip", "capi.hip"]
 HEADERS = ["mhmr_common.h", "mhmr_internal.h", "vit_plan.h", "ln_stats.h", "hph_shared.h", "body_shared.h", "row_sums.h", "adam_element.h", "render_shared.h", os.path.join("..", "..", "include", "mhmr.h")]
 
 VERSION = 106                       # include/mhmr.h MHMR_VERSION (struct layouts and entry-point semantics)
@@ -51,6 +51,7 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: are restated operation by operation in numpy by the tests; an FMA would change the last bit).  render_maps.hip: the same geometry
 #: (csrc/render_shared.h), which must agree with render.hip's bit for bit.  scene.hip: the same fp64 geometry.
 #: raster_grad.hip: the same geometry again: its depth is the key's high word bit for bit, its barycentrics are the oracle's.
+#: silhouette.hip: the projection of mhmr_render_point_visibility and the face setup of mhmr_render_amodal: the same pixels, the same bits.
 #: loss.hip: every element of the training loss is the reference's fp32 subtraction(s), rounded one by one (its sign is the gradient).
 #: optim.hip: the Adam update is torch's sequence of fp32 operations, each rounded on its own.
 #: attention_bf16.hip: the logit S = fl(QSCALE * acc) is rounded before exp2(S - lse) in all three kernels, as the contract states it.
@@ -61,7 +62,7 @@ COMMON_FLAGS = ["-fno-slp-vectorize", "-DMHMR_NO_SLP", "-fvisibility=hidden"]
 #: one expression whose zero is part of its contract (the face normal) is formed under `#pragma clang fp contract(off)` in the source.
 EXTRA_FLAGS = {"render.hip": ["-ffp-contract=off"], "render_maps.hip": ["-ffp-contract=off"], "scene.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
                "optim.hip": ["-ffp-contract=off"], "encoder_pack.hip": ["-ffp-contract=off"], "attention_bf16.hip": ["-ffp-contract=off"], "fit.hip": ["-ffp-contract=off"],
-               "track.hip": ["-ffp-contract=off"], "raster_grad.hip": ["-ffp-contract=off"]}
+               "track.hip": ["-ffp-contract=off"], "raster_grad.hip": ["-ffp-contract=off"], "silhouette.hip": ["-ffp-contract=off"]}
 
 
 def source_hash() -> str:
@@ -222,6 +223,23 @@ class RasterDesc(C.Structure):
 
 
 RASTER_MAX_CHANNELS = 16            # include/mhmr.h mhmr_raster_desc: C in [0, 16]
+
+
+class DistanceTransformDesc(C.Structure):
+    """include/mhmr.h mhmr_distance_transform_desc."""
+    _fields_ = [(n, _i) for n in ("N", "H", "W")] + [("src", _vp), ("max_dist", _i), ("dist2", _vp), ("nearest", _vp), ("workspace", _vp),
+                                                     ("workspace_bytes", C.c_longlong)]
+
+
+class SilhouetteDesc(C.Structure):
+    """include/mhmr.h mhmr_silhouette_desc."""
+    _fields_ = ([(n, _i) for n in ("B", "H", "W", "P", "V", "F")] + [("verts", _vp), ("vstride", C.c_longlong)] +
+                [(n, _vp) for n in ("faces", "image_index", "K", "Rt")] + [("znear", _f), ("zfar", _f), ("cull_back", _i), ("mask", _vp), ("allowed", _vp),
+                                                                          ("sigma", _f), ("robust", _i), ("max_dist", _i)] +
+                [(n, _vp) for n in ("terms", "counts", "g_verts", "splat", "moments", "workspace")] + [("workspace_bytes", C.c_longlong)])
+
+
+DISTANCE_MAX_SIDE, DISTANCE_MAX_R = 4096, 46340   # include/mhmr.h mhmr_distance_transform_desc: H, W and max_dist at most these
 
 
 class ContactDesc(C.Structure):
@@ -503,6 +521,10 @@ _SIGS = {
     "mhmr_raster_workspace_bytes": ([C.POINTER(RasterDesc), _i], C.c_longlong),
     "mhmr_raster_interpolate": ([C.POINTER(RasterDesc), _vp], _i),
     "mhmr_raster_backward": ([C.POINTER(RasterDesc), _vp], _i),
+    "mhmr_distance_transform_workspace_bytes": ([C.POINTER(DistanceTransformDesc)], C.c_longlong),
+    "mhmr_distance_transform": ([C.POINTER(DistanceTransformDesc), _vp], _i),
+    "mhmr_silhouette_workspace_bytes": ([C.POINTER(SilhouetteDesc), _i], C.c_longlong),
+    "mhmr_silhouette": ([C.POINTER(SilhouetteDesc), _vp], _i),
     "mhmr_contact_workspace_bytes": ([_i, _i], C.c_longlong),
     "mhmr_contact_check_faces": ([_vp, _i, _i], _i),
     "mhmr_contact": ([C.POINTER(ContactDesc), _vp], _i),
