@@ -107,7 +107,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             // final norm: ctx16 is the 16-bit copy OF feat32 (include/mhmr.h).  Left to itself the f16 conversion fuses with the multiply-add
             // (v_fma_mixlo_f16: ONE rounding of the exact sum), which differs from op16 of the stored fp32 value where that value sits on a
             // 16-bit tie -- one element in 2^14 by expectation, one unit in the last place (tests/test_gpu_vit_forms.py, check D)
-            if constexpr (FINAL) asm volatile("" : "+v"(ye));
+            // pair: lo must be taken against the STORED hi, so hi and lo convert the same opaque fp32 value as well (gelu_pair_kernel)
+            if constexpr (FINAL || PAIR) asm volatile("" : "+v"(ye));
             y[e] = ye;
             h[e] = (T)ye;
             if constexpr (PAIR) hl[e] = (T)(y[e] - (float)h[e]);
@@ -249,7 +250,11 @@ __global__ __launch_bounds__(256) void gelu_pair_kernel(const float* __restrict_
     V4 hi, lo;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float y = gelu_erf(v[e]);
+        float y = gelu_erf(v[e]);
+        // ONE fp32 value under both conversions.  Left to itself the compiler stores hi = op16(fl32(a b)) (v_cvt_pk_f16_f32) and takes lo
+        // against op16 of the EXACT product (v_fma_mixlo_f16): where fl32(a b) sits on an f16 tie the two differ by one unit and hi + lo is
+        // off by 2^-11 relative, one element in 2^14 (tests/test_gpu_x3_pairs.py gates every element)
+        asm volatile("" : "+v"(y));
         hi[e] = (T)y;
         lo[e] = (T)(y - (float)hi[e]);
     }
